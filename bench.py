@@ -2,8 +2,21 @@
 """Benchmark: frames/sec (track -> 3D) at 1280x1024, 169 markers (BASELINE.json).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full          # + every side measurement below
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times `--steps` steps and prints the line: metric, value, unit, ms_per_step (one timed
+step), dtype and `config` (workload, frame-0 ID check, tracked observations, NCC decision counters; the N > 1
+self-validation).  `--full` adds the side measurements (roofline, roofline_mfma, kernels, cpu_baseline and the side
+legs in `config`), each still subject to `--no-cpu-baseline` / `--no-extras`.
+
+`--dump-outputs DIR` writes what the last timed step returned to a caller on rank 0 - the tracking table [frames, M, 10],
+the displacement rows [frames, M, 5], the per-frame detection counts and, for c5, the plane fits [frames, 5] - as
+DIR/<name>.npy (float32; counts as float64).  Above 64 MB in all, a fixed seeded sample of frames is written instead, and
+DIR/<name>_frame_index.npy (float64) names the frames kept.  The inputs depend on the arguments alone (seeded), so two
+builds can be compared output for output.
 
 Workload (BASELINE config 3/4): `--frames` (default 4096) synthetic 1280x1024 gray uint8 frames PER
 GPU, 13x13 dots, resident in HBM before the timed region.  One step = one pass of the hot path over
@@ -117,6 +130,35 @@ def _band_stage_live(workload, frames=512, timeout=240):
         except Exception as e:
             return None, f"unparsable child output: {r.stdout[-200:]!r}"
     return out, None
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 20241016
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write `arrays` (name -> NumPy array, frames along axis 0) as out_dir/<name>.npy in float32 / float64.  When they
+    exceed `budget` bytes in all, every array keeps the same share of its frames, chosen by a fixed seed, and
+    out_dir/<name>_frame_index.npy holds the indices kept.  Returns {name: frames written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype.itemsize > 4 or v.dtype.kind in "iu" else np.float32)
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    share = 1.0
+    if total > budget:
+        # (an index entry of 8 bytes per frame kept, and 4 KB for the .npy headers)
+        share = (budget - 4096) / sum(v.nbytes + 8 * v.shape[0] for v in arrays.values())
+    written = {}
+    for name, v in arrays.items():
+        if share < 1.0:
+            n = v.shape[0]
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, max(1, int(n * share)), replace=False))
+            v = v[idx]
+            np.save(os.path.join(out_dir, f"{name}_frame_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+        written[name] = int(v.shape[0])
+    return written
 
 
 def _cpu_worker(args):
@@ -431,8 +473,13 @@ def avi_path_fps(n, seed, batch=256):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the side measurements: roofline, per-kernel times, CPU baseline, BGR / host / "
+                         "AVI / single-frame legs (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB: a seeded sample of frames above)")
     ap.add_argument("--frames", type=int, default=4096, help="frames per GPU per step")
     ap.add_argument("--stage-impl", type=int, default=0, help="VBS_OPT_STAGE_IMPL for the timed engine (A/B of the labelling kernel's shapes: 3 = 768 threads per frame always, 4 = 256 wherever the geometry allows; results identical)")
     ap.add_argument("--batch", type=int, default=1536, help="frames per internal pass (workspace size).  1536 = six frames per CU for the labelling kernel's 256-thread instance (three workgroups per CU): 512 / 768 / 1024 / 1536 / 2048 ran at 290.6 / 291.4 / 293.1 / 294.0 / 292.7 k frames/s in one sweep (profiles/r5o_stage256_large_ab3.log); rounds 2-5 quoted 512")
@@ -465,10 +512,12 @@ def main():
                     help="N > 1: 1 = one all-gather per internal pass pair, overlapping the next passes (dist.TableGather); "
                          "0 = every pass first, then the SINGLE all-gather of SURVEY 8(e) (dist.gather_tables)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # the parallel-CPU probe of the cpu_baseline leg forks: it runs before anything touches the GPU
     cpu_probe = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu_probe = probe_parallel_cpus(_host_cpus()[2])
         except Exception as e:
@@ -589,9 +638,8 @@ def main():
         _, counts, table = track_and_gather(eng, fr, n_total, xy, 20.0, cam, 5.0,     # all-gather per internal pass pair
                                             pipelined=bool(args.pipelined))
         disp = eng.displacement(table, 0, 5.0, 50.0, frame_range=(a, b))    # this rank's frames of the gathered table
-        if args.workload == "c5":
-            eng.plane_fit(table[a:b])
-        return table, disp, counts
+        plane = eng.plane_fit(table[a:b]) if args.workload == "c5" else None
+        return table, disp, counts, plane
 
     def barrier():
         if world > 1:
@@ -616,7 +664,7 @@ def main():
 
     elapsed, out = timed(frames, args.steps, args.warmup)
     ncc_ctr = eng.ncc_counters()
-    table, disp, counts = out
+    table, disp, counts, plane = out
     tracked = int((table[..., 0].int() & 1).sum().item())
     solved = int(((table[..., 0].int() & 2) > 0).sum().item())
     assert int(counts.min().item()) >= 0, "a frame reported a device status"
@@ -637,6 +685,12 @@ def main():
         td.all_gather(allsums, mine)
         table_sums = [[int(v) for v in t.tolist()] for t in allsums]
         assert all(t == table_sums[0] for t in table_sums), f"rank {rank}: the gathered tables differ between ranks: {table_sums}"
+
+    if args.dump_outputs and rank == 0:
+        outs = {"table": table, "displacement": disp, "counts": counts}
+        if plane is not None:
+            outs["plane"] = plane
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outs.items()})
 
     result = None
     if rank == 0:
@@ -676,9 +730,10 @@ def main():
                        "ncc_counter_frames": ncc_ctr["frames"]},
         }
 
+    # ---- everything below is --full only ----------------------------------------------------------------------------
     # ---- the same workload on BGR frames (the reference's input format; gray stays the headline) ----------------------
     side_legs = not crop and args.workload != "real"       # legs that render their own synthetic frames
-    if args.channels == 1 and not args.no_extras and side_legs:
+    if args.full and args.channels == 1 and not args.no_extras and side_legs:
         nb_ = min(n_local, 2048)
         fb = as_bgr(gray[:nb_])
         n_keep = n_total
@@ -708,7 +763,7 @@ def main():
         del fb, n_keep
 
     # ---- live per-kernel timing + the threshold+CCL roofline (rank 0; other ranks idle at the barrier) ----
-    if rank == 0:
+    if rank == 0 and args.full:
         nk = min(args.roofline_frames or 2 * args.batch, n_local)
         eng.profile(True)                                                    # (passes on ONE stream from here on)
         eng.track_to_3d(frames[:nk], xy, 20.0, cam, 5.0)                     # warm-up in the profiled configuration,
@@ -853,7 +908,7 @@ def main():
     if world > 1:
         td.barrier()
 
-    if rank == 0 and world == 1 and not args.no_extras and side_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and side_legs:
         try:
             del frames
             torch.cuda.empty_cache()
@@ -868,7 +923,7 @@ def main():
             result["config"]["single_frame_us"] = single_frame_us(spec, args.seed, (K, dist, R, T))
         except Exception as e:
             result["config"]["single_frame_us"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and side_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and side_legs:
         try:
             result["cpu_baseline"] = cpu_baseline(spec, args.seed, (K, dist, R, T), args.cpu_single_frames,
                                                   args.cpu_workers, args.cpu_frames_per_worker, probe=cpu_probe)

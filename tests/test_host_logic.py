@@ -493,6 +493,30 @@ def test_bench_cpu_limits_and_profile_selection(tmp_path, monkeypatch):
     assert bench._newest("*_nothing.json") is None
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files; within the budget every frame, above it the same seeded sample
+    of frames on every call, its indices written beside, and the files together within the budget."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"table": rng.normal(size=(300, 7, 10)).astype(np.float32), "counts": rng.integers(0, 9, 300).astype(np.int32)}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == {"table": 300, "counts": 300}
+    t = np.load(tmp_path / "all" / "table.npy")
+    c = np.load(tmp_path / "all" / "counts.npy")
+    assert t.dtype == np.float32 and np.array_equal(t, arrays["table"])
+    assert c.dtype == np.float64 and np.array_equal(c, arrays["counts"])
+    assert sorted(os.listdir(tmp_path / "all")) == ["counts.npy", "table.npy"]
+    budget = 40_000
+    for d in ("s1", "s2"):
+        n = bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+        assert 0 < n["table"] < 300 and n["table"] == n["counts"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= budget
+    for name in ("table", "counts"):
+        idx = np.load(tmp_path / "s1" / f"{name}_frame_index.npy")
+        assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "s2" / f"{name}_frame_index.npy"))
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{name}.npy"), arrays[name][idx.astype(np.int64)])
+
+
 def test_status_text_names_every_per_frame_status():
     from vbs_amd import _lib as L
     assert "workspace" in L.status_text(L.VBS_ECAPACITY, 512) and "512" in L.status_text(L.VBS_ECAPACITY, 512)

@@ -6,12 +6,12 @@ set -e
 TAG=${1:-r4a}
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 cd $GRAFT_REPO_ROOT
-timeout -k 10 600 python bench.py --steps 5 --warmup 2 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench c3 done"
-timeout -k 10 300 python bench.py --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_c5.json 2> $OUT/${TAG}_bench_c5.err
-timeout -k 10 300 python bench.py --channels 3 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_bgr.json 2> $OUT/${TAG}_bench_bgr.err
-timeout -k 10 300 python bench.py --workload c1 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_bench_c1.json 2> $OUT/${TAG}_bench_c1.err
-timeout -k 10 300 python bench.py --workload real --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_bench_real.json 2> $OUT/${TAG}_bench_real.err
+timeout -k 10 300 python bench.py --full --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_c5.json 2> $OUT/${TAG}_bench_c5.err
+timeout -k 10 300 python bench.py --full --channels 3 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_bgr.json 2> $OUT/${TAG}_bench_bgr.err
+timeout -k 10 300 python bench.py --full --workload c1 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_bench_c1.json 2> $OUT/${TAG}_bench_c1.err
+timeout -k 10 300 python bench.py --full --workload real --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_bench_real.json 2> $OUT/${TAG}_bench_real.err
 echo "bench c5 / bgr / c1 / real done"
 timeout -k 10 300 python tools/gpu_stage_phase.py 1536 c3 > $OUT/${TAG}_stage_phase_timing_c3.log 2>&1
 timeout -k 10 300 python tools/gpu_ncc_phase.py 512 > $OUT/${TAG}_ncc_phase_timing.log 2>&1
