@@ -77,8 +77,7 @@ int vbs_version(void);
  * - 15 (default): OpenCV 4.x, (3735 B + 19235 G + 9798 R + 2^14) >> 15;  14: OpenCV <= 3.4.1, (1868 B + 9617 G +
  * 4899 R + 2^13) >> 14.  The two agree wherever B = G = R.  VBS_OPT_FORCE_SEQ_MATCH (test hook): 1 makes
  * vbs_marker_center replay the reference's sequential contour <-> centre matching (:203-243) instead of the parallel
- * form that is proven equal to it.  VBS_OPT_GRAY_SIDE_STREAM (tuning, results identical): 1 converts the
- * BGR frames of internal pass k + 1 on the handle's own stream while pass k computes, 0 (default) converts in line.
+ * form that is proven equal to it.
  * VBS_OPT_NCC_MARGIN (test hook, results identical): relative margin of the NCC's float32 filter in units of 1e-6
  * (never below the 20 the error bound needs); a wide margin sends thousands of pixels per frame through the queued
  * float64 re-evaluation.  VBS_OPT_STAGE_IMPL (test hook / fallback, results identical): 0 (default) runs band / open /
@@ -90,8 +89,8 @@ int vbs_version(void);
  * fallback, results identical): 0 (default) runs the two GaussianBlurs (:118-129) on 16-column strips (k_blur16) where the
  * frame allows it (large branch, width >= 240 and a multiple of 8, rows that load as aligned dwords), 1 always runs the 32-column
  * kernel (k_blur_mfma) that every other frame takes.  VBS_OPT_PASS_STREAMS (tuning, results identical): 2 (default) lets
- * vbs_track_to_3d run the odd internal passes of a call (gray or BGR frames converted in line) with a SECOND WORKSPACE on
- * the handle's own stream (forked from and joined to the caller's stream by events), so that the tail of one pass's kernels
+ * vbs_track_to_3d run the odd internal passes of a call with a SECOND WORKSPACE on the handle's own stream (forked from
+ * and joined to the caller's stream by events), so that the tail of one pass's kernels
  * overlaps the next pass; 1 runs every pass on the caller's stream.  The second workspace is a second copy of every
  * per-pass buffer (twice the device memory of the handle).  Setting the option to 2 EXPLICITLY builds it at once (a set-up
  * call: allocations, copies, one device synchronisation; VBS_ENOMEM / VBS_EHIP if it cannot be built).  A handle left at
@@ -102,7 +101,7 @@ int vbs_version(void);
  * marker_detection.py:434-453) labels every frame with several workgroups (k_stage_lat) instead of one (k_stage); 0 = never. */
 #define VBS_OPT_GRAY_COEFFS      1
 #define VBS_OPT_FORCE_SEQ_MATCH  2
-#define VBS_OPT_GRAY_SIDE_STREAM 3
+/* option 3 is retired (VBS_OPT_GRAY_SIDE_STREAM: BGR conversion a pass ahead on a side stream, no faster) and not reused */
 #define VBS_OPT_NCC_MARGIN       4
 #define VBS_OPT_STAGE_IMPL       5
 #define VBS_OPT_BLUR_IMPL        6

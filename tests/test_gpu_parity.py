@@ -1958,9 +1958,10 @@ def test_ncc_wide_margin_drives_the_queued_exact_path(cfg):
     eng.close()
 
 
-def test_bgr_side_stream_option_gives_the_same_results():
-    """VBS_OPT_GRAY_SIDE_STREAM: BGR frames over several internal passes, the conversion of pass k + 1 on the handle's own
-    stream (lead pass, two gray planes, event fork / join) - tables and masks identical to the in-line conversion."""
+def test_bgr_passes_on_one_or_two_streams_give_the_same_results():
+    """BGR frames over several internal passes, every pass converting its own frames in line: all on the caller's stream
+    (VBS_OPT_PASS_STREAMS 1) or the odd passes in the second workspace on its own stream (2) - tables, counts and masks
+    identical, masks equal to the oracle's in the first, a middle and the last pass.  The retired option 3 is refused."""
     rng = np.random.default_rng(21)
     spec = S.config1()
     g = S.make_frames(spec, range(11), seed=6)
@@ -1969,15 +1970,19 @@ def test_bgr_side_stream_option_gives_the_same_results():
     eng = engine(spec.height, spec.width, max_batch=3)
     from vbs_amd.pipeline import reference_from_frame0
     ids, xy = reference_from_frame0(eng, ft[:1], 5, "full", "optimal")
-    t0, _, c0 = eng.track_to_3d(ft, xy, 20.0, None, 5.0)
-    m0, a0 = eng.find_markers(ft)
-    eng.set_option(L.OPT_GRAY_SIDE_STREAM, 1)
-    for _ in range(2):                                         # twice: the planes and events are reused across calls
-        t1, _, c1 = eng.track_to_3d(ft, xy, 20.0, None, 5.0)
-        m1, a1 = eng.find_markers(ft)
-        assert torch.equal(t0, t1) and torch.equal(c0, c1) and torch.equal(m0, m1) and torch.equal(a0, a1)
-    om, oa = O.find_markers(frames[7])
-    assert np.array_equal(m1[7].cpu().numpy(), om) and np.array_equal(a1[7].cpu().numpy(), oa)
+    out = {}
+    for streams in (1, 2):
+        eng.set_option(L.OPT_PASS_STREAMS, streams)
+        t, _, c = eng.track_to_3d(ft, xy, 20.0, None, 5.0)
+        m, a = eng.find_markers(ft)
+        out[streams] = (t, c, m, a)
+    (t1, c1, m1, a1), (t2, c2, m2, a2) = out[1], out[2]
+    assert torch.equal(t1, t2) and torch.equal(c1, c2) and torch.equal(m1, m2) and torch.equal(a1, a2)
+    for i in (0, 7, 10):
+        om, oa = O.find_markers(frames[i])
+        assert np.array_equal(m2[i].cpu().numpy(), om) and np.array_equal(a2[i].cpu().numpy(), oa), i
+    with pytest.raises(ValueError, match="unknown option"):
+        eng.set_option(3, 1)
     eng.close()
 
 

@@ -24,14 +24,18 @@ def test_library_exports_every_header_symbol():
     assert lib.vbs_version() >= 100
 
 
-def test_option_and_status_constants_match_the_header():
-    """`_lib.py` restates the header's #defines (options, status codes, table layout): they must agree."""
+def test_option_and_status_constants_match_the_header_with_option_3_retired():
+    """`_lib.py` restates the header's #defines (options, status codes, table layout): they must agree.  Option number 3
+    (the removed side-stream conversion) is defined on neither side."""
     hdr = open(os.path.join(ROOT, "include", "vbs.h")).read()
     defs = {k: int(v) for k, v in re.findall(r"#define\s+(VBS_[A-Z0-9_]+)\s+(-?\d+)", hdr)}
-    for name in ("GRAY_COEFFS", "FORCE_SEQ_MATCH", "GRAY_SIDE_STREAM", "NCC_MARGIN", "STAGE_IMPL", "BLUR_IMPL", "PASS_STREAMS"):
+    names = ("GRAY_COEFFS", "FORCE_SEQ_MATCH", "NCC_MARGIN", "STAGE_IMPL", "BLUR_IMPL", "PASS_STREAMS", "LATENCY_FRAMES")
+    for name in names:
         assert getattr(L, "OPT_" + name) == defs["VBS_OPT_" + name], name
+    assert {k[len("VBS_OPT_"):] for k in defs if k.startswith("VBS_OPT_")} == set(names)
+    assert {k[len("OPT_"):] for k in vars(L) if k.startswith("OPT_")} == set(names)
     opts = [v for k, v in defs.items() if k.startswith("VBS_OPT_")]
-    assert len(opts) == len(set(opts)) == 8
+    assert len(opts) == len(set(opts)) == 7 and 3 not in opts
     for k, v in defs.items():
         if hasattr(L, k[4:]) and isinstance(getattr(L, k[4:]), int) and not k.startswith("VBS_OPT_"):
             assert getattr(L, k[4:]) == v, k

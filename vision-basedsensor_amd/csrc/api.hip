@@ -111,9 +111,6 @@ extern "C" int vbs_destroy(vbs_handle* h) {
     if (h->ev_tfork) (void)hipEventDestroy(h->ev_tfork);
     if (h->ev_tjoin) (void)hipEventDestroy(h->ev_tjoin);
     for (void* p : h->allocs) (void)hipFree(p);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    for (int i = 0; i < 2; ++i) { if (h->ev_gray[i]) (void)hipEventDestroy(h->ev_gray[i]); if (h->ev_free[i]) (void)hipEventDestroy(h->ev_free[i]); }
     delete h;
     return VBS_OK;
 }
@@ -157,7 +154,7 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
     const size_t B = (size_t)max_batch, HW = (size_t)height * h->WW;
     int rc;
 #define ALLOC(field, count) if ((rc = dev_alloc(h, &h->field, (count))) != VBS_OK) return rc
-    h->gray = h->gray2 = nullptr;                       // allocated at the first 3-channel / undistorted use (need_gray)
+    h->gray = nullptr;                                  // allocated at the first 3-channel / undistorted use (need_gray)
     ALLOC(area_bits, B * HW); ALLOC(mask_bits, B * HW); ALLOC(band_bits, B * HW);
     ALLOC(open_bits, B * HW);
     ALLOC(ncc_rx, (size_t)width); ALLOC(ncc_ry, (size_t)height);
@@ -229,12 +226,6 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
         HIPCHK(h, hipMemcpy(h->uwtab, wt.data(), 4096 * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     HIPCHK(h, hipMemset(h->ncc_tot, 0, 4 * sizeof(u64)));
-    HIPCHK(h, hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_gray[i], hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_free[i], hipEventDisableTiming));
-    }
     HIPCHK(h, hipDeviceSynchronize());
     return VBS_OK;
 }
@@ -250,25 +241,22 @@ static bool capturing(hipStream_t s) {
     return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
 }
 
-// Gray planes of 3-channel / undistorted input ([maxb][H][P] each; the second one only serves VBS_OPT_GRAY_SIDE_STREAM):
-// gray frames never touch them, so they are allocated at the first call that needs them, or by vbs_set_undistort /
-// vbs_set_option(VBS_OPT_GRAY_SIDE_STREAM).  Never under stream capture: there the call fails and says why.
-static int need_gray(vbs_handle* h, int planes, hipStream_t s) {
-    u8** slot[2] = {&h->gray, &h->gray2};
-    for (int i = 0; i < planes; ++i) {
-        if (*slot[i]) continue;
+// The gray plane of 3-channel / undistorted input ([maxb][H][P]): gray frames never touch it, so it is allocated at the
+// first call that needs it, or by vbs_set_undistort.  Never under stream capture: there the call fails and says why.
+static int need_gray(vbs_handle* h, hipStream_t s) {
+    if (!h->gray) {
         if (capturing(s)) {
             h->err = "the gray plane of 3-channel / undistorted input is allocated at first use: run one such call (or "
                      "vbs_set_undistort) outside stream capture first";
             return VBS_EINVAL;
         }
-        int rc = dev_alloc(h, slot[i], (size_t)h->maxb * h->H * h->P);
+        int rc = dev_alloc(h, &h->gray, (size_t)h->maxb * h->H * h->P);
         if (rc != VBS_OK) return rc;
     }
-    // the second workspace converts its own passes: its first plane exists whenever this handle's does, so that a multi-pass
+    // the second workspace converts its own passes: its plane exists whenever this handle's does, so that a multi-pass
     // call on 3-channel frames captured into a graph finds it in place after ANY uncaptured 3-channel call
-    if (h->twin && !h->twin->gray && h->gray && !capturing(s)) {
-        int rc = need_gray(h->twin, 1, s);
+    if (h->twin && !h->twin->gray && !capturing(s)) {
+        int rc = need_gray(h->twin, s);
         if (rc != VBS_OK) { h->err = "second pass workspace: " + h->twin->err; return rc; }
     }
     return VBS_OK;
@@ -289,16 +277,13 @@ static void clear_pass(vbs_handle* h, int nb, hipStream_t s) {
     }
 }
 
-// One internal pass of the detection stage.  `pre` = gray plane already converted for this pass (vbs_detect_loop's
-// side-stream pipeline), else the conversion runs here on `s`.
+// One internal pass of the detection stage: the blur reads gray frames directly, others are converted or remapped first.
 static int detect_pass(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n,
-                       int64_t stride_row, u8* mask_u8, u8* area_u8, double* ncc_out, hipStream_t s, const u8* pre = nullptr) {
-    if (!pre && (h->undist || channels != 1)) { int rc = need_gray(h, 1, s); if (rc != VBS_OK) return rc; }
+                       int64_t stride_row, u8* mask_u8, u8* area_u8, double* ncc_out, hipStream_t s) {
+    if (h->undist || channels != 1) { int rc = need_gray(h, s); if (rc != VBS_OK) return rc; }
     h->last_ws = h; h->last_nb = nb;                     // (vbs_track_to_3d names the workspace of ITS last pass afterwards)
     clear_pass(h, nb, s);
-    if (pre) {
-        launch_blur(h, pre, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
-    } else if (h->undist) {                             // marker_detection.py:88-89: undistort, then cvtColor
+    if (h->undist) {                                    // marker_detection.py:88-89: undistort, then cvtColor
         launch_remap(h, frames, nb, channels, stride_n, stride_row, h->gray, 1, s);
         launch_blur(h, h->gray, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
     } else if (channels == 1) {
@@ -311,60 +296,19 @@ static int detect_pass(vbs_handle* h, const u8* frames, int nb, int channels, in
     return check_launch(h);
 }
 
-// BGR frames over several internal passes with VBS_OPT_GRAY_SIDE_STREAM set: cvtColor of pass k + 1 runs on the handle's
-// side stream while pass k's kernels run on `s` (two gray planes; fork / join by events, so a caller may capture the whole
-// call in a graph).  Off by default (`on` false: every pass converts in line, see detect_pass).
-struct GrayPipe {
-    vbs_handle* h; const u8* frames; int n, channels; int64_t stride_n, stride_row; hipStream_t s;
-    bool on;
-    bool stagger = false;                               // two pass streams: a first pass of half a batch puts them out of phase
-    int start() {
-        on = h->gray_side && !h->undist && channels == 3 && n > h->maxb;
-        if (!on) return VBS_OK;
-        { int rc = need_gray(h, 2, s); if (rc != VBS_OK) { on = false; return rc; } }
-        HIPCHK(h, hipEventRecord(h->ev_fork, s));
-        HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        return convert(0);
+// vbs_find_markers / vbs_ncc_map: detect_pass over passes of maxb frames, each writing its slice of the outputs given
+static int detect_loop(vbs_handle* h, const u8* frames, int n, int channels, int64_t stride_n, int64_t stride_row,
+                       u8* mask, u8* area_mask, double* ncc, hipStream_t s) {
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t hw = (size_t)h->H * h->W;
+    for (int off = 0; off < n; off += h->maxb) {
+        int rc = detect_pass(h, frames + (int64_t)off * stride_n, std::min(h->maxb, n - off), channels, stride_n, stride_row,
+                             mask ? mask + off * hw : nullptr, area_mask ? area_mask + off * hw : nullptr,
+                             ncc ? ncc + off * hw : nullptr, s);
+        if (rc != VBS_OK) return rc;
     }
-    // pass schedule: with the conversion pipelined, a short first pass keeps the only exposed conversion small
-    int lead() const { return on ? std::min(h->maxb, std::max(64, h->maxb / 8)) : (stagger ? std::max(1, h->maxb / 2) : h->maxb); }
-    int pass_off(int k) const { return k == 0 ? 0 : lead() + (k - 1) * h->maxb; }
-    int pass_len(int k) const { return std::min(k == 0 ? lead() : h->maxb, n - pass_off(k)); }
-    int convert(int k) {                                // pass k -> plane k & 1, on the side stream
-        const int off = pass_off(k), nb = pass_len(k);
-        launch_gray(h, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, k & 1 ? h->gray2 : h->gray, h->side);
-        HIPCHK(h, hipEventRecord(h->ev_gray[k & 1], h->side));
-        return VBS_OK;
-    }
-    // before pass k's blur: its plane is ready; the next pass's conversion may start once ITS plane is free again
-    int acquire(int k, const u8** plane) {
-        *plane = nullptr;
-        if (!on) return VBS_OK;
-        HIPCHK(h, hipStreamWaitEvent(s, h->ev_gray[k & 1], 0));
-        if (pass_off(k + 1) < n) {
-            if (k >= 1) HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_free[(k + 1) & 1], 0));
-            int rc = convert(k + 1);
-            if (rc != VBS_OK) return rc;
-        }
-        *plane = k & 1 ? h->gray2 : h->gray;
-        return VBS_OK;
-    }
-    int release(int k) {                                // after pass k's blur has been enqueued
-        if (!on) return VBS_OK;
-        HIPCHK(h, hipEventRecord(h->ev_free[k & 1], s));
-        return VBS_OK;
-    }
-    // an error return in the middle of the passes: the conversion already running on the side stream is joined into `s`
-    // (an un-joined fork would break a caller's stream capture and leave a kernel writing the gray planes unordered
-    // against the next call); returns rc unchanged
-    int fail(int rc) {
-        if (on) {
-            (void)hipEventRecord(h->ev_gray[0], h->side);
-            (void)hipStreamWaitEvent(s, h->ev_gray[0], 0);
-        }
-        return rc;
-    }
-};
+    return VBS_OK;
+}
 
 extern "C" int vbs_find_markers(vbs_handle* h, const uint8_t* frames, int n, int channels, int64_t stride_n,
                                 int64_t stride_row, uint8_t* mask, uint8_t* area_mask, void* stream) {
@@ -373,22 +317,7 @@ extern "C" int vbs_find_markers(vbs_handle* h, const uint8_t* frames, int n, int
         h->err = "vbs_find_markers: bad argument";
         return VBS_EINVAL;
     }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t hw = (size_t)h->H * h->W;
-    GrayPipe gp{h, frames, n, channels, stride_n, stride_row, s, false};
-    int rc = gp.start();
-    if (rc != VBS_OK) return rc;
-    for (int k = 0; gp.pass_off(k) < n; ++k) {
-        const int off = gp.pass_off(k), nb = gp.pass_len(k);
-        const u8* plane;
-        if ((rc = gp.acquire(k, &plane)) != VBS_OK) return gp.fail(rc);
-        rc = detect_pass(h, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row,
-                         mask ? mask + off * hw : nullptr, area_mask ? area_mask + off * hw : nullptr, nullptr, s, plane);
-        if (rc != VBS_OK) return gp.fail(rc);
-        if ((rc = gp.release(k)) != VBS_OK) return gp.fail(rc);
-    }
-    return VBS_OK;
+    return detect_loop(h, frames, n, channels, stride_n, stride_row, mask, area_mask, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int vbs_bgr2gray(vbs_handle* h, const uint8_t* frames, int n, int64_t stride_n, int64_t stride_row,
@@ -407,22 +336,7 @@ extern "C" int vbs_ncc_map(vbs_handle* h, const uint8_t* frames, int n, int chan
         h->err = "vbs_ncc_map: bad argument";
         return VBS_EINVAL;
     }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t hw = (size_t)h->H * h->W;
-    GrayPipe gp{h, frames, n, channels, stride_n, stride_row, s, false};
-    int rc = gp.start();
-    if (rc != VBS_OK) return rc;
-    for (int k = 0; gp.pass_off(k) < n; ++k) {
-        const int off = gp.pass_off(k), nb = gp.pass_len(k);
-        const u8* plane;
-        if ((rc = gp.acquire(k, &plane)) != VBS_OK) return gp.fail(rc);
-        rc = detect_pass(h, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, nullptr, nullptr,
-                         ncc + off * hw, s, plane);
-        if (rc != VBS_OK) return gp.fail(rc);
-        if ((rc = gp.release(k)) != VBS_OK) return gp.fail(rc);
-    }
-    return VBS_OK;
+    return detect_loop(h, frames, n, channels, stride_n, stride_row, nullptr, nullptr, ncc, (hipStream_t)stream);
 }
 
 extern "C" int vbs_normxcorr2(vbs_handle* h, const uint8_t* area_mask, int n, double* ncc, uint8_t* mask,
@@ -448,8 +362,7 @@ static int twin_of(vbs_handle* h);
 
 extern "C" int vbs_set_option(vbs_handle* h, int option, int value) {
     if (!h) return VBS_EINVAL;
-    // (same checks, same answer; the twin never converts a pass ahead on a side stream: its second gray plane would be dead memory)
-    if (h->twin && option != VBS_OPT_PASS_STREAMS && option != VBS_OPT_GRAY_SIDE_STREAM) (void)vbs_set_option(h->twin, option, value);
+    if (h->twin && option != VBS_OPT_PASS_STREAMS) (void)vbs_set_option(h->twin, option, value);     // (same checks, same answer)
     switch (option) {
         case VBS_OPT_PASS_STREAMS:
             if (value != 1 && value != 2) break;
@@ -459,10 +372,6 @@ extern "C" int vbs_set_option(vbs_handle* h, int option, int value) {
             if (value == 2 && !h->is_twin) { int rc = twin_of(h); if (rc != VBS_OK) return rc; }
             return VBS_OK;
         case VBS_OPT_FORCE_SEQ_MATCH: h->force_seq_match = value != 0; return VBS_OK;
-        case VBS_OPT_GRAY_SIDE_STREAM:
-            h->gray_side = value != 0;
-            if (h->gray_side) { HIPCHK(h, hipSetDevice(h->device)); int rc = need_gray(h, 2, nullptr); if (rc != VBS_OK) return rc; }
-            return VBS_OK;
         case VBS_OPT_NCC_MARGIN:
             if (value < 0 || value > 100000) break;
             h->ncc_margin_ppm = value;
@@ -542,7 +451,7 @@ extern "C" int vbs_set_undistort(vbs_handle* h, const double* K9, const double* 
         return VBS_EINVAL;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = need_gray(h, 1, (hipStream_t)stream);      // (a set-up call: the plane the undistorted frames go to)
+    int rc = need_gray(h, (hipStream_t)stream);      // (a set-up call: the plane the undistorted frames go to)
     if (rc != VBS_OK) return rc;
     rc = setup_undistort(h, K9, dist, ndist, (hipStream_t)stream);
     if (rc != VBS_OK) return rc;
@@ -700,7 +609,7 @@ static int twin_of(vbs_handle* h) {
     }
     h->twin_stream = st; h->ev_tfork = ef; h->ev_tjoin = ej;
     h->twin = t;
-    if (h->gray) { int rg = need_gray(t, 1, nullptr); if (rg != VBS_OK) { h->err = "second pass workspace: " + t->err; return rg; } }
+    if (h->gray) { int rg = need_gray(t, nullptr); if (rg != VBS_OK) { h->err = "second pass workspace: " + t->err; return rg; } }
     return VBS_OK;
 }
 
@@ -717,14 +626,11 @@ extern "C" int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int 
     if (cam) { int rc = check_cam(h, cam); if (rc != VBS_OK) return rc; }
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(h, hipSetDevice(h->device));
-    GrayPipe gp{h, frames, n, channels, stride_n, stride_row, s, false};
-    int rc = gp.start();
-    if (rc != VBS_OK) return rc;
     // Several passes: odd passes on the second workspace and stream (VBS_OPT_PASS_STREAMS), so that the partly filled last
     // round of one pass's kernels runs next to the other pass - and, for BGR frames, the bandwidth-bound conversion of one pass
     // next to the matrix-core kernels of the other (each workspace converts into its own gray plane).  Every pass writes its own slice of the
     // caller's tables; the second stream starts behind what the caller's stream holds and is joined before the return.
-    bool two = h->pass_streams == 2 && !h->prof && !h->undist && !gp.on && n > h->maxb;     // (gp.on: BGR converted a pass ahead on h->side)
+    bool two = h->pass_streams == 2 && !h->prof && !h->undist && n > h->maxb;
     if (two && !h->twin) {
         // The second workspace normally exists by now (vbs_set_option(VBS_OPT_PASS_STREAMS, 2) builds it).  A handle left at
         // the default builds it at its first call that spans several passes - unless the caller's stream is being captured
@@ -733,7 +639,6 @@ extern "C" int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int 
         if (capturing(s) || twin_of(h) != VBS_OK) { two = false; h->err.clear(); }
     }
     if (two) {
-        gp.stagger = true;
         HIPCHK(h, hipEventRecord(h->ev_tfork, s));
         HIPCHK(h, hipStreamWaitEvent(h->twin_stream, h->ev_tfork, 0));
     }
@@ -744,17 +649,14 @@ extern "C" int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int 
         }
         return code;
     };
-    for (int k = 0; gp.pass_off(k) < n; ++k) {
-        const int off = gp.pass_off(k), nb = gp.pass_len(k);
+    const int lead = two ? std::max(1, h->maxb / 2) : h->maxb;     // two pass streams: a first pass of half a batch puts them out of phase
+    for (int k = 0, off = 0, nb = 0; off < n; off += nb, ++k) {
+        nb = std::min(k == 0 ? lead : h->maxb, n - off);
         vbs_handle* hh = (two && (k & 1)) ? h->twin : h;
         hipStream_t ss = (two && (k & 1)) ? h->twin_stream : s;
-        const u8* plane;
-        if ((rc = gp.acquire(k, &plane)) != VBS_OK) return join(gp.fail(rc));
-        rc = detect_pass(hh, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, nullptr, nullptr, nullptr,
-                         ss, plane);
-        if (rc != VBS_OK) { if (hh != h) h->err = hh->err; return join(gp.fail(rc)); }
+        int rc = detect_pass(hh, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, nullptr, nullptr, nullptr, ss);
+        if (rc != VBS_OK) { if (hh != h) h->err = hh->err; return join(rc); }
         h->last_ws = hh; h->last_nb = nb;                // (what vbs_frame_stats / vbs_stage_tables read)
-        if ((rc = gp.release(k)) != VBS_OK) return join(gp.fail(rc));
         launch_labelling(hh, nb, ss);
         if (table && nb <= hh->lat_frames)               // a few frames: detections and tracking rows in one launch
                                                          // (for a batch pass the one launch measured nothing: 282.1 k against 283.1 k frames/s)
@@ -768,7 +670,7 @@ extern "C" int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int 
                                    min_marker_size_px, ss);
         }
         rc = check_launch(hh);
-        if (rc != VBS_OK) { if (hh != h) h->err = hh->err; return join(gp.fail(rc)); }
+        if (rc != VBS_OK) { if (hh != h) h->err = hh->err; return join(rc); }
     }
     return join(VBS_OK);
 }

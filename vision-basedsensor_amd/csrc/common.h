@@ -59,9 +59,6 @@ struct vbs_handle {
     std::string err;
     // ---- device workspace (per internal pass of maxb frames) ----
     u8* gray;          // [maxb][H][P]   gray plane of 3-channel / undistorted input; null until first needed (need_gray)
-    u8* gray2;         // second plane: the conversion of pass k + 1 runs on `side` while pass k computes
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_gray[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
     uint4* blur_frags; // Toeplitz operand fragments of k_blur_mfma (blur_mfma_fragments)
     uint4* blur16_h = nullptr;   // k_blur16: horizontal fragments per 16-column strip (blur16_fragments); null = not built
     uint4* blur16_v = nullptr;   // k_blur16: the 12 vertical fragment variants
@@ -112,7 +109,6 @@ struct vbs_handle {
     int stage_impl = 0;             // vbs_set_option(VBS_OPT_STAGE_IMPL): 0 fused k_stage, 1 the round-2 kernels (k_morph + k_ccl), 2 k_label for every frame, 3 / 4 fused at 768 / 256 threads
     int gray_bits = 15;             // BGR2GRAY fixed-point coefficient set: 15 (OpenCV 4) | 14 (OpenCV <= 3.4.1)
     bool force_seq_match = false;   // vbs_set_option(VBS_OPT_FORCE_SEQ_MATCH)
-    bool gray_side = false;         // vbs_set_option(VBS_OPT_GRAY_SIDE_STREAM)
     int ncc_margin_ppm = 0;         // vbs_set_option(VBS_OPT_NCC_MARGIN): test hook, widens the float32 filter's margin
     u8* lut;           // [256] contour vertex table
     short* umap1;      // [H][W][2] int16 undistortion source pixel (CV_16SC2)

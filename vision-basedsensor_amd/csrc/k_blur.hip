@@ -27,9 +27,8 @@ __device__ __forceinline__ u32 bgr4_to_gray(u32 a, u32 b, u32 c, const GrayCoef&
 
 // cvtColor(BGR2GRAY) (or a plain copy for 1 channel) into the pitched gray plane the blur reads: a streaming kernel,
 // 16 pixels per thread (three 16-byte loads, one 16-byte store) when the rows are 16-byte aligned: 0.85-1.0 us per
-// 1280x1024 frame (5.3-6.2 TB/s of its 5.2 MB).  It runs in line in front of the blur; VBS_OPT_GRAY_SIDE_STREAM moves it one
-// internal pass ahead onto the handle's own stream (api.hip), which measured no faster: the matrix-core kernels leave
-// the HBM idle but not the registers, LDS and issue slots a conversion workgroup needs next to them.
+// 1280x1024 frame (5.3-6.2 TB/s of its 5.2 MB).  It runs in line in front of the blur (converting a pass ahead on a side
+// stream measured no faster: profiles/NOTES.md section 9).
 // (Converting inside the blur's own loader was built and measured: LDS-DMA staging of the raw bytes kept the matrix
 //  operands in registers only at the price of 50 spilled VGPRs - 5 us per frame against 1.45.)
 __global__ __launch_bounds__(256) void k_gray(const u8* __restrict__ frames, int channels, int64_t stride_n,
@@ -107,20 +106,6 @@ __global__ __launch_bounds__(256) void k_gray(const u8* __restrict__ frames, int
         out[k >> 2] |= v << (8 * (k & 3));
     }
     *reinterpret_cast<uint4*>(dst) = make_uint4(out[0], out[1], out[2], out[3]);
-}
-
-// k_gray's dense path without LDS (48 contiguous bytes per thread, 3 KB per wave): the form the side stream launches, so
-// that its workgroups fit next to k_ncc_mfma's, which leave registers and wave slots but no LDS
-__global__ __launch_bounds__(256) void k_gray_flat(const u8* __restrict__ frames, int64_t stride_n, u8* __restrict__ gray,
-                                                   int64_t npx, GrayCoef gc) {
-    const int n = blockIdx.z;
-    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (p0 >= npx) return;
-    const uint4* s4 = reinterpret_cast<const uint4*>(frames + (int64_t)n * stride_n + p0 * 3);
-    const uint4 r0 = s4[0], r1 = s4[1], r2 = s4[2];
-    *reinterpret_cast<uint4*>(gray + (int64_t)n * npx + p0) =
-        make_uint4(bgr4_to_gray(r0.x, r0.y, r0.z, gc), bgr4_to_gray(r0.w, r1.x, r1.y, gc),
-                   bgr4_to_gray(r1.z, r1.w, r2.x, gc), bgr4_to_gray(r2.y, r2.z, r2.w, gc));
 }
 
 // the cvtColor stage on its own (vbs_bgr2gray): dense [n,H,W] output, one pixel per thread
@@ -864,12 +849,6 @@ void launch_gray(vbs_handle* h, const u8* frames, int nb, int channels, int64_t 
                  int64_t stride_row, u8* gray, hipStream_t s) {
     const int vec_ok = (reinterpret_cast<uintptr_t>(frames) % 16 == 0) && (stride_n % 16 == 0) && (stride_row % 16 == 0);
     const int flat = vec_ok && channels == 3 && stride_row == (int64_t)h->W * 3 && h->P == h->W && ((int64_t)h->H * h->W) % 16 == 0;
-    if (flat && s == h->side) {
-        const int64_t npx = (int64_t)h->H * h->W;
-        VBS_LAUNCH(h, s, "k_gray", k_gray_flat, dim3((unsigned)((npx / 16 + 255) / 256), 1, nb), dim3(256), 0, s, frames, stride_n,
-                   gray, npx, gray_coef(h->gray_bits));
-        return;
-    }
     dim3 grid = flat ? dim3((unsigned)(((int64_t)h->H * h->W + 8191) / 8192), 1, nb)
                      : dim3((unsigned)(((int64_t)h->H * (h->P / 16) + 255) / 256), 1, nb);
     VBS_LAUNCH(h, s, "k_gray", k_gray, grid, dim3(256), 0, s, frames, channels, stride_n, stride_row, gray,
