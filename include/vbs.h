@@ -130,6 +130,36 @@ int vbs_mjpeg_entropy_batch(const uint8_t* buf, const int64_t* offs, const int32
                             int threads);
 int vbs_mjpeg_reconstruct(const uint32_t* ent, const uint32_t* tab, const int64_t* frame_base, const uint16_t* qt, int n,
                           const int32_t* info, uint8_t* planes, uint8_t* out, int64_t out_frame, int64_t out_row, void* stream);
+/* The annotated tracking video (`_tracked.avi`, marker_detection.py:69-76,453) as Motion-JPEG, encoded on the device.
+ * vbs_jpeg_encode: n BGR frames [dev] uint8 (frame / row strides in bytes, 3 bytes per pixel; a crop view is fine) -> one
+ * complete JFIF file per frame, equal byte for byte to Pillow's `Image.save(buf, "JPEG", quality=quality)` (libjpeg-turbo
+ * defaults: 4:2:0, islow DCT, Annex K Huffman tables, no optimisation).  File i is written at payload + offsets[i], sizes[i]
+ * bytes long, the files back to back (offsets[0] = 0); offsets / sizes are DEVICE arrays.  No handle: the caller owns the
+ * workspace [dev] and the payload [dev], sized by vbs_jpeg_encode_workspace (host-only, no GPU needed), which also reports the
+ * bound on one file.  Entropy coding runs on the device; asynchronous on `stream`.
+ * Payload bound: a block (8x8 samples) codes to at most VBS_JPEG_BLOCK_BITS_MAX bits (DC: an 11-bit code + 11 magnitude bits;
+ * each of 63 AC coefficients: a 16-bit code + 10 magnitude bits; a ZRL or EOB replaces coefficients that would cost more),
+ * byte stuffing at most doubles the scan, so one frame of B = 6 ceil(W/16) ceil(H/16) blocks takes at most
+ * VBS_JPEG_HEADER_BYTES + 2 ceil(B VBS_JPEG_BLOCK_BITS_MAX / 8) + 2 (EOI) bytes; payload_bytes = n times that.
+ * quality 1..100; frames of up to 65535 x 65535 whose scan bound stays below 2^32 bits. */
+#define VBS_JPEG_BLOCK_BITS_MAX 1660
+#define VBS_JPEG_HEADER_BYTES   623
+int vbs_jpeg_encode_workspace(int width, int height, int n, int64_t* workspace_bytes, int64_t* payload_bytes,
+                              int64_t* frame_bound);
+int vbs_jpeg_encode(const uint8_t* frames, int n, int width, int height, int64_t stride_n, int64_t stride_row, int quality,
+                    void* workspace, int64_t workspace_bytes, uint8_t* payload, int64_t payload_bytes, int64_t* offsets,
+                    int32_t* sizes, void* stream);
+/* MarkerTracker._draw_tracking (marker_detection.py:398-427), painted on every frame of a batch for the video:
+ * frames [dev] uint8 BGR [n,H,W,3] (frame / row strides in bytes; a crop view is fine; not modified), det [dev] float64
+ * [n,max_markers,VBS_DET_COLS] and table [dev] float32 [n,m_ref,VBS_TABLE_COLS] as vbs_track_to_3d writes them, ref_xy [dev]
+ * float64 [m_ref,2] -> out [dev] uint8 [n,H,W,3] dense.  For each slot with VBS_FLAG_TRACKED, in slot order: the filled red
+ * disc of radius 4 at (int(Cx), int(Cy)), the red arrow of thickness 2 (tipLength 0.25) from (int(Ox), int(Oy)), the yellow
+ * major and the blue minor axis of thickness 2; a later primitive covers an earlier one.  Coordinates come from the float64
+ * det rows (the table's det index, col 9).  Rasterisation restated from OpenCV 4.x imgproc/src/drawing.cpp (circle FILLED,
+ * line/ThickLine with XY_SHIFT 16 and round caps, arrowedLine).  lastw [dev] int32 scratch of n*H*W.  Asynchronous. */
+int vbs_draw_tracking(const uint8_t* frames, int n, int height, int width, int64_t stride_n, int64_t stride_row,
+                      const double* det, int max_markers, const float* table, const double* ref_xy, int m_ref,
+                      int32_t* lastw, uint8_t* out, void* stream);
 /* host-only helper: the 256-entry table that classifies a border pixel's 8-neighbourhood into the
  * number of CHAIN_APPROX_SIMPLE vertices it contributes (bit d of the index = neighbour in chain
  * direction d is foreground; 0=E,1=NE,2=N,...,7=SE). */

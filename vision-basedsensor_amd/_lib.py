@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvbs.so")
 VBS_OK, VBS_EINVAL, VBS_ECAPACITY, VBS_EHIP, VBS_ENOMEM, VBS_EINTERNAL = 0, -1, -2, -3, -4, -5
 DET_COLS, TABLE_COLS, DISP_COLS, PLANE_COLS, DEVPLANE_COLS = 6, 10, 5, 5, 9
 FLAG_TRACKED, FLAG_XYZ = 1, 2
+JPEG_BLOCK_BITS_MAX, JPEG_HEADER_BYTES = 1660, 623
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -17,7 +18,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_track", "vbs_solve3d", "vbs_track_to_3d", "vbs_displacement", "vbs_displacement_range", "vbs_displacement_f64",
            "vbs_plane_fit", "vbs_assign_ids", "vbs_set_option", "vbs_bgr2gray", "vbs_ncc_counters", "vbs_normxcorr2_general",
            "vbs_stage_tables", "vbs_deviation_plane", "vbs_format_csv", "vbs_mjpeg_probe", "vbs_mjpeg_entropy_batch",
-           "vbs_mjpeg_reconstruct")
+           "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking")
 
 
 class Camera(C.Structure):
@@ -99,6 +100,9 @@ def lib():
         "vbs_mjpeg_probe": (i32, [vp, i64, vp]),
         "vbs_mjpeg_entropy_batch": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32]),
         "vbs_mjpeg_reconstruct": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i64, i64, vp]),
+        "vbs_jpeg_encode_workspace": (i32, [i32, i32, i32, vp, vp, vp]),
+        "vbs_jpeg_encode": (i32, [vp, i32, i32, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, vp]),
+        "vbs_draw_tracking": (i32, [vp, i32, i32, i32, i64, i64, vp, i32, vp, vp, i32, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

@@ -256,6 +256,32 @@ class Engine:
                 _ptr(counts), self._stream()), "vbs_track_to_3d")
         return table, det, counts
 
+    # ---- the annotated video (`_draw_tracking`, marker_detection.py:398-427) ----------------------
+    def draw_tracking(self, frames, det, table, ref_xy):
+        """The reference's `_draw_tracking` on every tracked slot of every frame, in slot order: frames uint8 [n,H,W,3] BGR
+        on the device (a crop view is fine; not modified), det [n,max_markers,6] float64 / table [n,m,10] float32 as
+        `track_to_3d(..., want_det=True)` returns them, ref_xy [m,2] -> a new dense uint8 [n,H,W,3] tensor."""
+        frames, n, ch, sn, sr = self._frames(frames)
+        if ch != 3 or frames.dim() != 4:
+            raise ValueError("draw_tracking needs BGR frames [n,H,W,3] (the reference only draws on colour frames)")
+        ref = torch.as_tensor(ref_xy, dtype=torch.float64, device=self.device).contiguous().reshape(-1, 2)
+        m = ref.shape[0]
+        if (det.dtype != torch.float64 or det.dim() != 3 or det.shape[0] < n or det.shape[2] != L.DET_COLS
+                or not det.is_contiguous() or det.device != self.device):
+            raise ValueError("det must be a contiguous float64 device tensor [n,max_markers,6]")
+        if (table.dtype != torch.float32 or tuple(table.shape) != (n, m, L.TABLE_COLS) or not table.is_contiguous()
+                or table.device != self.device):
+            raise ValueError("table must be a contiguous float32 device tensor [n,m_ref,10] matching ref_xy")
+        need = n * self.H * self.W
+        if getattr(self, "_lastw", None) is None or self._lastw.numel() < need:
+            self._lastw = torch.empty(need, dtype=torch.int32, device=self.device)
+        out = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_draw_tracking(_ptr(frames), n, self.H, self.W, sn, sr, _ptr(det), det.shape[1],
+                                                   _ptr(table), _ptr(ref), m, _ptr(self._lastw), _ptr(out), self._stream()),
+                        "vbs_draw_tracking")
+        return out
+
     # ---- a21, f1 -------------------------------------------------------------------------------
     def displacement(self, table, warmup_frames=100, min_marker_size_px=5.0, max_displacement=50.0,
                      frame_range=None):

@@ -3,13 +3,19 @@ argument meaning and exceptions; the per-frame work runs in HIP kernels on the M
 
     tracker = MarkerTracker(config)      # config keys as `marker_detection.py:478-489`
     tracker.process()                    # video -> <name>_markers.csv        (`:429-462`)
+                                         #   (+ <name>_tracked.avi with config["write_video"])
 
 Differences a maintainer should know (all deliberate):
  * frames are processed in device batches through the fused `vbs_track_to_3d`; the static per-stage
    methods (`_find_markers`, `_marker_center`, `_normxcorr2`) are kept with NumPy in / NumPy out;
  * video decode needs OpenCV, which is outside this path: `video_path` may also be a `.npy` / `.npz`
    array of frames [N,H,W(,3)] uint8, and `process_frames(frames)` takes frames already in memory;
-   the annotated AVI (`:69-76,453`) and the drawing calls are not produced (visual only);
+ * the annotated AVI (`:69-76,453`) is opt-in: `write_video` (default False; then nothing of it runs) draws the reference's
+   `_draw_tracking` overlays on every cropped (undistorted, with `calibration_params`) frame on the device (`Engine.draw_tracking`,
+   OpenCV's rasterisation restated, unverified against cv2 - cv2 is not installed) and writes `self.output_video` as
+   Motion-JPEG (`video_quality`, default 95; JPEG encoded on the device, `video_io.MjpegDeviceEncoder`) instead of the
+   reference's XVID: MJPG is what the sensor's camera records and what cv2 / ffmpeg read.  Gray input with `write_video`
+   raises ValueError (the reference only draws on BGR).  The static `_draw_marker` / `_draw_tracking` stay no-ops;
  * extra optional config keys: `id_mode` ("as_written" | "full"), `kmeans` ("optimal" | "sklearn"),
    `device` (GPU index), `batch` (frames per device batch), `gray_coeffs` (15 = OpenCV 4's BGR2GRAY fixed-point
    set, the default; 14 = the older set; identical on grey frames).
@@ -324,8 +330,9 @@ class MarkerTracker:
         return rows
 
     # ---- overlays (`:252-273`, `:398-427`) -------------------------------------------------------------
-    # Drawing into the annotated AVI is out of scope (a15 "_draw_tracking is OUT", a16 "AVI writer OUT");
-    # the names exist so that a caller written against the reference gets a no-op instead of an AttributeError.
+    # The annotated AVI is drawn on the device (`write_video`, `_video_batch`), not through these: they would draw on a
+    # caller's NumPy frame.  The names exist so that a caller written against the reference gets a no-op instead of an
+    # AttributeError.
     @staticmethod
     def _draw_marker(frame, center, ellipse, major, minor, angle):
         return None
@@ -353,6 +360,7 @@ class MarkerTracker:
                     except Exception:
                         # a frame the workspace cannot hold: the rows of the batches before it are not lost (the reference
                         # would have written a CSV covering them too)
+                        self._video_close(quiet=True)
                         if data:
                             self._save_results(data)
                         self._cleanup()
@@ -360,6 +368,7 @@ class MarkerTracker:
                     buf = []
                 if not ret:
                     break
+        self._video_close()
         self._save_results(data)
         self._cleanup()
 
@@ -412,6 +421,7 @@ class MarkerTracker:
                             fut.result()
                         except Exception:
                             pass
+                    self._video_close(quiet=True)
                     if data:
                         self._save_results(data)
                     self._cleanup()
@@ -433,13 +443,18 @@ class MarkerTracker:
                 data.append(self._process_batch(part))
             except Exception as e:
                 e.rows = _Rows(data)                    # what the batches before the failing frame produced
+                self._video_close(quiet=True)
                 if getattr(self, "_frames", None) is not None and data:
                     self._save_results(data)            # (called from `process`: keep the partial CSV)
                 raise
+        self._video_close()
         return _Rows(data)
 
     def _process_batch(self, frames):
         import torch
+        video = bool(self.config.get("write_video", False))
+        if video and (len(frames.shape) != 4 or frames.shape[3] != 3):
+            raise ValueError("write_video needs BGR frames [N,H,W,3]: the reference draws its overlays on colour frames only")
         left, right, top, bottom = _crop_box(self.width, self.height, self.config["crop_ratios"])
         eng = _engine(bottom - top, right - left, self.config.get("device"),
                       max(min(int(self.config.get("batch", 64)), max(int(frames.shape[0]), 1)), getattr(self, "_batch_hint", 1)),
@@ -479,6 +494,7 @@ class MarkerTracker:
         ids, ref_xy = getattr(self, "_ref_arrays", None) or _ids.reference_arrays(self.first_frame_markers)
         table, det, counts = eng.track_to_3d(ft, ref_xy, self.config.get("min_marker_distance", 20),
                                              want_det=True)
+        table_d, det_d = table, det
         counts = counts.cpu().numpy()
         if (counts < 0).any():                  # the reference would have emitted rows: never drop a frame silently
             from ._lib import VbsError
@@ -496,11 +512,62 @@ class MarkerTracker:
         block = {"frameno": self.frame_count + fi, "row": np.asarray(ids)[si, 0].astype(np.int64),
                  "col": np.asarray(ids)[si, 1].astype(np.int64), "Ox": refs[si, 0], "Oy": refs[si, 1],
                  "Cx": d[:, 0], "Cy": d[:, 1], "major_axis": d[:, 2], "minor_axis": d[:, 3], "angle": d[:, 4]}
+        if video:
+            self._video_batch(eng, ft, det_d, table_d, ref_xy)
         n_before = self.frame_count
         self.frame_count += table.shape[0]
         for k in range(n_before // 100 + 1, self.frame_count // 100 + 1):
             print(f"Processed frame {100 * k}")
         return _RowBlock(block, format_now=True)
+
+    # ---- the annotated video (`:69-76`, `self.writer.write(cropped)` `:453`) -----------------------------------------------
+    def _video_batch(self, eng, ft, det, table, ref_xy):
+        """Draw and encode one batch on the device; its files are downloaded and appended to the AVI by a host thread while
+        the next batch computes.  Only the JPEG files and their sizes leave the device."""
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+
+        from .video_io import AviWriter, MjpegDeviceEncoder
+        v = getattr(self, "_video", None)
+        if v is None:
+            fps = float(getattr(self, "fps", 0.0) or 0.0) or 30.0          # as for arrays without "fps"
+            h, w = int(ft.shape[1]), int(ft.shape[2])
+            v = self._video = {"enc": MjpegDeviceEncoder(eng.device, w, h, 64, int(self.config.get("video_quality", 95))),
+                               "writer": AviWriter(self.output_video, fps, w, h), "pool": ThreadPoolExecutor(1),
+                               "pending": deque()}
+        src = eng.undistort_frames(ft) if self.config.get("calibration_params") is not None else ft
+        drawn = eng.draw_tracking(src, det, table, ref_xy)
+        enc, writer, pending = v["enc"], v["writer"], v["pending"]
+
+        def write(ticket):
+            for jpeg in enc.fetch(ticket):
+                writer.write(jpeg)
+
+        for s in range(0, drawn.shape[0], enc.batch):
+            while len(pending) >= 2:                    # the encoder's slot of two batches back must have been fetched
+                pending.popleft().result()
+            pending.append(v["pool"].submit(write, enc.encode(drawn[s:s + enc.batch])))
+
+    def _video_close(self, quiet=False):
+        """Finish the annotated video: the batches handed to the writer thread are written, the AVI headers completed.  On
+        an error path (`quiet`) the file keeps the frames of the batches before the failure."""
+        v = getattr(self, "_video", None)
+        if v is None:
+            return
+        self._video = None
+        try:
+            while v["pending"]:
+                fut = v["pending"].popleft()
+                try:
+                    fut.result()
+                except Exception:
+                    if not quiet:
+                        raise
+        finally:
+            v["pool"].shutdown(wait=True)
+            v["writer"].release()
+            if not quiet:
+                print(f"Saved tracking video to {self.output_video}")
 
     def _save_results(self, data):
         """`:464-468`.  `data`: row dicts (the reference's form) or the per-batch column blocks of `_process_batch`."""

@@ -11,7 +11,9 @@ def process_video(video_dir="./video", input_name="test2.avi", output_csv="marke
                   **extra):
     """Track the marker array of `<video_dir>/<input_name>` and write `<video_dir>/<output_csv>` with
     columns frameno,row,col,Ox,Oy,Cx,Cy,major_axis,minor_axis,angle (`tracking.py:74-85,255`).
-    The defaults are the reference's constants; the annotated video is not produced."""
+    The defaults are the reference's constants.  `extra` config keys reach `MarkerTracker`; with `write_video=True`
+    (and optionally `video_quality`) the annotated video is written too, as `<video_dir>/<name>_tracked.avi` in
+    Motion-JPEG (the reference writes XVID)."""
     os.makedirs(video_dir, exist_ok=True)
     path = os.path.join(video_dir, input_name)
     if not os.path.exists(path):

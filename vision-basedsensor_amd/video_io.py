@@ -10,7 +10,10 @@ are reshaped.  The reader mimics the four `cv2.VideoCapture` calls the reference
 bounds the real-world rate from a file: 50 k frames/s natively, 3.3 k through Pillow (640x480).  Other codecs (XVID,
 H.264 ...) need a real decoder: IOError, as `cv2` absent did.
 
-`write_avi` is the matching minimal writer (MJPG or uncompressed), used by the tests to make fixtures on the fly.
+`AviWriter` is the matching streaming writer (MJPG or uncompressed, 'idx1' index, OpenDML 'AVIX' continuation beyond 1 GB);
+`write_avi` builds a whole clip on it with Pillow (the tests' fixtures).  `MjpegDeviceEncoder` encodes BGR frames on the device
+into JPEG files equal to Pillow's - the tracker's annotated video (`write_video`), Motion-JPEG where the reference writes XVID:
+MJPG is what the sensor's camera records and what cv2 / ffmpeg read.
 """
 from __future__ import annotations
 
@@ -313,6 +316,192 @@ class MjpegDeviceDecoder:
         return out[:m]
 
 
+class AviWriter:
+    """Streaming AVI writer (the `cv2.VideoWriter` calls the reference makes: `write`, `isOpened`, `release`): every `write`
+    appends one already-encoded frame (a JPEG file for MJPG, a bottom-up DIB for uncompressed) to the 'movi' list, an 'idx1'
+    index follows the first RIFF chunk, and the file continues in OpenDML 'AVIX' RIFF chunks - the form `AviReader` follows -
+    once the current one would pass `riff_bytes` (about 1 GB, the limit of the original AVI format) or, with `riff_frames` > 0,
+    holds that many frames.  The frame count and the largest frame size in the headers are patched in by `release()`."""
+
+    def __init__(self, path: str, fps: float, width: int, height: int, fourcc: bytes = b"MJPG", bits: int = 24,
+                 riff_frames: int = 0, riff_bytes: int = 1 << 30):
+        self.width, self.height, self.fps = int(width), int(height), float(fps)
+        self._fourcc, self._bits = bytes(fourcc), int(bits)
+        self._tag = b"00dc" if self._fourcc == b"MJPG" else b"00db"
+        self._riff_frames, self._riff_bytes = int(riff_frames), int(riff_bytes)
+        self.frames = 0
+        self._maxsz = 0
+        self._index = []                        # idx1 entries of the first RIFF chunk
+        self._riff = 0                          # RIFF chunks started so far
+        self._in_riff = 0                       # frames in the current one
+        self._f = open(path, "wb")
+        n = 0
+        avih = struct.pack("<14I", int(round(1e6 / fps)) if fps else 0, 0, 0, 0x10, n, 0, 1, 0, self.width, self.height, 0, 0, 0, 0)
+        rate, scale = int(round(fps * 1000)), 1000
+        strh = b"vids" + self._fourcc + struct.pack("<IHHIIIIIIII4h", 0, 0, 0, 0, scale, rate, 0, n, 0, 0xFFFFFFFF, 0, 0, 0,
+                                                    self.width, self.height)
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.width, self.height, 1, self._bits, self._fourcc, 0, 0, 0,
+                           256 if self._bits == 8 else 0, 0)
+        if self._bits == 8:
+            strf += b"".join(struct.pack("<4B", i, i, i, 0) for i in range(256))
+        strl = _chunk(b"strh", strh) + _chunk(b"strf", strf)
+        hdrl = _list(b"hdrl", _chunk(b"avih", avih) + _list(b"strl", strl))
+        # where release() patches the frame count and the suggested buffer size (offsets into the file)
+        avih_at = 12 + 12 + 8
+        strh_at = avih_at + 56 + 12 + 8
+        strf_at = strh_at + len(strh) + 8
+        self._patch = {"frames": (avih_at + 16, strh_at + 32), "maxsz": (avih_at + 28, strh_at + 36, strf_at + 20)}
+        self._f.write(b"RIFF" + struct.pack("<I", 0) + b"AVI " + hdrl)
+        self._open_movi()
+
+    def _open_movi(self):
+        self._riff_at = 0 if self._riff == 0 else self._f.tell()
+        if self._riff:
+            self._f.write(b"RIFF" + struct.pack("<I", 0) + b"AVIX")
+        self._movi_at = self._f.tell()
+        self._f.write(b"LIST" + struct.pack("<I", 0) + b"movi")
+        self._riff += 1
+        self._in_riff = 0
+
+    def _close_riff(self):
+        f = self._f
+        end = f.tell()
+        f.seek(self._movi_at + 4)
+        f.write(struct.pack("<I", end - self._movi_at - 8))
+        f.seek(end)
+        if self._riff == 1:
+            f.write(_chunk(b"idx1", b"".join(self._index)))
+            end = f.tell()
+        f.seek(self._riff_at + 4)
+        f.write(struct.pack("<I", end - self._riff_at - 8))
+        f.seek(end)
+
+    def isOpened(self) -> bool:
+        return self._f is not None
+
+    def write(self, payload) -> None:
+        """Append one encoded frame (bytes-like)."""
+        if self._f is None:
+            raise IOError("AviWriter is released")
+        data = bytes(payload)
+        size = 8 + len(data) + (len(data) & 1)
+        if self._in_riff and ((self._riff_frames > 0 and self._in_riff >= self._riff_frames) or
+                              self._f.tell() + size - self._riff_at > self._riff_bytes):
+            self._close_riff()
+            self._open_movi()
+        if self._riff == 1:
+            self._index.append(self._tag + struct.pack("<III", 0x10, self._f.tell() - self._movi_at - 8, len(data)))
+        self._f.write(_chunk(self._tag, data))
+        self.frames += 1
+        self._in_riff += 1
+        self._maxsz = max(self._maxsz, len(data))
+
+    def release(self) -> None:
+        if self._f is None:
+            return
+        f = self._f
+        self._close_riff()
+        for at in self._patch["frames"]:
+            f.seek(at)
+            f.write(struct.pack("<I", self.frames))
+        for at in self._patch["maxsz"]:
+            f.seek(at)
+            f.write(struct.pack("<I", self._maxsz))
+        f.close()
+        self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+
+def _chunk(cc, data):
+    return cc + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b"")
+
+
+def _list(kind, data):
+    return b"LIST" + struct.pack("<I", len(data) + 4) + kind + data
+
+
+class MjpegDeviceEncoder:
+    """Native Motion-JPEG encoder for BGR frames on the device (csrc/k_jpeg_enc.hip): colour conversion, 4:2:0 downsampling,
+    the islow forward DCT, quantisation AND the Huffman coding run as HIP kernels, so only the finished JPEG files (and their
+    sizes) cross PCIe.  The files equal Pillow's `Image.save(buf, "JPEG", quality=quality)` (libjpeg-turbo) byte for byte.
+
+    `encode(frames)` enqueues a batch on torch's current stream into one of two slots and returns a ticket; `fetch(ticket)`
+    (safe on a helper thread: it copies on a stream of its own) waits for that batch and returns its files as `bytes`.  A
+    slot is reused two `encode` calls later, so a batch's `fetch` must have returned before then."""
+
+    def __init__(self, device, width: int, height: int, batch: int, quality: int = 95):
+        import ctypes as C
+
+        import torch
+
+        from . import _lib as L
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("quality must be 1..100")
+        self._lib = L.lib()
+        self.device = torch.device(device)
+        self.width, self.height, self.batch, self.quality = int(width), int(height), int(batch), int(quality)
+        ws, pay, fb = C.c_int64(), C.c_int64(), C.c_int64()
+        if self._lib.vbs_jpeg_encode_workspace(self.width, self.height, self.batch, C.byref(ws), C.byref(pay), C.byref(fb)) != 0:
+            raise ValueError(f"frame size {self.width}x{self.height} / batch {self.batch} outside the encoder")
+        self.frame_bound = fb.value
+        self._ws = torch.empty(ws.value, dtype=torch.uint8, device=self.device)
+        self._pay = [torch.empty(pay.value, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._off = [torch.empty(self.batch, dtype=torch.int64, device=self.device) for _ in range(2)]
+        self._size = [torch.empty(self.batch, dtype=torch.int32, device=self.device) for _ in range(2)]
+        pin = self.device.type == "cuda"
+        self._hsize = [torch.empty(self.batch, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        self._copy = torch.cuda.Stream(device=self.device)
+        self._k = 0
+        self.downloaded_bytes = 0                       # what crossed to the host so far (sizes and files)
+
+    def encode(self, frames):
+        """frames: uint8 device tensor [m <= batch, H, W, 3] BGR (a crop view is fine) -> ticket for `fetch`."""
+        import torch
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.device != self.device:
+            raise ValueError("frames must be a uint8 BGR tensor [m,H,W,3] on the encoder's device")
+        m = int(frames.shape[0])
+        if tuple(frames.shape[1:3]) != (self.height, self.width) or m > self.batch:
+            raise ValueError(f"the encoder takes up to {self.batch} frames of {self.height}x{self.width}")
+        if frames.stride(3) != 1 or frames.stride(2) != 3:
+            frames = frames.contiguous()
+        slot = self._k & 1
+        self._k += 1
+        stream = torch.cuda.current_stream(self.device)
+        rc = self._lib.vbs_jpeg_encode(frames.data_ptr(), m, self.width, self.height, frames.stride(0), frames.stride(1),
+                                       self.quality, self._ws.data_ptr(), self._ws.numel(), self._pay[slot].data_ptr(),
+                                       self._pay[slot].numel(), self._off[slot].data_ptr(), self._size[slot].data_ptr(),
+                                       stream.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"vbs_jpeg_encode failed ({rc})")
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        # (the input frames may be reused by the caller as soon as the event has passed)
+        return (slot, m, ev, frames)
+
+    def fetch(self, ticket) -> list:
+        """The JPEG files of an `encode`d batch, in order (blocks until the batch is encoded)."""
+        import torch
+        slot, m, ev, _ = ticket
+        if not m:
+            return []
+        with torch.cuda.stream(self._copy):
+            self._copy.wait_event(ev)
+            self._hsize[slot][:m].copy_(self._size[slot][:m], non_blocking=True)
+            self._copy.synchronize()
+            sizes = self._hsize[slot][:m].numpy().astype(np.int64)
+            total = int(sizes.sum())
+            host = self._pay[slot][:total].to("cpu", non_blocking=False)   # the files, back to back from offset 0
+        self.downloaded_bytes += total + 4 * m
+        buf = host.numpy().tobytes()
+        ends = np.cumsum(sizes)
+        return [buf[e - s:e] for s, e in zip(sizes.tolist(), ends.tolist())]
+
+
 def write_avi(path: str, frames: np.ndarray, fps: float = 30.0, codec: str = "MJPG", quality: int = 95, subsampling: int = 2,
               riff_frames: int = 0, **jpeg_options):
     """frames uint8 [N,H,W,3] BGR or [N,H,W] gray -> AVI with one 'movi' list and an 'idx1' index.  `subsampling` (0 = 4:4:4,
@@ -323,50 +512,24 @@ def write_avi(path: str, frames: np.ndarray, fps: float = 30.0, codec: str = "MJ
         raise ValueError("frames must be uint8 [N,H,W] or [N,H,W,3]")
     n, h, w = frames.shape[:3]
     gray = frames.ndim == 3
-    payloads = []
     if codec.upper() == "MJPG":
         from PIL import Image
-        for fr in frames:
-            im = Image.fromarray(fr if gray else np.ascontiguousarray(fr[:, :, ::-1]))
-            bio = io.BytesIO()
-            im.save(bio, format="JPEG", quality=quality, subsampling=0 if gray else subsampling, **jpeg_options)
-            payloads.append(bio.getvalue())
         fourcc, bits = b"MJPG", 24
     else:
         bits = 8 if gray else 24
         stride = (w * bits // 8 + 3) & ~3
-        for fr in frames:
-            rows = np.zeros((h, stride), dtype=np.uint8)
-            rows[:, :w * bits // 8] = fr.reshape(h, -1)
-            payloads.append(rows[::-1].tobytes())
         fourcc = b"\x00\x00\x00\x00"
-    tag = b"00dc" if fourcc == b"MJPG" else b"00db"
-
-    def chunk(cc, data):
-        return cc + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b"")
-
-    def lst(kind, data):
-        return b"LIST" + struct.pack("<I", len(data) + 4) + kind + data
-
-    maxsz = max(len(p) for p in payloads) if payloads else 0
-    avih = struct.pack("<14I", int(round(1e6 / fps)) if fps else 0, 0, 0, 0x10, n, 0, 1, maxsz, w, h, 0, 0, 0, 0)
-    rate, scale = int(round(fps * 1000)), 1000
-    strh = b"vids" + fourcc + struct.pack("<IHHIIIIIIII4h", 0, 0, 0, 0, scale, rate, 0, n, maxsz, 0xFFFFFFFF, 0,
-                                         0, 0, w, h)
-    strf = struct.pack("<IiiHH4sIiiII", 40, w, h, 1, bits, fourcc, maxsz, 0, 0, 256 if bits == 8 else 0, 0)
-    if bits == 8:
-        strf += b"".join(struct.pack("<4B", i, i, i, 0) for i in range(256))
-    hdrl = lst(b"hdrl", chunk(b"avih", avih) + lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
-    first = payloads[:riff_frames] if riff_frames > 0 else payloads
-    movi_body, index, off = b"", b"", 4
-    for p in first:
-        index += tag + struct.pack("<III", 0x10, off, len(p))
-        c = chunk(tag, p)
-        movi_body += c
-        off += len(c)
-    body = b"AVI " + hdrl + lst(b"movi", movi_body) + chunk(b"idx1", index)
-    with open(path, "wb") as f:
-        f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
-        for k in range(len(first), len(payloads), max(riff_frames, 1)):       # OpenDML continuation chunks
-            ext = b"AVIX" + lst(b"movi", b"".join(chunk(tag, p) for p in payloads[k:k + riff_frames]))
-            f.write(b"RIFF" + struct.pack("<I", len(ext)) + ext)
+    out = AviWriter(path, fps, w, h, fourcc=fourcc, bits=bits, riff_frames=riff_frames, riff_bytes=1 << 62)
+    try:
+        for fr in frames:
+            if fourcc == b"MJPG":
+                im = Image.fromarray(fr if gray else np.ascontiguousarray(fr[:, :, ::-1]))
+                bio = io.BytesIO()
+                im.save(bio, format="JPEG", quality=quality, subsampling=0 if gray else subsampling, **jpeg_options)
+                out.write(bio.getvalue())
+            else:
+                rows = np.zeros((h, stride), dtype=np.uint8)
+                rows[:, :w * bits // 8] = fr.reshape(h, -1)
+                out.write(rows[::-1].tobytes())
+    finally:
+        out.release()
