@@ -92,10 +92,10 @@ int vbs_version(void);
  * vbs_track_to_3d run the odd internal passes of a call with a SECOND WORKSPACE on the handle's own stream (forked from
  * and joined to the caller's stream by events), so that the tail of one pass's kernels
  * overlaps the next pass; 1 runs every pass on the caller's stream.  The second workspace is a second copy of every
- * per-pass buffer (twice the device memory of the handle).  Setting the option to 2 EXPLICITLY builds it at once (a set-up
- * call: allocations, copies, one device synchronisation; VBS_ENOMEM / VBS_EHIP if it cannot be built).  A handle left at
- * the default builds it at its first call that spans several passes; if that call's stream is being captured, or the
- * workspace cannot be built, the call runs every pass on the caller's stream instead.  (With vbs_profile on, passes run on
+ * per-pass buffer, nearly doubling the handle's device memory (the constant tables exist once).  Setting the option to 2
+ * EXPLICITLY builds it at once (a set-up call: allocations, one device synchronisation; VBS_ENOMEM / VBS_EHIP if it cannot
+ * be built).  A handle left at the default builds it at its first call that spans several passes; if that call's stream
+ * is being captured, or the workspace cannot be built, the call runs every pass on the caller's stream instead.  (With vbs_profile on, passes run on
  * one stream: the per-kernel event timings would otherwise overlap.)  VBS_OPT_LATENCY_FRAMES (tuning, results identical):
  * an internal pass of at most this many frames (default 24, at most 32: 1 frame 128 against 264 us, 8: 185 / 324, 16: 269 / 356, 24: 346 / 390, 32: 424 / 406; the reference calls process() with ONE,
  * marker_detection.py:434-453) labels every frame with several workgroups (k_stage_lat) instead of one (k_stage); 0 = never. */

@@ -6,9 +6,6 @@
 
 #include "common.h"
 
-void launch_track_fused(vbs_handle* h, int nb, const double* ref_xy, int m_ref, double min_dist,
-                        float* table, const vbs_camera* cam, double min_size, hipStream_t s);
-
 // ---- host tables -----------------------------------------------------------------------------------
 // OpenCV 4 bit-exact uint8 Gaussian kernel in 8 fractional bits (see oracle/stages.py:gaussian_kernel_q8)
 static std::vector<int> gaussian_taps_q8(int ksize, double sigma) {
@@ -106,16 +103,48 @@ extern "C" int vbs_ncc_template(int l, double sigma, double* g, double* stats) {
 extern "C" int vbs_destroy(vbs_handle* h) {
     if (!h) return VBS_EINVAL;
     (void)hipSetDevice(h->device);
-    if (h->twin) { (void)vbs_destroy(h->twin); h->twin = nullptr; }
-    if (h->twin_stream) (void)hipStreamDestroy(h->twin_stream);
-    if (h->ev_tfork) (void)hipEventDestroy(h->ev_tfork);
-    if (h->ev_tjoin) (void)hipEventDestroy(h->ev_tjoin);
+    if (h->stream2) (void)hipStreamDestroy(h->stream2);
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (void* p : h->allocs) (void)hipFree(p);
     delete h;
     return VBS_OK;
 }
 
 extern "C" const char* vbs_last_error(const vbs_handle* h) { return h ? h->err.c_str() : "null handle"; }
+
+// The per-pass buffers of one workspace (its gray plane comes later: need_gray) and its NCC counters <- 0
+static int alloc_workspace(vbs_handle* h, Workspace& w) {
+    const size_t B = (size_t)h->maxb, M = (size_t)h->maxm, HW = (size_t)h->H * h->WW;
+    int rc;
+#define ALLOC(field, count) if ((rc = dev_alloc(h, &w.field, (count))) != VBS_OK) return rc
+    ALLOC(area_bits, B * HW); ALLOC(mask_bits, B * HW); ALLOC(band_bits, B * HW);
+    ALLOC(open_bits, B * HW);
+    ALLOC(wbase, B * 2 * HW);
+    if (2 * HW < (size_t)16 * SG_REC) ALLOC(stage_mrec, B * 16 * SG_REC);   // (k_stage.hip: stage_geom)
+    ALLOC(node_pos, B * 2 * VBS_RUN_CAP); ALLOC(node_comp, B * 2 * VBS_RUN_CAP);
+    ALLOC(ncomp, B * 2);
+    ALLOC(band_first, B * M); ALLOC(band_sums, B * M * 4);
+    ALLOC(area_first, B * M); ALLOC(area_sums, B * M * VBS_AREA_SUMS);
+    ALLOC(ell, B * M * 8); ALLOC(det64, B * M * 6);
+    ALLOC(cnt, B);
+    ALLOC(probe, B * M * 4); ALLOC(ncc_tot, 4);
+    // one allocation, one fill per pass: k_stage_lat's headers | slow counter | slow flags | frame statistics
+    ALLOC(lat_hdr, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + 4 + B + B * 8 + 8);     // (+ one spare word: displacement's first-frame cell)
+#undef ALLOC
+    w.slow_total = w.lat_hdr + (size_t)VBS_LAT_MAXN * VBS_LAT_HDR;
+    w.slow_flag = w.slow_total + 4;
+    w.fstat = w.slow_flag + B;
+    // the few-frames labelling kernel's scratch: optional (without it such passes take the batch kernel), at most 256 MB
+    w.lat_slots = 0;
+    if (const size_t per = stage_lat_scratch(h)) {
+        const size_t slots = std::min<size_t>(std::min<size_t>(B, VBS_LAT_MAXN), ((size_t)256 << 20) / per);
+        if (slots >= 1 && dev_alloc(h, &w.lat_scratch, per * slots) == VBS_OK) w.lat_slots = (int)slots;
+        else { w.lat_scratch = nullptr; h->err.clear(); (void)hipGetLastError(); }
+    }
+    HIPCHK(h, hipMemset(w.ncc_tot, 0, 4 * sizeof(u64)));
+    return VBS_OK;
+}
 
 extern "C" int vbs_create(int device, int height, int width, int max_markers, int max_batch,
                           vbs_handle** out) {
@@ -151,34 +180,9 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
         if (width >= (bp.small ? 176 : 240) && (width & 3) == 0) blur16_fragments(ka, kb, width, bp.small != 0, &frags16h, &frags16v);
     }
 
-    const size_t B = (size_t)max_batch, HW = (size_t)height * h->WW;
     int rc;
 #define ALLOC(field, count) if ((rc = dev_alloc(h, &h->field, (count))) != VBS_OK) return rc
-    h->gray = nullptr;                                  // allocated at the first 3-channel / undistorted use (need_gray)
-    ALLOC(area_bits, B * HW); ALLOC(mask_bits, B * HW); ALLOC(band_bits, B * HW);
-    ALLOC(open_bits, B * HW);
     ALLOC(ncc_rx, (size_t)width); ALLOC(ncc_ry, (size_t)height);
-    ALLOC(wbase, B * 2 * HW);
-    if (2 * HW < (size_t)16 * SG_REC) ALLOC(stage_mrec, B * 16 * SG_REC);   // (k_stage.hip: stage_geom)
-    ALLOC(node_pos, B * 2 * VBS_RUN_CAP); ALLOC(node_comp, B * 2 * VBS_RUN_CAP);
-    ALLOC(ncomp, B * 2);
-    ALLOC(band_first, B * max_markers); ALLOC(band_sums, B * max_markers * 4);
-    ALLOC(area_first, B * max_markers); ALLOC(area_sums, B * max_markers * VBS_AREA_SUMS);
-    ALLOC(ell, B * max_markers * 8); ALLOC(det64, B * max_markers * 6);
-    ALLOC(cnt, B);
-    ALLOC(probe, B * max_markers * 4); ALLOC(ncc_tot, 4);
-    // one allocation, one fill per pass: k_stage_lat's headers | slow counter | slow flags | frame statistics
-    ALLOC(lat_hdr, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + 4 + B + B * 8 + 8);     // (+ one spare word: displacement's first-frame cell)
-    h->slow_total = h->lat_hdr + (size_t)VBS_LAT_MAXN * VBS_LAT_HDR;
-    h->slow_flag = h->slow_total + 4;
-    h->fstat = h->slow_flag + B;
-    // the few-frames labelling kernel's scratch: optional (without it such passes take the batch kernel), at most 256 MB
-    h->lat_slots = 0;
-    if (const size_t per = stage_lat_scratch(h)) {
-        const size_t slots = std::min<size_t>(std::min<size_t>(B, VBS_LAT_MAXN), ((size_t)256 << 20) / per);
-        if (slots >= 1 && dev_alloc(h, &h->lat_scratch, per * slots) == VBS_OK) h->lat_slots = (int)slots;
-        else { h->lat_scratch = nullptr; h->err.clear(); (void)hipGetLastError(); }
-    }
     ALLOC(lut, 256);
     ALLOC(blur_frags, frags.size() / 4);
     if (!frags16h.empty()) { ALLOC(blur16_h, frags16h.size() / 4); ALLOC(blur16_v, frags16v.size() / 4); }
@@ -225,7 +229,7 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
         bilinear_weights_i16(wt.data());
         HIPCHK(h, hipMemcpy(h->uwtab, wt.data(), 4096 * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    HIPCHK(h, hipMemset(h->ncc_tot, 0, 4 * sizeof(u64)));
+    if ((rc = alloc_workspace(h, h->ws[0])) != VBS_OK) return rc;
     HIPCHK(h, hipDeviceSynchronize());
     return VBS_OK;
 }
@@ -241,58 +245,58 @@ static bool capturing(hipStream_t s) {
     return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
 }
 
-// The gray plane of 3-channel / undistorted input ([maxb][H][P]): gray frames never touch it, so it is allocated at the
-// first call that needs it, or by vbs_set_undistort.  Never under stream capture: there the call fails and says why.
-static int need_gray(vbs_handle* h, hipStream_t s) {
-    if (!h->gray) {
+// The gray plane of 3-channel / undistorted input ([maxb][H][P]) of workspace w: gray frames never touch it, so it is
+// allocated at the first call that needs it, or by vbs_set_undistort.  Never under stream capture: there the call fails
+// and says why.
+static int need_gray(vbs_handle* h, Workspace& w, hipStream_t s) {
+    const size_t bytes = (size_t)h->maxb * h->H * h->P;
+    if (!w.gray) {
         if (capturing(s)) {
             h->err = "the gray plane of 3-channel / undistorted input is allocated at first use: run one such call (or "
                      "vbs_set_undistort) outside stream capture first";
             return VBS_EINVAL;
         }
-        int rc = dev_alloc(h, &h->gray, (size_t)h->maxb * h->H * h->P);
+        int rc = dev_alloc(h, &w.gray, bytes);
         if (rc != VBS_OK) return rc;
     }
-    // the second workspace converts its own passes: its plane exists whenever this handle's does, so that a multi-pass
+    // the second workspace converts its own passes: its plane exists whenever the first one's does, so that a multi-pass
     // call on 3-channel frames captured into a graph finds it in place after ANY uncaptured 3-channel call
-    if (h->twin && !h->twin->gray && !capturing(s)) {
-        int rc = need_gray(h->twin, s);
-        if (rc != VBS_OK) { h->err = "second pass workspace: " + h->twin->err; return rc; }
+    if (h->nws == 2 && !h->ws[1].gray && !capturing(s)) {
+        int rc = dev_alloc(h, &h->ws[1].gray, bytes);
+        if (rc != VBS_OK) { h->err = "second pass workspace: " + h->err; return rc; }
     }
     return VBS_OK;
 }
 
 // The per-frame statistics of a pass <- 0; for a pass of a few frames also what launch_labelling would clear (k_stage_lat's
 // headers, the slow counter and flags lie in front of fstat in one allocation): one launch instead of two
-static void clear_pass(vbs_handle* h, int nb, hipStream_t s) {
-    h->last_ws = h; h->last_nb = nb;                     // every pass entry point records itself (vbs_track_to_3d names the
-                                                         // workspace of ITS last pass afterwards): vbs_frame_stats / vbs_stage_tables
-    if (nb <= h->lat_frames && (h->stage_impl == 0 || h->stage_impl >= 3) && nb <= h->lat_slots) {
-        launch_fill(h->lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + 4 + (size_t)h->maxb + (size_t)nb * 8, s);
-        h->pass_cleared = true;
+static void clear_pass(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
+    h->last_ws = &w;                                     // every pass records its workspace: vbs_frame_stats / vbs_stage_tables
+    if (nb <= h->lat_frames && (h->stage_impl == 0 || h->stage_impl >= 3) && nb <= w.lat_slots) {
+        launch_fill(w.lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + 4 + (size_t)h->maxb + (size_t)nb * 8, s);
+        w.pass_cleared = true;
     } else {
         // (the slow counter and the frames' flags lie right in front of the statistics: launch_labelling's fill with this one)
-        launch_fill(h->slow_total, 0u, (size_t)4 + (size_t)h->maxb + (size_t)nb * 8, s);
-        h->pass_cleared = true;
+        launch_fill(w.slow_total, 0u, (size_t)4 + (size_t)h->maxb + (size_t)nb * 8, s);
+        w.pass_cleared = true;
     }
 }
 
 // One internal pass of the detection stage: the blur reads gray frames directly, others are converted or remapped first.
-static int detect_pass(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n,
+static int detect_pass(vbs_handle* h, Workspace& w, const u8* frames, int nb, int channels, int64_t stride_n,
                        int64_t stride_row, u8* mask_u8, u8* area_u8, double* ncc_out, hipStream_t s) {
-    if (h->undist || channels != 1) { int rc = need_gray(h, s); if (rc != VBS_OK) return rc; }
-    h->last_ws = h; h->last_nb = nb;                     // (vbs_track_to_3d names the workspace of ITS last pass afterwards)
-    clear_pass(h, nb, s);
+    if (h->undist || channels != 1) { int rc = need_gray(h, w, s); if (rc != VBS_OK) return rc; }
+    clear_pass(h, w, nb, s);
     if (h->undist) {                                    // marker_detection.py:88-89: undistort, then cvtColor
-        launch_remap(h, frames, nb, channels, stride_n, stride_row, h->gray, 1, s);
-        launch_blur(h, h->gray, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
+        launch_remap(h, frames, nb, channels, stride_n, stride_row, w.gray, 1, s);
+        launch_blur(h, w, w.gray, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
     } else if (channels == 1) {
-        launch_blur(h, frames, stride_n, stride_row, nb, area_u8, s);
+        launch_blur(h, w, frames, stride_n, stride_row, nb, area_u8, s);
     } else {
-        launch_gray(h, frames, nb, channels, stride_n, stride_row, h->gray, s);
-        launch_blur(h, h->gray, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
+        launch_gray(h, frames, nb, channels, stride_n, stride_row, w.gray, s);
+        launch_blur(h, w, w.gray, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
     }
-    launch_ncc(h, nb, mask_u8, ncc_out, s);
+    launch_ncc(h, w, nb, mask_u8, ncc_out, s);
     return check_launch(h);
 }
 
@@ -302,8 +306,8 @@ static int detect_loop(vbs_handle* h, const u8* frames, int n, int channels, int
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
     for (int off = 0; off < n; off += h->maxb) {
-        int rc = detect_pass(h, frames + (int64_t)off * stride_n, std::min(h->maxb, n - off), channels, stride_n, stride_row,
-                             mask ? mask + off * hw : nullptr, area_mask ? area_mask + off * hw : nullptr,
+        int rc = detect_pass(h, h->ws[0], frames + (int64_t)off * stride_n, std::min(h->maxb, n - off), channels, stride_n,
+                             stride_row, mask ? mask + off * hw : nullptr, area_mask ? area_mask + off * hw : nullptr,
                              ncc ? ncc + off * hw : nullptr, s);
         if (rc != VBS_OK) return rc;
     }
@@ -344,32 +348,32 @@ extern "C" int vbs_normxcorr2(vbs_handle* h, const uint8_t* area_mask, int n, do
     if (!h) return VBS_EINVAL;
     if (!area_mask || n < 0 || (!ncc && !mask)) { h->err = "vbs_normxcorr2: bad argument"; return VBS_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
+    Workspace& w = h->ws[0];
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
     for (int off = 0; off < n; off += h->maxb) {
         int nb = std::min(h->maxb, n - off);
-        clear_pass(h, nb, s);
-        launch_threshold(h, area_mask + off * hw, area_mask + off * hw, nb, s);
-        launch_popcount(h, nb, s);
-        launch_ncc(h, nb, mask ? mask + off * hw : nullptr, ncc ? ncc + off * hw : nullptr, s);
+        clear_pass(h, w, nb, s);
+        launch_threshold(h, w, area_mask + off * hw, area_mask + off * hw, nb, s);
+        launch_popcount(h, w, nb, s);
+        launch_ncc(h, w, nb, mask ? mask + off * hw : nullptr, ncc ? ncc + off * hw : nullptr, s);
         int rc = check_launch(h);
         if (rc != VBS_OK) return rc;
     }
     return VBS_OK;
 }
 
-static int twin_of(vbs_handle* h);
+static int add_second_workspace(vbs_handle* h);
 
 extern "C" int vbs_set_option(vbs_handle* h, int option, int value) {
     if (!h) return VBS_EINVAL;
-    if (h->twin && option != VBS_OPT_PASS_STREAMS) (void)vbs_set_option(h->twin, option, value);     // (same checks, same answer)
     switch (option) {
         case VBS_OPT_PASS_STREAMS:
             if (value != 1 && value != 2) break;
             h->pass_streams = value;
             // an explicit 2 builds the second workspace NOW (a set-up call: allocations, copies, a device synchronisation),
             // so that no later vbs_track_to_3d has to - and a call captured into a graph finds it in place
-            if (value == 2 && !h->is_twin) { int rc = twin_of(h); if (rc != VBS_OK) return rc; }
+            if (value == 2) { int rc = add_second_workspace(h); if (rc != VBS_OK) return rc; }
             return VBS_OK;
         case VBS_OPT_FORCE_SEQ_MATCH: h->force_seq_match = value != 0; return VBS_OK;
         case VBS_OPT_NCC_MARGIN:
@@ -383,7 +387,6 @@ extern "C" int vbs_set_option(vbs_handle* h, int option, int value) {
         case VBS_OPT_LATENCY_FRAMES:
             if (value < 0 || value > VBS_LAT_MAXN) break;
             h->lat_frames = value;
-            if (h->twin) h->twin->lat_frames = value;
             return VBS_OK;
         case VBS_OPT_BLUR_IMPL:
             if (value != 0 && value != 1) break;
@@ -451,7 +454,7 @@ extern "C" int vbs_set_undistort(vbs_handle* h, const double* K9, const double* 
         return VBS_EINVAL;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = need_gray(h, (hipStream_t)stream);      // (a set-up call: the plane the undistorted frames go to)
+    int rc = need_gray(h, h->ws[0], (hipStream_t)stream);     // (a set-up call: the plane the undistorted frames go to)
     if (rc != VBS_OK) return rc;
     rc = setup_undistort(h, K9, dist, ndist, (hipStream_t)stream);
     if (rc != VBS_OK) return rc;
@@ -473,14 +476,11 @@ extern "C" int vbs_undistort_frames(vbs_handle* h, const uint8_t* frames, int n,
     return check_launch(h);
 }
 
-// the workspace the last internal pass ran in: with two pass streams that is the second workspace for an odd last pass
-static vbs_handle* last_ws(vbs_handle* h) { return (h->last_ws && (h->last_ws == h || h->last_ws == h->twin)) ? h->last_ws : h; }
-
 extern "C" int vbs_frame_stats(vbs_handle* h, uint32_t* out, int n) {
     if (!h || !out || n < 0 || n > h->maxb) return VBS_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());                   // (the last pass may have run on the handle's own stream)
-    HIPCHK(h, hipMemcpy(out, last_ws(h)->fstat, (size_t)n * 8 * sizeof(u32), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out, h->last_ws->fstat, (size_t)n * 8 * sizeof(u32), hipMemcpyDeviceToHost));
     return VBS_OK;
 }
 
@@ -490,15 +490,13 @@ extern "C" int vbs_stage_tables(vbs_handle* h, int n, uint32_t* ncomp, uint64_t*
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     const size_t N = (size_t)n, M = (size_t)h->maxm;
-    vbs_handle* const caller = h;
-    h = last_ws(h);
-    (void)caller;
-    if (ncomp) HIPCHK(h, hipMemcpy(ncomp, h->ncomp, N * 2 * sizeof(u32), hipMemcpyDeviceToHost));
-    if (band_sums) HIPCHK(h, hipMemcpy(band_sums, h->band_sums, N * M * 4 * sizeof(u64), hipMemcpyDeviceToHost));
-    if (area_first) HIPCHK(h, hipMemcpy(area_first, h->area_first, N * M * sizeof(u32), hipMemcpyDeviceToHost));
-    if (area_sums) HIPCHK(h, hipMemcpy(area_sums, h->area_sums, N * M * VBS_AREA_SUMS * sizeof(i64), hipMemcpyDeviceToHost));
-    if (probe) HIPCHK(h, hipMemcpy(probe, h->probe, N * M * 4 * sizeof(unsigned short), hipMemcpyDeviceToHost));
-    if (slow) HIPCHK(h, hipMemcpy(slow, h->slow_flag, N * sizeof(u32), hipMemcpyDeviceToHost));
+    const Workspace& w = *h->last_ws;
+    if (ncomp) HIPCHK(h, hipMemcpy(ncomp, w.ncomp, N * 2 * sizeof(u32), hipMemcpyDeviceToHost));
+    if (band_sums) HIPCHK(h, hipMemcpy(band_sums, w.band_sums, N * M * 4 * sizeof(u64), hipMemcpyDeviceToHost));
+    if (area_first) HIPCHK(h, hipMemcpy(area_first, w.area_first, N * M * sizeof(u32), hipMemcpyDeviceToHost));
+    if (area_sums) HIPCHK(h, hipMemcpy(area_sums, w.area_sums, N * M * VBS_AREA_SUMS * sizeof(i64), hipMemcpyDeviceToHost));
+    if (probe) HIPCHK(h, hipMemcpy(probe, w.probe, N * M * 4 * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    if (slow) HIPCHK(h, hipMemcpy(slow, w.slow_flag, N * sizeof(u32), hipMemcpyDeviceToHost));
     return VBS_OK;
 }
 
@@ -506,12 +504,11 @@ extern "C" int vbs_ncc_counters(vbs_handle* h, uint64_t out[3], int reset) {
     if (!h || !out) return VBS_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMemcpy(out, h->ncc_tot, 3 * sizeof(u64), hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(h, hipMemset(h->ncc_tot, 0, 4 * sizeof(u64)));
-    if (h->twin) {                                      // the passes the second workspace ran
+    for (int i = 0; i < 3; ++i) out[i] = 0;
+    for (int k = 0; k < h->nws; ++k) {                  // each workspace counts the passes it ran
         uint64_t t[3] = {0, 0, 0};
-        HIPCHK(h, hipMemcpy(t, h->twin->ncc_tot, 3 * sizeof(u64), hipMemcpyDeviceToHost));
-        if (reset) HIPCHK(h, hipMemset(h->twin->ncc_tot, 0, 4 * sizeof(u64)));
+        HIPCHK(h, hipMemcpy(t, h->ws[k].ncc_tot, 3 * sizeof(u64), hipMemcpyDeviceToHost));
+        if (reset) HIPCHK(h, hipMemset(h->ws[k].ncc_tot, 0, 4 * sizeof(u64)));
         for (int i = 0; i < 3; ++i) out[i] += t[i];
     }
     return VBS_OK;
@@ -539,15 +536,15 @@ extern "C" int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8
     if (!h) return VBS_EINVAL;
     if (!mask || !area_mask || !det || !counts || n < 0) { h->err = "vbs_marker_center: bad argument"; return VBS_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
+    Workspace& w = h->ws[0];
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
     for (int off = 0; off < n; off += h->maxb) {
         int nb = std::min(h->maxb, n - off);
-        clear_pass(h, nb, s);
-        h->last_ws = h; h->last_nb = nb;
-        launch_threshold(h, mask + off * hw, area_mask + off * hw, nb, s);
-        launch_labelling(h, nb, s);
-        launch_finalize(h, nb, det + (size_t)off * h->maxm * VBS_DET_COLS, counts + off, s);
+        clear_pass(h, w, nb, s);
+        launch_threshold(h, w, mask + off * hw, area_mask + off * hw, nb, s);
+        launch_labelling(h, w, nb, s);
+        launch_finalize(h, w, nb, det + (size_t)off * h->maxm * VBS_DET_COLS, counts + off, s);
         int rc = check_launch(h);
         if (rc != VBS_OK) return rc;
     }
@@ -580,36 +577,41 @@ extern "C" int vbs_solve3d(vbs_handle* h, float* table, int n, int m_ref, const 
     return check_launch(h);
 }
 
-// The second workspace of VBS_OPT_PASS_STREAMS = 2: a whole second handle (same geometry, same options) plus the stream
-// its passes run on and the two events that fork it from / join it to the caller's stream.
-static int twin_of(vbs_handle* h) {
-    if (h->twin) return VBS_OK;
-    vbs_handle* t = nullptr;
-    int rc = vbs_create(h->device, h->H, h->W, h->maxm, h->maxb, &t);
-    if (rc != VBS_OK) {
-        h->err = std::string("second pass workspace: ") + (t ? t->err : std::string("allocation failed"));
-        if (t) (void)vbs_destroy(t);
+// The second workspace of VBS_OPT_PASS_STREAMS = 2 (the per-pass buffers once more; geometry, options and tables are the
+// handle's) plus the stream its passes run on and the two events that fork it from / join it to the caller's stream.
+static int add_second_workspace(vbs_handle* h) {
+    if (h->nws == 2) return VBS_OK;
+    const size_t mark = h->allocs.size();
+    auto build = [&]() -> int {
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc = alloc_workspace(h, h->ws[1]);
+        if (rc != VBS_OK) return rc;
+        if (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
+            h->err = "stream / event creation failed";
+            return VBS_EHIP;
+        }
+        HIPCHK(h, hipDeviceSynchronize());
+        return VBS_OK;
+    };
+    int rc = build();
+    if (rc != VBS_OK) {                                 // (whatever of it exists goes: nothing half-made stays on h)
+        if (h->stream2) (void)hipStreamDestroy(h->stream2);
+        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+        if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+        h->stream2 = nullptr; h->ev_fork = h->ev_join = nullptr;
+        for (size_t i = mark; i < h->allocs.size(); ++i) (void)hipFree(h->allocs[i]);
+        h->allocs.resize(mark);
+        h->ws[1] = Workspace();
+        h->err = "second pass workspace: " + h->err;
         return rc;
     }
-    t->pass_streams = 1;
-    t->is_twin = true;
-    t->gray_bits = h->gray_bits; t->force_seq_match = h->force_seq_match; t->ncc_margin_ppm = h->ncc_margin_ppm;
-    t->stage_impl = h->stage_impl; t->blur_impl = h->blur_impl; t->lat_frames = h->lat_frames;
-    hipStream_t st = nullptr;
-    hipEvent_t ef = nullptr, ej = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ef, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ej, hipEventDisableTiming) != hipSuccess) {
-        if (st) (void)hipStreamDestroy(st);             // (whatever of the three exists goes: nothing half-made stays on h)
-        if (ef) (void)hipEventDestroy(ef);
-        if (ej) (void)hipEventDestroy(ej);
-        (void)vbs_destroy(t);
-        h->err = "second pass workspace: stream / event creation failed";
-        return VBS_EHIP;
+    h->nws = 2;
+    if (h->ws[0].gray) {                                // (need_gray: its plane exists whenever the first one's does)
+        rc = dev_alloc(h, &h->ws[1].gray, (size_t)h->maxb * h->H * h->P);
+        if (rc != VBS_OK) { h->err = "second pass workspace: " + h->err; return rc; }
     }
-    h->twin_stream = st; h->ev_tfork = ef; h->ev_tjoin = ej;
-    h->twin = t;
-    if (h->gray) { int rg = need_gray(t, nullptr); if (rg != VBS_OK) { h->err = "second pass workspace: " + t->err; return rg; } }
     return VBS_OK;
 }
 
@@ -631,46 +633,46 @@ extern "C" int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int 
     // next to the matrix-core kernels of the other (each workspace converts into its own gray plane).  Every pass writes its own slice of the
     // caller's tables; the second stream starts behind what the caller's stream holds and is joined before the return.
     bool two = h->pass_streams == 2 && !h->prof && !h->undist && n > h->maxb;
-    if (two && !h->twin) {
+    if (two && h->nws == 1) {
         // The second workspace normally exists by now (vbs_set_option(VBS_OPT_PASS_STREAMS, 2) builds it).  A handle left at
         // the default builds it at its first call that spans several passes - unless the caller's stream is being captured
         // (allocations and the device synchronisation of a set-up would break the capture), and if it cannot be built
         // (memory) the call simply runs every pass on the caller's stream: results are identical either way.
-        if (capturing(s) || twin_of(h) != VBS_OK) { two = false; h->err.clear(); }
+        if (capturing(s) || add_second_workspace(h) != VBS_OK) { two = false; h->err.clear(); }
     }
     if (two) {
-        HIPCHK(h, hipEventRecord(h->ev_tfork, s));
-        HIPCHK(h, hipStreamWaitEvent(h->twin_stream, h->ev_tfork, 0));
+        HIPCHK(h, hipEventRecord(h->ev_fork, s));
+        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
     }
     auto join = [&](int code) {                          // (also on the error returns: an un-joined fork breaks a capture)
         if (two) {
-            (void)hipEventRecord(h->ev_tjoin, h->twin_stream);
-            (void)hipStreamWaitEvent(s, h->ev_tjoin, 0);
+            (void)hipEventRecord(h->ev_join, h->stream2);
+            (void)hipStreamWaitEvent(s, h->ev_join, 0);
         }
         return code;
     };
     const int lead = two ? std::max(1, h->maxb / 2) : h->maxb;     // two pass streams: a first pass of half a batch puts them out of phase
     for (int k = 0, off = 0, nb = 0; off < n; off += nb, ++k) {
         nb = std::min(k == 0 ? lead : h->maxb, n - off);
-        vbs_handle* hh = (two && (k & 1)) ? h->twin : h;
-        hipStream_t ss = (two && (k & 1)) ? h->twin_stream : s;
-        int rc = detect_pass(hh, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, nullptr, nullptr, nullptr, ss);
-        if (rc != VBS_OK) { if (hh != h) h->err = hh->err; return join(rc); }
-        h->last_ws = hh; h->last_nb = nb;                // (what vbs_frame_stats / vbs_stage_tables read)
-        launch_labelling(hh, nb, ss);
-        if (table && nb <= hh->lat_frames)               // a few frames: detections and tracking rows in one launch
+        Workspace& w = h->ws[(two && (k & 1)) ? 1 : 0];
+        hipStream_t ss = (two && (k & 1)) ? h->stream2 : s;
+        int rc = detect_pass(h, w, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, nullptr, nullptr, nullptr,
+                             ss);
+        if (rc != VBS_OK) return join(rc);
+        launch_labelling(h, w, nb, ss);
+        if (table && nb <= h->lat_frames)                // a few frames: detections and tracking rows in one launch
                                                          // (for a batch pass the one launch measured nothing: 282.1 k against 283.1 k frames/s)
-            launch_finalize_track(hh, nb, det ? det + (size_t)off * h->maxm * VBS_DET_COLS : nullptr, counts ? counts + off : nullptr,
+            launch_finalize_track(h, w, nb, det ? det + (size_t)off * h->maxm * VBS_DET_COLS : nullptr, counts ? counts + off : nullptr,
                                   ref_xy, m_ref, min_dist, table + (size_t)off * m_ref * VBS_TABLE_COLS, cam, min_marker_size_px, ss);
         else {
-            launch_finalize(hh, nb, det ? det + (size_t)off * h->maxm * VBS_DET_COLS : nullptr,
+            launch_finalize(h, w, nb, det ? det + (size_t)off * h->maxm * VBS_DET_COLS : nullptr,
                             counts ? counts + off : nullptr, ss);
             if (table)
-                launch_track_fused(hh, nb, ref_xy, m_ref, min_dist, table + (size_t)off * m_ref * VBS_TABLE_COLS, cam,
+                launch_track_fused(h, w, nb, ref_xy, m_ref, min_dist, table + (size_t)off * m_ref * VBS_TABLE_COLS, cam,
                                    min_marker_size_px, ss);
         }
-        rc = check_launch(hh);
-        if (rc != VBS_OK) { if (hh != h) h->err = hh->err; return join(rc); }
+        rc = check_launch(h);
+        if (rc != VBS_OK) return join(rc);
     }
     return join(VBS_OK);
 }
@@ -685,7 +687,7 @@ extern "C" int vbs_displacement_range(vbs_handle* h, const float* table, int n, 
     }
     HIPCHK(h, hipSetDevice(h->device));
     if (frame_end > frame_begin)
-        launch_displacement(h, table, n, m_ref, warmup_frames, min_marker_size_px, max_displacement, frame_begin,
+        launch_displacement(h, h->ws[0], table, n, m_ref, warmup_frames, min_marker_size_px, max_displacement, frame_begin,
                             frame_end, disp, (hipStream_t)stream);
     return check_launch(h);
 }
@@ -750,9 +752,8 @@ extern "C" int vbs_assign_ids(vbs_handle* h, const double* det, const int32_t* c
 // tools/ builds only: k_stage_lat's per-frame header words of the last pass (phase stamps in words 80..), synchronising
 extern "C" int vbs_debug_lat_hdr(vbs_handle* h, uint32_t* out, int frames) {
     if (!h || !out || frames < 1 || frames > VBS_LAT_MAXN) return VBS_EINVAL;
-    vbs_handle* w = last_ws(h);
     HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMemcpy(out, w->lat_hdr, (size_t)frames * VBS_LAT_HDR * sizeof(u32), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out, h->last_ws->lat_hdr, (size_t)frames * VBS_LAT_HDR * sizeof(u32), hipMemcpyDeviceToHost));
     return VBS_OK;
 }
 #endif

@@ -50,38 +50,14 @@ static inline GrayCoef gray_coef(int bits) {
 struct ProfRec { const char* name; hipEvent_t a, b; };
 
 #define SG_REC 2048                // k_stage / k_stage_lat: segment records per frame, at most (StageGeom::rec_cap)
-struct vbs_handle {
-    bool prof = false;                     // record a HIP event pair around every kernel launch
-    std::vector<ProfRec> recs;
-    int device, H, W, P, WW, maxm, maxb;   // P = row pitch (mult. of 64), WW = P/64 words per row
-    BranchParams bp;
-    NccConst ncc;
-    std::string err;
-    // ---- device workspace (per internal pass of maxb frames) ----
-    u8* gray;          // [maxb][H][P]   gray plane of 3-channel / undistorted input; null until first needed (need_gray)
-    uint4* blur_frags; // Toeplitz operand fragments of k_blur_mfma (blur_mfma_fragments)
-    uint4* blur16_h = nullptr;   // k_blur16: horizontal fragments per 16-column strip (blur16_fragments); null = not built
-    uint4* blur16_v = nullptr;   // k_blur16: the 12 vertical fragment variants
-    int blur_impl = 0;           // vbs_set_option(VBS_OPT_BLUR_IMPL): 0 k_blur16 where it applies, 1 always k_blur_mfma
-    // vbs_set_option(VBS_OPT_PASS_STREAMS) = 2: the internal passes of vbs_track_to_3d alternate between this handle on the
-    // caller's stream and a second workspace (`twin`, created at first use) on `twin_stream`
-    int pass_streams = 2;
-    vbs_handle* twin = nullptr;
-    bool is_twin = false;                  // this handle IS some handle's second workspace (never grows one of its own)
-    vbs_handle* last_ws = nullptr;         // workspace (this handle or its twin) and length of the last internal pass
-    int last_nb = 0;
-    hipStream_t twin_stream = nullptr;
-    hipEvent_t ev_tfork = nullptr, ev_tjoin = nullptr;
+
+// What the kernels of one internal pass (at most maxb frames) write.  A handle has one, or two with VBS_OPT_PASS_STREAMS = 2.
+struct Workspace {
+    u8* gray = nullptr;   // [maxb][H][P]   gray plane of 3-channel / undistorted input; null until first needed (need_gray)
     u64* area_bits;    // [maxb][H][WW]
     u64* mask_bits;    // [maxb][H][WW]
     u64* band_bits;    // [maxb][H][WW]
     u64* open_bits;    // [maxb][H][WW]
-    double* ncc_rx;    // [W]  sum of g over the in-image part of the window (columns)
-    double* ncc_ry;    // [H]
-    uint4* ncc_frags;  // Toeplitz operand fragments of k_ncc_mfma (ncc_mfma_fragments)
-    float2* ncc_rowf;  // [H] {rows of the NCC window inside the image, (float) ncc_ry}: border tiles of k_ncc_mfma
-    double* ncc_tab;   // [VBS_NCC_MAXL] g, then [VBS_NCC_MAXL + 1] cg: the exact path of k_ncc_mfma reads them from memory
-    u32* fstat;        // [maxb][8]  0: area popcount, 1: ambiguous ncc pixels, 2: status
     u32* wbase;        // [maxb][2][H*WW]   first node index of each word
     u32* stage_mrec = nullptr;   // k_stage's moment records when a frame's slice of wbase would hold fewer than SG_REC of them
                                  // (small frames with many blobs: the reference's real 65-dot layout); null = they live in wbase
@@ -96,26 +72,56 @@ struct vbs_handle {
     double* det64;     // [maxb][maxm][6]
     int32_t* cnt;      // [maxb]
     unsigned short* probe;   // [maxb][maxm][4]  component ids of the 2x2 cell around every band centroid
-    u64* ncc_tot;      // [4]  running NCC decision counters (vbs_ncc_counters)
+    u64* ncc_tot;      // [4]  running NCC decision counters of the passes run here (vbs_ncc_counters sums the workspaces')
     u32* lat_hdr;      // [VBS_LAT_MAXN][VBS_LAT_HDR] k_stage_lat's per-frame counters; slow_total / slow_flag follow (one fill clears all)
-    unsigned char* lat_scratch = nullptr;   // [VBS_LAT_MAXN][stage_lat_scratch()] what the workgroups of a frame share; null = path not available
-    int lat_slots = 0;              // frames lat_scratch holds (min(max_batch, VBS_LAT_MAXN), fewer for very large frames)
-    int lat_frames = 24;            // vbs_set_option(VBS_OPT_LATENCY_FRAMES): passes of <= this many frames take k_stage_lat (0: never)
-    size_t lat_lds_set = 0;
-    bool pass_cleared = false;      // detect_pass cleared the labelling headers / flags of this pass together with fstat
     u32* slow_total;   // [1]  frames of this pass the fused kernel handed on (lets the general kernels leave at once)
     u32* slow_flag;    // [maxb]  non-zero = the fast labelling path handed the frame on (the value says why)
-    size_t stage_lds_set[2] = {0, 0}, ccl_lds_set[2] = {0, 0};   // dynamic LDS declared for k_stage / k_ccl<0|1> through this handle
-    int stage_impl = 0;             // vbs_set_option(VBS_OPT_STAGE_IMPL): 0 fused k_stage, 1 the round-2 kernels (k_morph + k_ccl), 2 k_label for every frame, 3 / 4 fused at 768 / 256 threads
-    int gray_bits = 15;             // BGR2GRAY fixed-point coefficient set: 15 (OpenCV 4) | 14 (OpenCV <= 3.4.1)
-    bool force_seq_match = false;   // vbs_set_option(VBS_OPT_FORCE_SEQ_MATCH)
-    int ncc_margin_ppm = 0;         // vbs_set_option(VBS_OPT_NCC_MARGIN): test hook, widens the float32 filter's margin
+    u32* fstat;        // [maxb][8]  0: area popcount, 1: ambiguous ncc pixels, 2: status
+    unsigned char* lat_scratch = nullptr;   // [VBS_LAT_MAXN][stage_lat_scratch()] what the workgroups of a frame share; null = path not available
+    int lat_slots = 0;              // frames lat_scratch holds (min(max_batch, VBS_LAT_MAXN), fewer for very large frames)
+    bool pass_cleared = false;      // detect_pass cleared the labelling headers / flags of this pass together with fstat
+};
+
+struct vbs_handle {
+    bool prof = false;                     // record a HIP event pair around every kernel launch
+    std::vector<ProfRec> recs;
+    int device, H, W, P, WW, maxm, maxb;   // P = row pitch (mult. of 64), WW = P/64 words per row
+    BranchParams bp;
+    NccConst ncc;
+    std::string err;
+    // ---- constant tables (vbs_create, vbs_set_undistort) ----
+    uint4* blur_frags; // Toeplitz operand fragments of k_blur_mfma (blur_mfma_fragments)
+    uint4* blur16_h = nullptr;   // k_blur16: horizontal fragments per 16-column strip (blur16_fragments); null = not built
+    uint4* blur16_v = nullptr;   // k_blur16: the 12 vertical fragment variants
+    double* ncc_rx;    // [W]  sum of g over the in-image part of the window (columns)
+    double* ncc_ry;    // [H]
+    uint4* ncc_frags;  // Toeplitz operand fragments of k_ncc_mfma (ncc_mfma_fragments)
+    float2* ncc_rowf;  // [H] {rows of the NCC window inside the image, (float) ncc_ry}: border tiles of k_ncc_mfma
+    double* ncc_tab;   // [VBS_NCC_MAXL] g, then [VBS_NCC_MAXL + 1] cg: the exact path of k_ncc_mfma reads them from memory
     u8* lut;           // [256] contour vertex table
     short* umap1;      // [H][W][2] int16 undistortion source pixel (CV_16SC2)
     unsigned short* umap2;   // [H][W] fractional index into the bilinear weight table
     int* uwtab;        // [1024][4] bilinear weights in 1/32768
     bool undist = false;     // frame undistortion enabled (vbs_set_undistort)
     double newK[9];
+    // ---- options (vbs_set_option) ----
+    int blur_impl = 0;              // VBS_OPT_BLUR_IMPL: 0 k_blur16 where it applies, 1 always k_blur_mfma
+    int pass_streams = 2;           // VBS_OPT_PASS_STREAMS
+    int stage_impl = 0;             // VBS_OPT_STAGE_IMPL: 0 fused k_stage, 1 the round-2 kernels (k_morph + k_ccl), 2 k_label for every frame, 3 / 4 fused at 768 / 256 threads
+    int gray_bits = 15;             // VBS_OPT_GRAY_COEFFS, the BGR2GRAY fixed-point coefficient set: 15 (OpenCV 4) | 14 (OpenCV <= 3.4.1)
+    bool force_seq_match = false;   // VBS_OPT_FORCE_SEQ_MATCH
+    int ncc_margin_ppm = 0;         // VBS_OPT_NCC_MARGIN: test hook, widens the float32 filter's margin
+    int lat_frames = 24;            // VBS_OPT_LATENCY_FRAMES: passes of <= this many frames take k_stage_lat (0: never)
+    // dynamic LDS declared (hipFuncSetAttribute) for k_stage / k_ccl<0|1> / k_stage_lat through this handle
+    size_t stage_lds_set[2] = {0, 0}, ccl_lds_set[2] = {0, 0}, lat_lds_set = 0;
+    // ---- per-pass workspaces ----
+    // VBS_OPT_PASS_STREAMS = 2: the internal passes of vbs_track_to_3d alternate between ws[0] on the caller's stream and
+    // ws[1] on `stream2`; ws[1], the stream and its fork / join events are built at first use (nws = 2)
+    Workspace ws[2];
+    int nws = 1;
+    Workspace* last_ws = ws;               // the workspace of the last internal pass (vbs_frame_stats, vbs_stage_tables)
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<void*> allocs;
 };
 
@@ -139,24 +145,24 @@ struct vbs_handle {
         if ((h)->prof) { (void)hipEventRecord(b_, s); (h)->recs.push_back({name, a_, b_}); } \
     } while (0)
 
-// ---- launchers (each enqueues on `s`; nb = frames in this pass) --------------------------------
+// ---- launchers (each enqueues on `s`; nb = frames in this pass, whose buffers are those of workspace `w`) ----------
 void launch_gray(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n,
                  int64_t stride_row, u8* gray, hipStream_t s);
 void launch_gray_dense(vbs_handle* h, const u8* frames, int nb, int64_t stride_n, int64_t stride_row, u8* out,
                        hipStream_t s);
-void launch_blur(vbs_handle* h, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
+void launch_blur(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
                  u8* area_u8, hipStream_t s);
-void launch_ncc(vbs_handle* h, int nb, u8* mask_u8, double* ncc_out, hipStream_t s);
+void launch_ncc(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, double* ncc_out, hipStream_t s);
 void launch_points(int which, const double* in, int n, const vbs_camera& cam, double* out, int32_t* ok,
                    hipStream_t s);
-void launch_threshold(vbs_handle* h, const u8* mask, const u8* area, int nb, hipStream_t s);
-void launch_labelling(vbs_handle* h, int nb, hipStream_t s);    // band / open planes, their components and sums (a9 - a12)
-void launch_finalize(vbs_handle* h, int nb, double* det, int32_t* counts, hipStream_t s);
+void launch_threshold(vbs_handle* h, Workspace& w, const u8* mask, const u8* area, int nb, hipStream_t s);
+void launch_labelling(vbs_handle* h, Workspace& w, int nb, hipStream_t s);    // band / open planes, their components and sums (a9 - a12)
+void launch_finalize(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, hipStream_t s);
 void launch_track(vbs_handle* h, const double* det, const int32_t* counts32, int nb,
                   const double* ref_xy, int m_ref, double min_dist, float* table, hipStream_t s);
 void launch_solve3d(vbs_handle* h, float* table, int n, int m_ref, const vbs_camera& cam,
                     double min_size, hipStream_t s);
-void launch_displacement(vbs_handle* h, const float* table, int n, int m_ref, int warmup,
+void launch_displacement(vbs_handle* h, Workspace& w, const float* table, int n, int m_ref, int warmup,
                          double min_size, double max_disp, int f0, int f1, float* disp, hipStream_t s);
 void launch_plane_fit(vbs_handle* h, const float* table, int n, int m_ref, float* plane,
                       hipStream_t s);
@@ -170,12 +176,12 @@ std::vector<u32> blur_mfma_fragments(const std::vector<int>& taps_a, const std::
                                      int sa0, int nka);
 void blur16_fragments(const std::vector<int>& taps_s, const std::vector<int>& taps_l, int W, bool small, std::vector<u32>* hfrag,
                       std::vector<u32>* vfrag);
-void launch_track_fused(vbs_handle* h, int nb, const double* ref_xy, int m_ref, double min_dist,
+void launch_track_fused(vbs_handle* h, Workspace& w, int nb, const double* ref_xy, int m_ref, double min_dist,
                         float* table, const vbs_camera* cam, double min_size, hipStream_t s);
 // launch_finalize + launch_track_fused as one launch (k_finalize_track: passes of a few frames)
-void launch_finalize_track(vbs_handle* h, int nb, double* det, int32_t* counts, const double* ref_xy, int m_ref, double min_dist,
-                           float* table, const vbs_camera* cam, double min_size, hipStream_t s);
-void launch_popcount(vbs_handle* h, int nb, hipStream_t s);
+void launch_finalize_track(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, const double* ref_xy, int m_ref,
+                           double min_dist, float* table, const vbs_camera* cam, double min_size, hipStream_t s);
+void launch_popcount(vbs_handle* h, Workspace& w, int nb, hipStream_t s);
 size_t stage_lat_scratch(const vbs_handle* h);          // bytes of scratch per frame k_stage_lat needs for this geometry (0: not taken)
 // n 32-bit words <- value, as a KERNEL on `s`: the per-pass clears of the hot path.  (Not hipMemsetAsync: captured into a HIP
 // graph, the memset nodes of a one-stream multi-pass call left the first pass's status words holding address-like garbage

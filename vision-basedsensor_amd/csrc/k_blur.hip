@@ -855,7 +855,7 @@ void launch_gray(vbs_handle* h, const u8* frames, int nb, int channels, int64_t 
                        h->H, h->W, h->P, gray_coef(h->gray_bits), vec_ok, flat);
 }
 
-void launch_blur(vbs_handle* h, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
+void launch_blur(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
                  u8* area_u8, hipStream_t s) {
     const int k3 = 256 * (128 + 32768) + 32768, k8 = k3 + (15 - h->bp.thresh) * 65536;
     if (blur16_takes(h, gray, gstride_n, gstride_row)) {
@@ -870,7 +870,7 @@ void launch_blur(vbs_handle* h, const u8* gray, int64_t gstride_n, int64_t gstri
         dim3 grid16 = xcd ? dim3((unsigned)((nb + 7) / 8 * 8 * gx16 * nseg)) : dim3(gx16, nseg, nb);
 #define B16_GO(U8, SB_, SH_)                                                                                                  \
     VBS_LAUNCH(h, s, "k_blur16", (k_blur16<U8, SB_, SH_>), grid16, dim3(64 * (B16_NSW + 1)), 0, s, gray, gstride_n,              \
-               (int)gstride_row, h->blur16_h, h->blur16_v, h->area_bits, area_u8, h->fstat, h->H, h->W, h->WW, tps, k3, k8,     \
+               (int)gstride_row, h->blur16_h, h->blur16_v, w.area_bits, area_u8, w.fstat, h->H, h->W, h->WW, tps, k3, k8,     \
                h->bp.hi - h->bp.thresh, xcd, gx16, nseg, VBS_KNOB("VBS_BLUR16_DROP"))
 #define B16_GO2(U8, SB_) do { if (h->W & 7) B16_GO(U8, SB_, true); else B16_GO(U8, SB_, false); } while (0)
         if (h->bp.small) { if (area_u8) B16_GO2(true, true); else B16_GO2(false, true); }
@@ -886,7 +886,7 @@ void launch_blur(vbs_handle* h, const u8* gray, int64_t gstride_n, int64_t gstri
     dim3 grid(gx, nseg, nb);
 #define BLUR_GO(NK, SA0, NKA, U8)                                                                            \
     VBS_LAUNCH(h, s, "k_blur_mfma", (k_blur_mfma<NK, SA0, NKA, U8>), grid, dim3(256), 0, s, gray, gstride_n, \
-               gstride_row, h->blur_frags, h->area_bits, area_u8, h->fstat, h->H, h->W, h->WW, tps, k3, k8,  \
+               gstride_row, h->blur_frags, w.area_bits, area_u8, w.fstat, h->H, h->W, h->WW, tps, k3, k8,  \
                h->bp.hi - h->bp.thresh, VBS_KNOB("VBS_BLUR_DBG"))
     if (!h->bp.small) { if (area_u8) BLUR_GO(5, 1, 3, true); else BLUR_GO(5, 1, 3, false); }
     else { if (area_u8) BLUR_GO(3, 0, 3, true); else BLUR_GO(3, 0, 3, false); }

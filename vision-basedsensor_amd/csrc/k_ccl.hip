@@ -532,7 +532,7 @@ static bool ccl_layout(const vbs_handle* h, int mode, CclGeom* g, size_t* lds_by
     return g->items < 65535 && h->W <= 4096 && h->H <= 2048 && cap >= 1024;     // (record: 9 + 11 + 12 bits)
 }
 
-bool launch_ccl(vbs_handle* h, int nb, hipStream_t s) {
+bool launch_ccl(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
     CclGeom g0, g1;
     size_t l0 = 0, l1 = 0;
     const bool fast = ccl_layout(h, 0, &g0, &l0) && ccl_layout(h, 1, &g1, &l1);
@@ -547,10 +547,10 @@ bool launch_ccl(vbs_handle* h, int nb, hipStream_t s) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_ccl<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1) != hipSuccess) { (void)hipGetLastError(); return false; }
             h->ccl_lds_set[1] = l1;
         }
-        VBS_LAUNCH(h, s, "k_ccl_band", k_ccl<0>, dim3(nb), dim3(CCL_NT), l0, s, h->band_bits, h->ncomp, h->band_first,
-                   h->band_sums, h->area_sums, h->probe, h->fstat, h->slow_flag, h->wbase, h->lut, g0, h->maxm);
-        VBS_LAUNCH(h, s, "k_ccl_open", k_ccl<1>, dim3(nb), dim3(CCL_NT), l1, s, h->open_bits, h->ncomp, h->area_first,
-                   h->band_sums, h->area_sums, h->probe, h->fstat, h->slow_flag, h->wbase, h->lut, g1, h->maxm);
+        VBS_LAUNCH(h, s, "k_ccl_band", k_ccl<0>, dim3(nb), dim3(CCL_NT), l0, s, w.band_bits, w.ncomp, w.band_first,
+                   w.band_sums, w.area_sums, w.probe, w.fstat, w.slow_flag, w.wbase, h->lut, g0, h->maxm);
+        VBS_LAUNCH(h, s, "k_ccl_open", k_ccl<1>, dim3(nb), dim3(CCL_NT), l1, s, w.open_bits, w.ncomp, w.area_first,
+                   w.band_sums, w.area_sums, w.probe, w.fstat, w.slow_flag, w.wbase, h->lut, g1, h->maxm);
     }
     return fast;                                         // false: every frame takes the general kernel
 }

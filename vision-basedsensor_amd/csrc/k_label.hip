@@ -70,11 +70,11 @@ __global__ __launch_bounds__(256) void k_threshold(const u8* __restrict__ mask,
     }
 }
 
-void launch_threshold(vbs_handle* h, const u8* mask, const u8* area, int nb, hipStream_t s) {
+void launch_threshold(vbs_handle* h, Workspace& w, const u8* mask, const u8* area, int nb, hipStream_t s) {
     int64_t total = (int64_t)nb * h->H * (h->P / 16);
     int vec_ok = (h->W % 16 == 0) && (((uintptr_t)mask | (uintptr_t)area) % 16 == 0);
     VBS_LAUNCH(h, s, "k_threshold", k_threshold, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mask, area,
-                       h->mask_bits, h->area_bits, nb, h->H, h->W, h->P, h->WW, vec_ok);
+                       w.mask_bits, w.area_bits, nb, h->H, h->W, h->P, h->WW, vec_ok);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void k_morph(const u64* __restrict__ mbits, co
     morph_wave<NS14>(mbits, abits, band, opn, H, W, WW, G, strips, rows_per_strip, n, gw - n * waves_per_frame);
 }
 
-static void launch_morph(vbs_handle* h, int nb, const u32* only, hipStream_t s) {
+static void launch_morph(vbs_handle* h, Workspace& w, int nb, const u32* only, hipStream_t s) {
     const int G = 64 / h->WW;                            // strips per wave (WW <= 64)
     // strips per frame: enough waves to fill the chip several times over, but strips much longer than the ns - 1 rows
     // each re-reads
@@ -211,11 +211,11 @@ static void launch_morph(vbs_handle* h, int nb, const u32* only, hipStream_t s) 
     const int waves = nb * wpf;
     dim3 grid((waves + 3) / 4);
     if (h->bp.ns == 14)
-        VBS_LAUNCH(h, s, "k_morph", k_morph<14>, grid, dim3(256), 0, s, h->mask_bits, h->area_bits, h->band_bits, h->open_bits,
-                   only, only ? h->slow_total : nullptr, nb, h->H, h->W, h->WW, G, strips, rps, wpf);
+        VBS_LAUNCH(h, s, "k_morph", k_morph<14>, grid, dim3(256), 0, s, w.mask_bits, w.area_bits, w.band_bits, w.open_bits,
+                   only, only ? w.slow_total : nullptr, nb, h->H, h->W, h->WW, G, strips, rps, wpf);
     else
-        VBS_LAUNCH(h, s, "k_morph", k_morph<8>, grid, dim3(256), 0, s, h->mask_bits, h->area_bits, h->band_bits, h->open_bits,
-                   only, only ? h->slow_total : nullptr, nb, h->H, h->W, h->WW, G, strips, rps, wpf);
+        VBS_LAUNCH(h, s, "k_morph", k_morph<8>, grid, dim3(256), 0, s, w.mask_bits, w.area_bits, w.band_bits, w.open_bits,
+                   only, only ? w.slow_total : nullptr, nb, h->H, h->W, h->WW, G, strips, rps, wpf);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -881,45 +881,45 @@ __global__ __launch_bounds__(1024) void k_label(u64* band_bits,
     }                                                   // frames
 }
 
-bool launch_ccl(vbs_handle* h, int nb, hipStream_t s);   // false: geometry outside the round-2 fast path
-bool launch_stage(vbs_handle* h, int nb, hipStream_t s);  // false: geometry outside the fused path
-bool launch_stage_lat(vbs_handle* h, int nb, hipStream_t s);   // k_stage_lat.hip; false: not for this pass
+bool launch_ccl(vbs_handle* h, Workspace& w, int nb, hipStream_t s);   // false: geometry outside the round-2 fast path
+bool launch_stage(vbs_handle* h, Workspace& w, int nb, hipStream_t s);  // false: geometry outside the fused path
+bool launch_stage_lat(vbs_handle* h, Workspace& w, int nb, hipStream_t s);   // k_stage_lat.hip; false: not for this pass
 
 // a9-a12: band / opened planes, labelling, per-component sums.  The fused kernel (k_stage.hip) takes the pass; k_morph and
 // the general kernel then run over the frames it handed on (none on marker frames: their waves / workgroups find no
 // flagged frame and exit).  Geometries outside the fused path - and VBS_OPT_STAGE_IMPL = 1 - take the round-2 kernels:
 // k_morph over every frame, k_ccl<0|1>, the general kernel over what those hand on.
-void launch_labelling(vbs_handle* h, int nb, hipStream_t s) {
+void launch_labelling(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
     // a pass of a few frames (MarkerTracker.process: ONE) spreads each frame over several workgroups: k_stage_lat.hip
     const bool fused = h->stage_impl == 0 || h->stage_impl >= 3;
-    const bool lat = fused && nb <= h->lat_frames && nb <= h->lat_slots;
-    if (h->pass_cleared) h->pass_cleared = false;        // (detect_pass cleared them with the frame statistics: one launch less)
-    else if (lat) launch_fill(h->lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + nb + 4, s);     // its headers, the counter and the flags
-    else launch_fill(h->slow_total, 0u, (size_t)nb + 4, s);                       // the counter and the flags
+    const bool lat = fused && nb <= h->lat_frames && nb <= w.lat_slots;
+    if (w.pass_cleared) w.pass_cleared = false;          // (detect_pass cleared them with the frame statistics: one launch less)
+    else if (lat) launch_fill(w.lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + nb + 4, s);     // its headers, the counter and the flags
+    else launch_fill(w.slow_total, 0u, (size_t)nb + 4, s);                        // the counter and the flags
     int all = 0;
     const u32* nslow = nullptr;
-    if (lat && launch_stage_lat(h, nb, s)) {
+    if (lat && launch_stage_lat(h, w, nb, s)) {
         // what it hands on: planes and labels by ONE more kernel (k_label<ns> makes the planes itself); no frame on marker frames
         const int G = 64 / h->WW, wpf = std::max(1, std::min(64, h->H / (2 * h->bp.ns) / G));
         const int strips = wpf * G, rps = (h->H + strips - 1) / strips;
 #define LABEL_M(NS_)                                                                                                              \
-        VBS_LAUNCH(h, s, "k_label", k_label<NS_>, dim3(nb), dim3(1024), 0, s, h->band_bits, h->open_bits, h->wbase, h->node_pos,    \
-                   h->node_comp, h->ncomp, h->band_first, h->band_sums, h->area_first, h->area_sums, h->fstat, h->lut, h->slow_flag, \
-                   h->slow_total, h->probe, nb, 0, h->H, h->W, h->WW, h->maxm, 0, h->mask_bits, h->area_bits, G, strips, rps, wpf)
+        VBS_LAUNCH(h, s, "k_label", k_label<NS_>, dim3(nb), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase, w.node_pos,      \
+                   w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat, h->lut, w.slow_flag,      \
+                   w.slow_total, w.probe, nb, 0, h->H, h->W, h->WW, h->maxm, 0, w.mask_bits, w.area_bits, G, strips, rps, wpf)
         if (h->bp.ns == 14) LABEL_M(14); else LABEL_M(8);
 #undef LABEL_M
         return;
     }
-    if (fused && launch_stage(h, nb, s)) {
-        launch_morph(h, nb, h->slow_flag, s);
-        nslow = h->slow_total;
+    if (fused && launch_stage(h, w, nb, s)) {
+        launch_morph(h, w, nb, w.slow_flag, s);
+        nslow = w.slow_total;
     } else {
-        launch_morph(h, nb, nullptr, s);
-        all = (h->stage_impl != 2 && launch_ccl(h, nb, s)) ? 0 : 1;       // (2: the general kernel labels EVERY frame - its rate, tests)
+        launch_morph(h, w, nb, nullptr, s);
+        all = (h->stage_impl != 2 && launch_ccl(h, w, nb, s)) ? 0 : 1;      // (2: the general kernel labels EVERY frame - its rate, tests)
     }
-    VBS_LAUNCH(h, s, "k_label", k_label<0>, dim3(nb < 64 ? nb : 64), dim3(1024), 0, s, h->band_bits, h->open_bits, h->wbase,
-               h->node_pos, h->node_comp, h->ncomp, h->band_first, h->band_sums, h->area_first, h->area_sums, h->fstat,
-               h->lut, h->slow_flag, nslow, h->probe, nb, all, h->H, h->W, h->WW, h->maxm, VBS_KNOB("VBS_LABEL_STOP"),
+    VBS_LAUNCH(h, s, "k_label", k_label<0>, dim3(nb < 64 ? nb : 64), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase,
+               w.node_pos, w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat,
+               h->lut, w.slow_flag, nslow, w.probe, nb, all, h->H, h->W, h->WW, h->maxm, VBS_KNOB("VBS_LABEL_STOP"),
                (const u64*)nullptr, (const u64*)nullptr, 0, 0, 0, 0);
 }
 
@@ -1272,10 +1272,10 @@ __global__ __launch_bounds__(256) void k_finalize(const u32* __restrict__ ncomp_
                    H, W, WW, maxm, stop, force_seq);
 }
 
-void launch_finalize(vbs_handle* h, int nb, double* det, int32_t* counts, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_finalize", k_finalize, dim3(nb), dim3(256), 0, s, h->ncomp, h->band_sums, h->area_first,
-                       h->area_sums, h->probe, h->fstat, h->ell, h->det64,
-                       h->cnt, det, counts, h->H, h->W, h->WW, h->maxm, VBS_KNOB("VBS_FINAL_STOP"),
+void launch_finalize(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, hipStream_t s) {
+    VBS_LAUNCH(h, s, "k_finalize", k_finalize, dim3(nb), dim3(256), 0, s, w.ncomp, w.band_sums, w.area_first,
+                       w.area_sums, w.probe, w.fstat, w.ell, w.det64,
+                       w.cnt, det, counts, h->H, h->W, h->WW, h->maxm, VBS_KNOB("VBS_FINAL_STOP"),
                        h->force_seq_match ? 1 : 0);                 // (vbs_set_option: exercises the sequential replay)
 }
 
@@ -1300,11 +1300,11 @@ __global__ __launch_bounds__(256) void k_finalize_track(const u32* __restrict__ 
     track_frame(blockIdx.x, det64, cnt64, maxm, ref_xy, m_ref, min_dist, table, do3d, cam, min_size);
 }
 
-void launch_finalize_track(vbs_handle* h, int nb, double* det, int32_t* counts, const double* ref_xy, int m_ref, double min_dist,
-                           float* table, const vbs_camera* cam, double min_size, hipStream_t s) {
+void launch_finalize_track(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, const double* ref_xy, int m_ref,
+                           double min_dist, float* table, const vbs_camera* cam, double min_size, hipStream_t s) {
     CamD c{};
     if (cam) c = make_cam(*cam);
-    VBS_LAUNCH(h, s, "k_finalize_track", k_finalize_track, dim3(nb), dim3(256), 0, s, h->ncomp, h->band_sums, h->area_first,
-               h->area_sums, h->probe, h->fstat, h->ell, h->det64, h->cnt, det, counts, h->H, h->W, h->WW, h->maxm,
+    VBS_LAUNCH(h, s, "k_finalize_track", k_finalize_track, dim3(nb), dim3(256), 0, s, w.ncomp, w.band_sums, w.area_first,
+               w.area_sums, w.probe, w.fstat, w.ell, w.det64, w.cnt, det, counts, h->H, h->W, h->WW, h->maxm,
                h->force_seq_match ? 1 : 0, ref_xy, m_ref, min_dist, table, cam ? 1 : 0, c, min_size);
 }

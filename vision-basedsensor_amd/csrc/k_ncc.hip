@@ -979,15 +979,15 @@ __global__ __launch_bounds__(256) void k_stat_accum(const u32* __restrict__ fsta
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&tot[2], (u64)nb);
 }
 
-static void launch_stat_accum(vbs_handle* h, int nb, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_stat_accum", k_stat_accum, dim3(1), dim3(256), 0, s, h->fstat, h->ncc_tot, nb);
+static void launch_stat_accum(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
+    VBS_LAUNCH(h, s, "k_stat_accum", k_stat_accum, dim3(1), dim3(256), 0, s, w.fstat, w.ncc_tot, nb);
 }
 
-void launch_popcount(vbs_handle* h, int nb, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_popcount", k_popcount, dim3(nb), dim3(256), 0, s, h->area_bits, h->fstat, h->H * h->WW);
+void launch_popcount(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
+    VBS_LAUNCH(h, s, "k_popcount", k_popcount, dim3(nb), dim3(256), 0, s, w.area_bits, w.fstat, h->H * h->WW);
 }
 
-void launch_ncc(vbs_handle* h, int nb, u8* mask_u8, double* ncc_out, hipStream_t s) {
+void launch_ncc(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, double* ncc_out, hipStream_t s) {
     if (!ncc_out && !VBS_KNOB("VBS_NCC_VALU")) {
         const int tilesY = (h->H + 15) / 16;
         // few frames: split the columns - into as many segments as keep every workgroup resident at once (256 CUs x 4): a
@@ -999,8 +999,8 @@ void launch_ncc(vbs_handle* h, int nb, u8* mask_u8, double* ncc_out, hipStream_t
         nseg = (tilesY + tps - 1) / tps;
         dim3 grid(h->WW, nseg, nb);
 #define NCC_GO(L_, LO_, U8)                                                                                      \
-    VBS_LAUNCH(h, s, "k_ncc_mfma", (k_ncc_mfma<L_, LO_, U8>), grid, dim3(256), 0, s, h->area_bits, h->ncc_rx,    \
-               h->ncc_ry, h->ncc_frags, h->ncc_tab, h->ncc_rowf, h->mask_bits, mask_u8, h->fstat, h->ncc_tot,   \
+    VBS_LAUNCH(h, s, "k_ncc_mfma", (k_ncc_mfma<L_, LO_, U8>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx,     \
+               h->ncc_ry, h->ncc_frags, h->ncc_tab, h->ncc_rowf, w.mask_bits, mask_u8, w.fstat, w.ncc_tot,       \
                h->H, h->W, h->WW, tps,                                                                           \
                VBS_KNOB("VBS_NCC_DBG"), std::max(NCC_REL, 1e-6f * (float)h->ncc_margin_ppm), h->ncc)
         if (!h->bp.small) { if (mask_u8) NCC_GO(80, -40, true); else NCC_GO(80, -40, false); }
@@ -1011,11 +1011,11 @@ void launch_ncc(vbs_handle* h, int nb, u8* mask_u8, double* ncc_out, hipStream_t
     dim3 grid(h->WW, (h->H + 63) / 64, nb);
     const int stop = VBS_KNOB("VBS_NCC_STOP");
     if (!h->bp.small) {
-        VBS_LAUNCH(h, s, "k_ncc", (k_ncc<80, -40>), grid, dim3(256), 0, s, h->area_bits, h->ncc_rx, h->ncc_ry,
-                   h->mask_bits, mask_u8, ncc_out, h->fstat, h->H, h->W, h->WW, stop, h->ncc);
+        VBS_LAUNCH(h, s, "k_ncc", (k_ncc<80, -40>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx, h->ncc_ry,
+                   w.mask_bits, mask_u8, ncc_out, w.fstat, h->H, h->W, h->WW, stop, h->ncc);
     } else {
-        VBS_LAUNCH(h, s, "k_ncc", (k_ncc<33, -16>), grid, dim3(256), 0, s, h->area_bits, h->ncc_rx, h->ncc_ry,
-                   h->mask_bits, mask_u8, ncc_out, h->fstat, h->H, h->W, h->WW, stop, h->ncc);
+        VBS_LAUNCH(h, s, "k_ncc", (k_ncc<33, -16>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx, h->ncc_ry,
+                   w.mask_bits, mask_u8, ncc_out, w.fstat, h->H, h->W, h->WW, stop, h->ncc);
     }
-    launch_stat_accum(h, nb, s);                         // (k_ncc_mfma adds to the running totals itself)
+    launch_stat_accum(h, w, nb, s);                         // (k_ncc_mfma adds to the running totals itself)
 }

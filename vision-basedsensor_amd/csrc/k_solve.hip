@@ -231,12 +231,12 @@ void launch_track(vbs_handle* h, const double* det, const int32_t* counts32, int
                        ref_xy, m_ref, min_dist, table, 0, cam, 0.0);
 }
 
-void launch_track_fused(vbs_handle* h, int nb, const double* ref_xy, int m_ref, double min_dist,
+void launch_track_fused(vbs_handle* h, Workspace& w, int nb, const double* ref_xy, int m_ref, double min_dist,
                         float* table, const vbs_camera* cam, double min_size, hipStream_t s) {
     CamD c{};
     if (cam) c = make_cam(*cam);
-    VBS_LAUNCH(h, s, "k_track", k_track, dim3(nb), dim3(256), 0, s, (const double*)h->det64,
-                       (const int32_t*)h->cnt, h->maxm, ref_xy, m_ref, min_dist, table, cam ? 1 : 0, c, min_size);
+    VBS_LAUNCH(h, s, "k_track", k_track, dim3(nb), dim3(256), 0, s, (const double*)w.det64,
+                       (const int32_t*)w.cnt, h->maxm, ref_xy, m_ref, min_dist, table, cam ? 1 : 0, c, min_size);
 }
 
 void launch_solve3d(vbs_handle* h, float* table, int n, int m_ref, const vbs_camera& cam, double min_size,
@@ -255,9 +255,9 @@ void launch_fill(u32* p, u32 value, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, s, p, value, n);
 }
 
-void launch_displacement(vbs_handle* h, const float* table, int n, int m_ref, int warmup, double min_size,
+void launch_displacement(vbs_handle* h, Workspace& w, const float* table, int n, int m_ref, int warmup, double min_size,
                          double max_disp, int f0, int f1, float* disp, hipStream_t s) {
-    int* fmin = reinterpret_cast<int*>(h->fstat + (size_t)h->maxb * 8);      // one spare word behind the counters
+    int* fmin = reinterpret_cast<int*>(w.fstat + (size_t)h->maxb * 8);      // one spare word behind the counters
     launch_fill(reinterpret_cast<u32*>(fmin), 0x7f7f7f7fu, 1, s);             // "no frame"
     VBS_LAUNCH(h, s, "k_disp_first", k_disp_first<float>, dim3(n), dim3(256), 0, s, table, n, m_ref, min_size, fmin);
     dim3 grid((f1 - f0 + 31) / 32, (m_ref + 255) / 256);

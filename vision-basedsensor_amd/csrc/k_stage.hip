@@ -669,7 +669,7 @@ static int stage_threads(const vbs_handle* h, int nb) {
 }
 
 // false = geometry outside the fused path (the round-2 kernels take it)
-static bool stage_geom(const vbs_handle* h, StageGeom* g, size_t* lds_bytes, int nt) {
+static bool stage_geom(const vbs_handle* h, const Workspace& w, StageGeom* g, size_t* lds_bytes, int nt) {
     if (h->W > 4096 || h->H > 2048 || h->maxm > 1024) return false;
     const int G = 64 / h->WW, NB = (nt / 64) * G;        // (WW <= 64: vbs_create)
     const int R = (h->H + NB - 1) / NB;
@@ -701,20 +701,14 @@ static bool stage_geom(const vbs_handle* h, StageGeom* g, size_t* lds_bytes, int
     *lds_bytes = g->off_tmp + misc;
     // moment records live in the frame's slice of the general path's word table (idle on the fast path) - unless that
     // slice holds fewer than SG_REC of them: small frames with many blobs (the reference's real layout: 65 dots in 467x437,
-    // tiles of 5 rows, ~650 records against the 437 its slice holds) have their own buffer (vbs_create: stage_mrec)
-    g->mrec_stride = h->stage_mrec ? 16u * (u32)SG_REC : 2u * (u32)h->H * (u32)h->WW;
+    // tiles of 5 rows, ~650 records against the 437 its slice holds) have their own buffer (alloc_workspace: stage_mrec)
+    g->mrec_stride = w.stage_mrec ? 16u * (u32)SG_REC : 2u * (u32)h->H * (u32)h->WW;
     g->mrec_cap = g->mrec_stride / 16u < (u32)SG_REC ? g->mrec_stride / 16u : (u32)SG_REC;
     return *lds_bytes <= (size_t)(half ? 160 * 1024 / 3 - 256 : 160 * 1024);
 }
 
-bool stage_supported(const vbs_handle* h) {
-    StageGeom g;
-    size_t lds;
-    return stage_geom(h, &g, &lds, ST_NT);
-}
-
 template <int NS, int NT>
-static bool stage_launch_t(vbs_handle* h, int nb, const StageGeom& g, size_t lds, hipStream_t s) {
+static bool stage_launch_t(vbs_handle* h, Workspace& w, int nb, const StageGeom& g, size_t lds, hipStream_t s) {
     size_t& set = h->stage_lds_set[NT == ST_NT ? 0 : 1];     // (of the NS instances a handle runs only one)
     if (lds > set) {
         // (per thread count; of the NS instances a handle runs only one)
@@ -725,27 +719,27 @@ static bool stage_launch_t(vbs_handle* h, int nb, const StageGeom& g, size_t lds
         }
         set = lds;
     }
-    VBS_LAUNCH(h, s, g.retry ? "k_stage_retry" : "k_stage", (k_stage<NS, NT>), dim3(nb), dim3(NT), lds, s, h->mask_bits, h->area_bits, h->ncomp,
-               h->band_sums, h->area_first, h->area_sums, h->probe, h->fstat, h->slow_flag, h->slow_total,
-               h->stage_mrec ? h->stage_mrec : h->wbase, g);
+    VBS_LAUNCH(h, s, g.retry ? "k_stage_retry" : "k_stage", (k_stage<NS, NT>), dim3(nb), dim3(NT), lds, s, w.mask_bits, w.area_bits, w.ncomp,
+               w.band_sums, w.area_first, w.area_sums, w.probe, w.fstat, w.slow_flag, w.slow_total,
+               w.stage_mrec ? w.stage_mrec : w.wbase, g);
     return true;
 }
 
 // false: geometry outside the fused path (or the LDS it needs was refused): the caller runs the round-2 kernels
-bool launch_stage(vbs_handle* h, int nb, hipStream_t s) {
+bool launch_stage(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
     StageGeom g;
     size_t lds = 0;
-    if (stage_threads(h, nb) < ST_NT && stage_geom(h, &g, &lds, ST_NT_SMALL) &&
-        (h->bp.ns == 14 ? stage_launch_t<14, ST_NT_SMALL>(h, nb, g, lds, s) : stage_launch_t<8, ST_NT_SMALL>(h, nb, g, lds, s))) {
+    if (stage_threads(h, nb) < ST_NT && stage_geom(h, w, &g, &lds, ST_NT_SMALL) &&
+        (h->bp.ns == 14 ? stage_launch_t<14, ST_NT_SMALL>(h, w, nb, g, lds, s) : stage_launch_t<8, ST_NT_SMALL>(h, w, nb, g, lds, s))) {
         // Its taller tiles and smaller tables give out earlier on dense layouts (17 x 17 dots at a pitch of 56 px in 1280x1024:
         // every frame); those frames get a second chance on 768 threads before the general kernels (11.1 -> 4.7 us per frame
         // there; a launch of workgroups that leave at once otherwise).
-        if (stage_geom(h, &g, &lds, ST_NT)) {
+        if (stage_geom(h, w, &g, &lds, ST_NT)) {
             g.retry = 1;
-            (void)(h->bp.ns == 14 ? stage_launch_t<14, ST_NT>(h, nb, g, lds, s) : stage_launch_t<8, ST_NT>(h, nb, g, lds, s));
+            (void)(h->bp.ns == 14 ? stage_launch_t<14, ST_NT>(h, w, nb, g, lds, s) : stage_launch_t<8, ST_NT>(h, w, nb, g, lds, s));
         }
         return true;
     }
-    if (!stage_geom(h, &g, &lds, ST_NT)) return false;
-    return h->bp.ns == 14 ? stage_launch_t<14, ST_NT>(h, nb, g, lds, s) : stage_launch_t<8, ST_NT>(h, nb, g, lds, s);
+    if (!stage_geom(h, w, &g, &lds, ST_NT)) return false;
+    return h->bp.ns == 14 ? stage_launch_t<14, ST_NT>(h, w, nb, g, lds, s) : stage_launch_t<8, ST_NT>(h, w, nb, g, lds, s);
 }

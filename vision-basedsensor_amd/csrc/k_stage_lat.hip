@@ -970,7 +970,7 @@ static bool lat_geom(const vbs_handle* h, LatGeom* g, size_t* lds_bytes) {
     return *lds_bytes <= 160 * 1024;
 }
 
-// bytes of per-frame scratch this geometry needs (vbs_create allocates VBS_LAT_MAXN of them); 0 = outside the path
+// bytes of per-frame scratch this geometry needs (alloc_workspace allocates VBS_LAT_MAXN of them); 0 = outside the path
 size_t stage_lat_scratch(const vbs_handle* h) {
     LatGeom g;
     size_t lds;
@@ -978,7 +978,7 @@ size_t stage_lat_scratch(const vbs_handle* h) {
 }
 
 template <int NS>
-static bool stage_lat_launch_t(vbs_handle* h, int nb, const LatGeom& g, size_t lds, hipStream_t s) {
+static bool stage_lat_launch_t(vbs_handle* h, Workspace& w, int nb, const LatGeom& g, size_t lds, hipStream_t s) {
     if (lds > h->lat_lds_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_stage_lat<NS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess) {
@@ -987,17 +987,17 @@ static bool stage_lat_launch_t(vbs_handle* h, int nb, const LatGeom& g, size_t l
         }
         h->lat_lds_set = lds;
     }
-    VBS_LAUNCH(h, s, "k_stage_lat", (k_stage_lat<NS>), dim3(2 * g.C, nb), dim3(LT_NT), lds, s, h->mask_bits, h->area_bits, h->ncomp,
-               h->band_sums, h->area_first, h->area_sums, h->probe, h->fstat, h->slow_flag, h->slow_total, h->lat_hdr,
-               h->lat_scratch, g);
+    VBS_LAUNCH(h, s, "k_stage_lat", (k_stage_lat<NS>), dim3(2 * g.C, nb), dim3(LT_NT), lds, s, w.mask_bits, w.area_bits, w.ncomp,
+               w.band_sums, w.area_first, w.area_sums, w.probe, w.fstat, w.slow_flag, w.slow_total, w.lat_hdr,
+               w.lat_scratch, g);
     return true;
 }
 
-// The few-frames form of launch_stage.  The caller has cleared the frames' headers (h->lat_hdr) on `s`.
+// The few-frames form of launch_stage.  The caller has cleared the frames' headers (w.lat_hdr) on `s`.
 // false: not for this pass (more than VBS_LAT_MAXN frames, geometry outside the path, no scratch)
-bool launch_stage_lat(vbs_handle* h, int nb, hipStream_t s) {
+bool launch_stage_lat(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
     LatGeom g;
     size_t lds = 0;
-    if (nb > h->lat_slots || !h->lat_scratch || !lat_geom(h, &g, &lds)) return false;
-    return h->bp.ns == 14 ? stage_lat_launch_t<14>(h, nb, g, lds, s) : stage_lat_launch_t<8>(h, nb, g, lds, s);
+    if (nb > w.lat_slots || !w.lat_scratch || !lat_geom(h, &g, &lds)) return false;
+    return h->bp.ns == 14 ? stage_lat_launch_t<14>(h, w, nb, g, lds, s) : stage_lat_launch_t<8>(h, w, nb, g, lds, s);
 }

@@ -7,7 +7,7 @@
 #define SG_KB 4                    // slots of the band walk (a ring crosses a tile as two arcs)
 #define SG_KO 3                    // slots of the opened-mask walk
 #define SG_SEGMAX 8                // segments a thread can start; segment id = 8 tid + i
-// (SG_REC, the segment records per frame: common.h - vbs_create sizes a buffer by it)
+// (SG_REC, the segment records per frame: common.h - alloc_workspace sizes a buffer by it)
 #define SG_PQ 4096                 // segment pairs waiting to be united, at most (StageGeom::pq_cap)
 #define NONE32 0xFFFFFFFFu
 // why a frame was handed on (slow_flag value)
