@@ -228,7 +228,8 @@ int vbs_profile_read(vbs_handle* h, char* buf, int cap);
  * 1: NCC pixels within 1e-9 (relative) of the 0.1 threshold, 2: status, 3: NCC pixels re-evaluated in float64,
  * 4: holes LEFT in the opened area mask (components - Euler number; holes are filled before contouring, like
  * cv2.findContours(RETR_EXTERNAL) ignores them, so this is 0 unless the fill pass ran out of capacity), 5 / 6: connected
- * components of the band / opened mask, 7: holes that were filled}] (synchronises). */
+ * components of the band / opened mask (the opened mask once its holes are filled: its external contours), 7: holes that were
+ * filled}] (synchronises). */
 int vbs_frame_stats(vbs_handle* h, uint32_t* out, int n);
 /* Diagnostic / parity entry: host copies of the per-component tables the labelling kernels left for the first n frames of
  * the LAST internal pass (synchronises; any pointer may be NULL): ncomp [n][2] components of the band / opened mask,

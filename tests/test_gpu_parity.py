@@ -13,6 +13,7 @@ Stated tolerances (north_star: IDs bit-exact, centroids / 3-D within an fp32 tol
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -26,7 +27,10 @@ from vbs_amd import _lib as L                                 # noqa: E402
 from vbs_amd import ids as I                                  # noqa: E402
 from oracle import stages as O                                # noqa: E402
 
-TOL_XY, TOL_AX, TOL_XYZ = 2.5e-4, 1e-3, 2e-5
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "helpers"))
+from markers import TOL_AX, angle_close, compare_markers      # noqa: E402,F401
+
+TOL_XY, TOL_XYZ = 2.5e-4, 2e-5
 
 
 def engine(h, w, **kw):
@@ -40,21 +44,6 @@ def rle_decode(runs, shape):
     vals = np.zeros(len(runs), dtype=np.uint8)
     vals[1::2] = 1
     return np.repeat(vals, runs).reshape(shape)
-
-
-def angle_close(a, b, tol=0.05):
-    d = abs((a - b + 90.0) % 180.0 - 90.0)
-    return d <= tol
-
-
-def compare_markers(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        assert g["center"][0] == w["center"][0] and g["center"][1] == w["center"][1]      # bit-exact
-        assert abs(g["major_axis"] - w["major_axis"]) <= TOL_AX
-        assert abs(g["minor_axis"] - w["minor_axis"]) <= TOL_AX
-        if w["major_axis"] - w["minor_axis"] > 1e-2:
-            assert angle_close(g["angle"], w["angle"]), (g, w)
 
 
 # ------------------------------------------------------------------------------------------------
