@@ -14,7 +14,8 @@
  *    exceptions that happen ONCE per handle and never under stream capture: the gray plane of 3-channel / undistorted
  *    input (first such call, or vbs_set_undistort), and the second pass workspace of a handle left at the default
  *    VBS_OPT_PASS_STREAMS (first call spanning several internal passes; vbs_set_option(h, VBS_OPT_PASS_STREAMS, 2)
- *    builds it ahead of time - do that before capturing calls into a graph);
+ *    builds it ahead of time - do that before capturing calls into a graph).  The time-axis reductions size their
+ *    scratch by the call instead (vbs_series_stats, vbs_window_means: built at the first call, grown only by a larger one);
  *  - calls are asynchronous on `stream` (a hipStream_t passed as void*, NULL = default stream);
  *    the caller synchronises before reading results;
  *  - return value: VBS_OK or a negative status; `vbs_last_error` gives the text.  Per-frame
@@ -319,6 +320,55 @@ int vbs_plane_fit(vbs_handle* h, const float* table, int n, int m_ref, float* pl
 int vbs_deviation_plane(vbs_handle* h, const float* vert_start, const float* vert_end, const float* tilt_start,
                         const float* tilt_end, const float* ref_xyz, int m_ref, int shell_mode, double scale,
                         float* deviation, float* out, void* stream);
+
+/* ---- The time axis: per-marker statistics of a tracked sequence, on the device ----------------------------------------
+ * What the reference computes from its result sheet with pandas, along time and per marker, from the two dense tensors a
+ * sequence ends as.  Float64 accumulation, no atomics: two calls on the same input give the same bits.  Frames are cut into
+ * chunks of VBS_SERIES_CHUNK, ALIGNED TO GLOBAL FRAME 0 (frame_begin = the global number of the first frame passed, as
+ * vbs_displacement_range's), one thread per (chunk, slot); a slot's chunks are then merged in frame order (Chan, Golub &
+ * LeVeque's pairwise update of mean and M2), so nothing is serial in the number of frames.
+ *
+ * vbs_series_stats - MarkerAnalysis.analyze_displacement (3d_reconstruction.py:332-334 cumulative series, :397-400 the
+ * statistics of displacement_statistics.csv): disp [dev] float32 [n,m_ref,VBS_DISP_COLS] as vbs_displacement writes it (col 0
+ * says which entries are rows of the reference's DataFrame, col 4 is its `displacement`) -> stats [dev] float64
+ * [m_ref,VBS_STATS_COLS] = count, mean, std (ddof = 1), max, total (= the last cumulative value).  count 0: the other four
+ * are NaN (the groupby has no such group); count 1: std is NaN (as pandas).  cumulative (may be NULL) [dev] float64 [n,m_ref]:
+ * the inclusive running sum per slot; where the flag is 0 the value of the frame before is carried (0 before the first row).
+ * Cost: three launches (four with cumulative) and a scratch of vbs_series_chunks * m_ref * (VBS_SERIES_REC_COLS + 1) doubles
+ * inside the handle - ALLOCATED AT THE FIRST CALL, sized by that call's n and m_ref (a gathered table is longer than a pass,
+ * so max_batch says nothing about it), kept, and grown only when a larger call arrives (hipFree + hipMalloc: synchronises
+ * the device; VBS_ENOMEM under stream capture).  A repeated call of the same or a smaller shape allocates nothing.
+ * vbs_window_means shares that scratch (n_windows * ceil(longest window / VBS_SERIES_CHUNK) * m_ref * 4 doubles).
+ * vbs_series_stats_f64: the same on a float64 disp (as vbs_displacement_f64 writes it), no handle; scratch [dev] = that many
+ * doubles, provided by the caller.
+ * vbs_series_partial / vbs_series_merge: the two halves, for a sequence whose disp is spread over ranks.  partial: records
+ * [dev] float64 [vbs_series_chunks,m_ref,VBS_SERIES_REC_COLS] = count, mean, M2, max, sum of every chunk the frames
+ * [frame_begin, frame_begin + n) touch (a chunk cut by the call's first or last frame gives a record of its part).  merge:
+ * n_records records IN FRAME ORDER (any mix of whole and cut chunks; records of count 0 are skipped, so padding changes no
+ * bit) -> stats as above, and prefix (may be NULL) [dev] float64 [n_records,m_ref] = the sum of the records before each.
+ * vbs_series_chunks (host only): the number of records of such a call; VBS_EINVAL for n < 1 or frame_begin < 0. */
+#define VBS_SERIES_CHUNK    32
+#define VBS_SERIES_REC_COLS 5   /* count, mean, M2 (sum of squared deviations), max, sum */
+#define VBS_STATS_COLS      5   /* count, mean, std (ddof = 1), max, total               */
+#define VBS_WINDOW_COLS     4   /* count, mean X, mean Y, mean Z                         */
+int vbs_series_chunks(int n, int frame_begin);
+int vbs_series_stats(vbs_handle* h, const float* disp, int n, int m_ref, int frame_begin, double* stats, double* cumulative,
+                     void* stream);
+int vbs_series_stats_f64(int device, const double* disp, int n, int m_ref, int frame_begin, double* stats, double* cumulative,
+                         double* scratch, void* stream);
+int vbs_series_partial(vbs_handle* h, const float* disp, int n, int m_ref, int frame_begin, double* records, void* stream);
+int vbs_series_merge(vbs_handle* h, const double* records, int n_records, int m_ref, double* stats, double* prefix,
+                     void* stream);
+/* calculate_average_coordinates (LocalAnalysis.py:53-60): for each of n_windows frame windows [a, b] - INCLUSIVE indices into
+ * the table's frames, windows = HOST int32 [n_windows][2] - per slot the number of rows with VBS_FLAG_XYZ and the float64 mean
+ * of their X, Y, Z (cols 6-8): means [dev] float64 [n_windows,m_ref,VBS_WINDOW_COLS]; NaN means at count 0 (the reference's
+ * groupby has no such marker, its inner merge :81 drops it).  A window outside [0, n) or with a > b: VBS_EINVAL. */
+int vbs_window_means(vbs_handle* h, const float* table, int n, int m_ref, const int32_t* windows, int n_windows, double* means,
+                     void* stream);
+/* MarkerDisplacement.py:158-173 (SCALAR mode: the distance of a marker from its own position in frame 0) for every slot and
+ * frame at once: out [dev] float64 [n,m_ref,2] = (flag, sqrt(dX^2 + dY^2 + dZ^2) against the slot's row in frame ref_frame);
+ * flag = 1 where both rows carry VBS_FLAG_XYZ, else (0, 0).  ref_frame outside [0, n): VBS_EINVAL. */
+int vbs_displacement_from_frame(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, double* out, void* stream);
 
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the

@@ -9,6 +9,7 @@ VBS_OK, VBS_EINVAL, VBS_ECAPACITY, VBS_EHIP, VBS_ENOMEM, VBS_EINTERNAL = 0, -1, 
 DET_COLS, TABLE_COLS, DISP_COLS, PLANE_COLS, DEVPLANE_COLS = 6, 10, 5, 5, 9
 FLAG_TRACKED, FLAG_XYZ = 1, 2
 JPEG_BLOCK_BITS_MAX, JPEG_HEADER_BYTES = 1660, 623
+SERIES_CHUNK, SERIES_REC_COLS, STATS_COLS, WINDOW_COLS = 32, 5, 5, 4
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -18,7 +19,9 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_track", "vbs_solve3d", "vbs_track_to_3d", "vbs_displacement", "vbs_displacement_range", "vbs_displacement_f64",
            "vbs_plane_fit", "vbs_assign_ids", "vbs_set_option", "vbs_bgr2gray", "vbs_ncc_counters", "vbs_normxcorr2_general",
            "vbs_stage_tables", "vbs_deviation_plane", "vbs_format_csv", "vbs_mjpeg_probe", "vbs_mjpeg_entropy_batch",
-           "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking")
+           "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking",
+           "vbs_series_chunks", "vbs_series_stats", "vbs_series_stats_f64", "vbs_series_partial", "vbs_series_merge",
+           "vbs_window_means", "vbs_displacement_from_frame")
 
 
 class Camera(C.Structure):
@@ -103,6 +106,13 @@ def lib():
         "vbs_jpeg_encode_workspace": (i32, [i32, i32, i32, vp, vp, vp]),
         "vbs_jpeg_encode": (i32, [vp, i32, i32, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, vp]),
         "vbs_draw_tracking": (i32, [vp, i32, i32, i32, i64, i64, vp, i32, vp, vp, i32, vp, vp, vp]),
+        "vbs_series_chunks": (i32, [i32, i32]),
+        "vbs_series_stats": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "vbs_series_stats_f64": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "vbs_series_partial": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "vbs_series_merge": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        "vbs_window_means": (i32, [vp, vp, i32, i32, vp, i32, vp, vp]),
+        "vbs_displacement_from_frame": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

@@ -107,6 +107,7 @@ extern "C" int vbs_destroy(vbs_handle* h) {
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (void* p : h->allocs) (void)hipFree(p);
+    if (h->series_ws) (void)hipFree(h->series_ws);
     delete h;
     return VBS_OK;
 }
@@ -733,6 +734,120 @@ extern "C" int vbs_deviation_plane(vbs_handle* h, const float* vert_start, const
     HIPCHK(h, hipSetDevice(h->device));
     launch_deviation_plane(h, vert_start, vert_end, tilt_start, tilt_end, ref_xyz, m_ref, shell_mode, scale, deviation, out,
                            (hipStream_t)stream);
+    return check_launch(h);
+}
+
+// ---- the time axis (k_series.hip) ---------------------------------------------------------------------------------------
+// The handle's scratch for these calls, `need` doubles: built at the first call, kept, grown only by a larger call (never
+// under stream capture: hipFree / hipMalloc synchronise).
+static int series_scratch(vbs_handle* h, size_t need, hipStream_t s) {
+    if (need <= h->series_cap) return VBS_OK;
+    if (capturing(s)) {
+        h->err = "the scratch of the time-axis reductions has to grow, which cannot happen under stream capture: call once "
+                 "with this shape before capturing";
+        return VBS_ENOMEM;
+    }
+    if (h->series_ws) { HIPCHK(h, hipFree(h->series_ws)); h->series_ws = nullptr; h->series_cap = 0; }
+    void* q = nullptr;
+    if (hipMalloc(&q, need * sizeof(double)) != hipSuccess) {
+        h->err = "hipMalloc failed (" + std::to_string(need * sizeof(double)) + " bytes)";
+        return VBS_ENOMEM;
+    }
+    h->series_ws = (double*)q;
+    h->series_cap = need;
+    return VBS_OK;
+}
+
+// n frames from frame_begin on, m_ref slots: within what the kernels index (int frame numbers, 16-bit grid y of 64-slot tiles)
+static bool series_shape_ok(int n, int m_ref, int frame_begin) {
+    return n >= 1 && m_ref >= 1 && m_ref <= 65535 * 64 && frame_begin >= 0 && (int64_t)frame_begin + n <= 0x7fffffff;
+}
+
+extern "C" int vbs_series_chunks(int n, int frame_begin) {
+    if (n < 1 || frame_begin < 0 || (int64_t)frame_begin + n > 0x7fffffff) return VBS_EINVAL;
+    return series_chunks(n, frame_begin);
+}
+
+extern "C" int vbs_series_partial(vbs_handle* h, const float* disp, int n, int m_ref, int frame_begin, double* records,
+                                  void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!disp || !records || !series_shape_ok(n, m_ref, frame_begin)) { h->err = "vbs_series_partial: bad argument"; return VBS_EINVAL; }
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_series_partial(h, disp, n, m_ref, frame_begin, records, (hipStream_t)stream);
+    return check_launch(h);
+}
+
+extern "C" int vbs_series_merge(vbs_handle* h, const double* records, int n_records, int m_ref, double* stats, double* prefix,
+                                void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!records || !stats || n_records < 1 || !series_shape_ok(1, m_ref, 0)) { h->err = "vbs_series_merge: bad argument"; return VBS_EINVAL; }
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_series_finalize(h, records, n_records, m_ref, stats, prefix, (hipStream_t)stream);
+    return check_launch(h);
+}
+
+extern "C" int vbs_series_stats(vbs_handle* h, const float* disp, int n, int m_ref, int frame_begin, double* stats,
+                                double* cumulative, void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!disp || !stats || !series_shape_ok(n, m_ref, frame_begin)) { h->err = "vbs_series_stats: bad argument"; return VBS_EINVAL; }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cells = (size_t)series_chunks(n, frame_begin) * m_ref;
+    int rc = series_scratch(h, cells * (VBS_SERIES_REC_COLS + 1), s);
+    if (rc != VBS_OK) return rc;
+    double *rec = h->series_ws, *prefix = rec + cells * VBS_SERIES_REC_COLS;
+    launch_series_partial(h, disp, n, m_ref, frame_begin, rec, s);
+    launch_series_finalize(h, rec, series_chunks(n, frame_begin), m_ref, stats, prefix, s);
+    if (cumulative) launch_series_cumsum(h, disp, n, m_ref, frame_begin, prefix, cumulative, s);
+    return check_launch(h);
+}
+
+extern "C" int vbs_series_stats_f64(int device, const double* disp, int n, int m_ref, int frame_begin, double* stats,
+                                    double* cumulative, double* scratch, void* stream) {
+    if (!disp || !stats || !scratch || !series_shape_ok(n, m_ref, frame_begin)) return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cells = (size_t)series_chunks(n, frame_begin) * m_ref;
+    double *rec = scratch, *prefix = rec + cells * VBS_SERIES_REC_COLS;
+    launch_series_partial64(disp, n, m_ref, frame_begin, rec, s);
+    launch_series_finalize(nullptr, rec, series_chunks(n, frame_begin), m_ref, stats, prefix, s);
+    if (cumulative) launch_series_cumsum64(disp, n, m_ref, frame_begin, prefix, cumulative, s);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_window_means(vbs_handle* h, const float* table, int n, int m_ref, const int32_t* windows, int n_windows,
+                                double* means, void* stream) {
+    if (!h) return VBS_EINVAL;
+    bool ok = table && windows && means && n_windows >= 1 && series_shape_ok(n, m_ref, 0);
+    int longest = 1;
+    for (int i = 0; ok && i < n_windows; ++i) {
+        const int a = windows[2 * i], b = windows[2 * i + 1];
+        ok = a >= 0 && b < n && a <= b;
+        if (ok) longest = std::max(longest, b - a + 1);
+    }
+    const int pieces = (longest + VBS_SERIES_CHUNK - 1) / VBS_SERIES_CHUNK;
+    if (!ok || pieces > 65535) { h->err = "vbs_window_means: bad argument (windows are inclusive [a, b] inside [0, n), a <= b)"; return VBS_EINVAL; }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int group = std::min(n_windows, VBS_WINDOWS_PER_LAUNCH);
+    int rc = series_scratch(h, (size_t)group * pieces * m_ref * 4, s);
+    if (rc != VBS_OK) return rc;
+    for (int w0 = 0; w0 < n_windows; w0 += VBS_WINDOWS_PER_LAUNCH)        // (stream order keeps one group's scratch from the next)
+        launch_window_means(h, table, m_ref, windows + 2 * w0, std::min(VBS_WINDOWS_PER_LAUNCH, n_windows - w0), pieces,
+                            h->series_ws, means + (size_t)w0 * m_ref * VBS_WINDOW_COLS, s);
+    return check_launch(h);
+}
+
+extern "C" int vbs_displacement_from_frame(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, double* out,
+                                           void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!table || !out || !series_shape_ok(n, m_ref, 0) || ref_frame < 0 || ref_frame >= n ||
+        ((int64_t)n * m_ref + 255) / 256 > 0x7fffffff) {
+        h->err = "vbs_displacement_from_frame: bad argument";
+        return VBS_EINVAL;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_disp_from_frame(h, table, n, m_ref, ref_frame, out, (hipStream_t)stream);
     return check_launch(h);
 }
 

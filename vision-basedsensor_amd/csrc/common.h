@@ -17,6 +17,7 @@ typedef uint8_t u8;
 #define VBS_AREA_SUMS 16           // n, 14 moments up to order 4, spare
 #define VBS_LAT_MAXN 32            // passes of at most this many frames may take the few-frames labelling kernel (k_stage_lat.hip)
 #define VBS_LAT_HDR 128            // dwords of counters / flags per frame of that kernel
+#define VBS_WINDOWS_PER_LAUNCH 16  // k_window_partial takes its windows as kernel arguments; longer lists are launched in groups
 
 struct BranchParams {              // marker_detection.py:117-126,129,170
     int taps_a, taps_b;            // GaussianBlur sizes
@@ -123,7 +124,15 @@ struct vbs_handle {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<void*> allocs;
+    // ---- scratch of the time-axis reductions (k_series.hip): sized by the call, built at first use, only ever grown ----
+    double* series_ws = nullptr;
+    size_t series_cap = 0;                 // doubles
 };
+
+// global chunks of VBS_SERIES_CHUNK frames that frames [frame_begin, frame_begin + n) touch (n >= 1, frame_begin >= 0)
+static inline int series_chunks(int n, int frame_begin) {
+    return (int)(((int64_t)frame_begin + n - 1) / VBS_SERIES_CHUNK - frame_begin / VBS_SERIES_CHUNK + 1);
+}
 
 #define HIPCHK(h, call)                                                                   \
     do {                                                                                  \
@@ -191,6 +200,15 @@ int launch_ncc_general(const double* T, int th, int tw, const double* I, int h, 
                        double* stats, hipStream_t s);
 void launch_displacement64(const double* table, int n, int m_ref, int warmup, double min_size, double max_disp,
                            double* disp, int* fmin_scratch, hipStream_t s);
+void launch_series_partial(vbs_handle* h, const float* disp, int n, int m_ref, int frame_begin, double* rec, hipStream_t s);
+void launch_series_partial64(const double* disp, int n, int m_ref, int frame_begin, double* rec, hipStream_t s);
+void launch_series_finalize(vbs_handle* h, const double* rec, int n_rec, int m_ref, double* stats, double* prefix, hipStream_t s);   // h may be null
+void launch_series_cumsum(vbs_handle* h, const float* disp, int n, int m_ref, int frame_begin, const double* prefix, double* cum,
+                          hipStream_t s);
+void launch_series_cumsum64(const double* disp, int n, int m_ref, int frame_begin, const double* prefix, double* cum, hipStream_t s);
+void launch_window_means(vbs_handle* h, const float* table, int m_ref, const int32_t* windows, int nw, int pieces, double* part,
+                         double* means, hipStream_t s);
+void launch_disp_from_frame(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, double* out, hipStream_t s);
 int setup_undistort(vbs_handle* h, const double* K9, const double* dist, int ndist, hipStream_t s);
 void launch_remap(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n, int64_t stride_row,
                   u8* out, int to_gray, hipStream_t s);

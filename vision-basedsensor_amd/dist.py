@@ -72,6 +72,24 @@ def gather_tables(local: torch.Tensor, n_total: int) -> torch.Tensor:
     return torch.cat([out[r * nmax:r * nmax + (b - a)] for r, (a, b) in enumerate(per)], dim=0)
 
 
+def gather_records(local: torch.Tensor, k_max: int) -> torch.Tensor:
+    """All-gather per-rank record blocks [k_r, M, C] (k_r <= k_max, float64) into [world * k_max, M, C] in rank order, each
+    rank's block padded with zero records to k_max rows so that ONE collective is enough.  (A record of count 0 is skipped
+    by the ordered merge, so the padding changes no bit of the result.)"""
+    rank, ws = world()
+    pad = torch.zeros((k_max,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+    pad[:local.shape[0]] = local
+    if ws == 1:
+        return pad
+    if td.get_backend() == "gloo" and local.is_cuda:      # rehearsal backend: gloo gathers host tensors
+        out = torch.empty((ws * k_max,) + tuple(local.shape[1:]), dtype=local.dtype)
+        td.all_gather_into_tensor(out, pad.cpu().contiguous())
+        return out.to(local.device)
+    out = torch.empty((ws * k_max,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+    td.all_gather_into_tensor(out, pad.contiguous())
+    return out
+
+
 class TableGather:
     """All-gather of the per-frame tables issued PASS BY PASS, so that the exchange of one internal pass overlaps the
     kernels of the next one (RCCL runs on its own stream; `async_op=True` only orders it after the pass that produced

@@ -331,6 +331,86 @@ class Engine:
                                                      self._stream()), "vbs_deviation_plane")
         return dev, out
 
+    # ---- the time axis: per-marker statistics of a tracked sequence (k_series.hip) ---------------------------------
+    def _disp32(self, disp):
+        if disp.dtype != torch.float32 or disp.device != self.device or disp.dim() != 3 or disp.shape[2] != L.DISP_COLS:
+            raise ValueError(f"disp must be a float32 tensor [n, m, {L.DISP_COLS}] on the engine's device")
+        if disp.shape[0] < 1 or disp.shape[1] < 1:
+            raise ValueError("disp holds no frames (n <= 0) or no slots")
+        return disp.contiguous()
+
+    def _table32(self, table):
+        if table.dtype != torch.float32 or table.device != self.device or table.dim() != 3 or table.shape[2] != L.TABLE_COLS:
+            raise ValueError(f"table must be a float32 tensor [n, m, {L.TABLE_COLS}] on the engine's device")
+        if table.shape[0] < 1 or table.shape[1] < 1:
+            raise ValueError("table holds no frames (n <= 0) or no slots")
+        return table.contiguous()
+
+    def series_stats(self, disp, frame_begin=0, cumulative=False):
+        """`analyze_displacement`'s numbers (`3d_reconstruction.py:332-334, 397-400`) from disp [n,m,5]: float64 stats [m,5] =
+        count, mean, std (ddof 1), max, total per slot (NaN where pandas has none), and with `cumulative=True` also the running
+        sum [n,m] float64.  `frame_begin`: global number of disp's first frame (chunks are aligned to global frame 0)."""
+        disp = self._disp32(disp)
+        n, m = disp.shape[0], disp.shape[1]
+        stats = torch.empty((m, L.STATS_COLS), dtype=torch.float64, device=self.device)
+        cum = torch.empty((n, m), dtype=torch.float64, device=self.device) if cumulative else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_series_stats(self._h, _ptr(disp), n, m, int(frame_begin), _ptr(stats), _ptr(cum),
+                                                  self._stream()), "vbs_series_stats")
+        return (stats, cum) if cumulative else stats
+
+    def series_partial(self, disp, frame_begin=0):
+        """The per-chunk records [chunks, m, 5] (count, mean, M2, max, sum) of this block of frames (`vbs_series_partial`)."""
+        disp = self._disp32(disp)
+        n, m = disp.shape[0], disp.shape[1]
+        k = self.lib.vbs_series_chunks(n, int(frame_begin))
+        if k < 0:
+            raise ValueError(f"series_partial: frame_begin {frame_begin} / {n} frames out of range")
+        rec = torch.empty((k, m, L.SERIES_REC_COLS), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_series_partial(self._h, _ptr(disp), n, m, int(frame_begin), _ptr(rec), self._stream()),
+                        "vbs_series_partial")
+        return rec
+
+    def series_merge(self, records):
+        """Records [k, m, 5] in frame order -> stats [m, 5] (`vbs_series_merge`)."""
+        if records.dtype != torch.float64 or records.device != self.device or records.dim() != 3 \
+                or records.shape[2] != L.SERIES_REC_COLS or records.shape[0] < 1 or records.shape[1] < 1:
+            raise ValueError(f"records must be a float64 tensor [k >= 1, m, {L.SERIES_REC_COLS}] on the engine's device")
+        records = records.contiguous()
+        m = records.shape[1]
+        stats = torch.empty((m, L.STATS_COLS), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_series_merge(self._h, _ptr(records), records.shape[0], m, _ptr(stats), None,
+                                                  self._stream()), "vbs_series_merge")
+        return stats
+
+    def window_means(self, table, windows):
+        """`calculate_average_coordinates` (`LocalAnalysis.py:53-60`): for every inclusive frame window (a, b) of `windows`
+        the per-slot count and float64 mean X, Y, Z over the rows with a 3-D point -> [W, m, 4] (NaN means at count 0)."""
+        table = self._table32(table)
+        n, m = table.shape[0], table.shape[1]
+        w = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+        if w.shape[0] < 1 or (w < -2**31).any() or (w >= 2**31).any():
+            raise ValueError("windows must be a non-empty list of (first, last) frame indices")
+        w = w.astype(np.int32)
+        means = torch.empty((w.shape[0], m, L.WINDOW_COLS), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_window_means(self._h, _ptr(table), n, m, w.ctypes.data_as(C.c_void_p), w.shape[0],
+                                                  _ptr(means), self._stream()), "vbs_window_means")
+        return means
+
+    def displacement_from_frame(self, table, ref_frame=0):
+        """`MarkerDisplacement.py:158-173` for every slot: [n, m, 2] float64 = (flag, distance from the slot's position in frame
+        `ref_frame`); flag 1 where both rows hold a 3-D point."""
+        table = self._table32(table)
+        n, m = table.shape[0], table.shape[1]
+        out = torch.empty((n, m, 2), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_displacement_from_frame(self._h, _ptr(table), n, m, int(ref_frame), _ptr(out),
+                                                             self._stream()), "vbs_displacement_from_frame")
+        return out
+
     # ---- a14 / f4 ------------------------------------------------------------------------------
     def assign_ids(self, det, counts, num_layers=5, id_mode="as_written"):
         """Frame-0 identities on the device: (ids int32 [M,2], ref_xy float64 [M,2]) as device tensors, in the
@@ -434,3 +514,29 @@ def displacement_f64(table64, warmup_frames=0, min_marker_size_px=0.0, max_displ
     if rc != L.VBS_OK:
         raise L.VbsError(f"vbs_displacement_f64 failed ({rc})")
     return disp
+
+
+def series_stats_f64(disp64, frame_begin=0, cumulative=False, device=None):
+    """float64 disp [n,m,5] (host or device, as `displacement_f64` returns it) -> stats float64 [m,5] (and the running sum
+    [n,m]) on the GPU (`vbs_series_stats_f64`)."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    d = torch.as_tensor(disp64, dtype=torch.float64, device=dev).contiguous()
+    if d.dim() != 3 or d.shape[2] != L.DISP_COLS or d.shape[0] < 1 or d.shape[1] < 1:
+        raise ValueError(f"disp must be [n >= 1, m >= 1, {L.DISP_COLS}]")
+    n, m = d.shape[0], d.shape[1]
+    k = L.lib().vbs_series_chunks(n, int(frame_begin))
+    if k < 0:
+        raise ValueError(f"series_stats_f64: frame_begin {frame_begin} / {n} frames out of range")
+    scratch = torch.empty((k * m * (L.SERIES_REC_COLS + 1),), dtype=torch.float64, device=dev)
+    stats = torch.empty((m, L.STATS_COLS), dtype=torch.float64, device=dev)
+    cum = torch.empty((n, m), dtype=torch.float64, device=dev) if cumulative else None
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_series_stats_f64(dev.index, _ptr(d), n, m, int(frame_begin), _ptr(stats), _ptr(cum), _ptr(scratch),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_series_stats_f64: bad argument")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_series_stats_f64 failed ({rc})")
+    return (stats, cum) if cumulative else stats

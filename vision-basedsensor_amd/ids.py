@@ -113,3 +113,14 @@ def reference_arrays(table: Dict[Tuple[int, int], dict]):
     ids = np.array(list(table.keys()), dtype=np.int64).reshape(-1, 2)
     xy = np.array([[v["Ox"], v["Oy"]] for v in table.values()], dtype=np.float64).reshape(-1, 2)
     return ids, xy
+
+
+def marker_ids(ids) -> np.ndarray:
+    """The integer `marker_id` of every (layer, idx) slot - the key the reference's L4 scripts read (`LocalAnalysis.py:47,58`,
+    `MarkerDisplacement.py:80,135`) and its figure prints: 1 + the rank of (layer, idx) in lexicographic order.  On the
+    1 + 6 + 12 + 18 + 24 + 4 layout that is 1 + [0, 1, 7, 19, 37, 61][layer] + idx."""
+    a = np.asarray(ids, dtype=np.int64).reshape(-1, 2)
+    order = np.lexsort((a[:, 1], a[:, 0]))
+    out = np.empty(len(a), dtype=np.int64)
+    out[order] = np.arange(1, len(a) + 1)
+    return out

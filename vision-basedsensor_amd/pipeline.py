@@ -143,3 +143,62 @@ def deviation_pose(eng: Engine, table_vert: torch.Tensor, table_tilt: torch.Tens
     o = out.cpu().numpy().astype(np.float64)
     return {"deviation": dev, "n": int(o[0]), "a": o[1], "b": o[2], "c": o[3], "tilt_deg": o[4],
             "mean_vector": o[5:8].copy(), "mean_magnitude": o[8]}
+
+
+# ---- the time axis (k_series.hip): what the reference's analysis layer computes from its result sheet ------------------------
+def series_stats_shard(eng: Engine, res: TrackResult, n_total: int) -> torch.Tensor:
+    """`Engine.series_stats` of a sequence whose `disp` is spread over the ranks (`track_shard`): every rank reduces its own
+    frames to per-chunk records (chunks aligned to global frame 0, so `frame_begin = res.frame_begin`), ONE all-gather of
+    those records (padded to the largest per-rank count), then the same merge in frame order on every rank -> stats [M, 5],
+    bit-identical on all ranks.  A chunk cut by a shard edge arrives as two records, merged in frame order like any others."""
+    rank, ws = D.world()
+    m = int(res.table.shape[1])
+    spans = [D.shard_bounds(n_total, ws, r) for r in range(ws)]
+    a, b = spans[rank]
+    if (a, b) != (res.frame_begin, res.frame_end):
+        raise ValueError(f"res holds frames [{res.frame_begin}, {res.frame_end}), rank {rank} of {ws} owns [{a}, {b})")
+    k_max = max((eng.lib.vbs_series_chunks(rb - ra, ra) if rb > ra else 0) for ra, rb in spans)
+    if k_max < 1:
+        raise ValueError("series_stats_shard: no frames")
+    if b > a:
+        rec = eng.series_partial(res.disp, frame_begin=a)
+    else:                                               # a rank without frames still joins the collective
+        rec = torch.zeros((0, m, L.SERIES_REC_COLS), dtype=torch.float64, device=eng.device)
+    return eng.series_merge(D.gather_records(rec, k_max))
+
+
+def window_displacement(eng: Engine, table: torch.Tensor, start=(1, 30), end=(120, 150), slots=None):
+    """`LocalAnalysis.py`'s flow (:53-60, :77-94) on a table [N, M, 10]: the mean X, Y, Z of every slot over two inclusive
+    frame windows, the inner join of the slots seen in both (:81), their difference vector, its norm and the mean norm.
+    `slots` (indices) selects markers as TARGET_MARKERS does (:11, :47).  Returns a dict of device tensors: `slots` [K],
+    `start_xyz` / `end_xyz` [K,3], `d` [K,4] = dX, dY, dZ, |d|, and `mean` (0-d; NaN when no slot is common)."""
+    means = eng.window_means(table, [start, end])
+    common = (means[0, :, 0] > 0) & (means[1, :, 0] > 0)
+    if slots is not None:
+        pick = torch.zeros_like(common)
+        pick[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=common.device)] = True
+        common &= pick
+    idx = torch.nonzero(common).reshape(-1)
+    s_xyz, e_xyz = means[0, idx, 1:4], means[1, idx, 1:4]
+    d = e_xyz - s_xyz
+    mag = torch.sqrt((d * d).sum(dim=1))
+    return {"slots": idx, "start_xyz": s_xyz, "end_xyz": e_xyz, "d": torch.cat([d, mag[:, None]], dim=1), "mean": mag.mean()}
+
+
+def to_marker_frame(table, ids, frame_offset=0, path=None):
+    """The sheet the reference's L4 scripts read (`LocalAnalysis.py:47,58`, `MarkerDisplacement.py:72,80`): one row
+    `frameno, marker_id, Xw, Yw, Zw` per table entry with a 3-D point, frame-major; `marker_id` = `ids.marker_ids`.
+    `path`: also written as .xlsx (`xlsx_io.dataframe_to_xlsx`), so a recorded session can be fed to those scripts."""
+    import pandas as pd
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    mid = _ids.marker_ids(ids)
+    if t.ndim != 3 or t.shape[2] != L.TABLE_COLS or t.shape[1] != len(mid):
+        raise ValueError(f"table must be [N, {len(mid)}, {L.TABLE_COLS}] for these ids")
+    f, s = np.nonzero((t[..., 0].astype(np.int64) & L.FLAG_XYZ) != 0)
+    df = pd.DataFrame({"frameno": (f + int(frame_offset)).astype(np.int64), "marker_id": mid[s],
+                       "Xw": t[f, s, 6].astype(np.float64), "Yw": t[f, s, 7].astype(np.float64),
+                       "Zw": t[f, s, 8].astype(np.float64)})
+    if path is not None:
+        from .xlsx_io import dataframe_to_xlsx
+        dataframe_to_xlsx(df, path)
+    return df

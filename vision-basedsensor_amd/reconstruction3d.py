@@ -226,6 +226,36 @@ class MarkerAnalysis:
         stats.to_csv(stats_path)
         logger.info(f"Saved displacement statistics: {stats_path}")
 
+    def analyze_tables(self, disp, ids, cumulative=False, path=None, engine=None, frame_begin=0):
+        """The dense-table form of `analyze_displacement` (`:332-334, 397-400`): disp [n, M, 5] on the device (float32 as
+        `track_shard` returns it, reduced through `engine`; or float64 as `displacement_f64` does, no engine needed) and the
+        slots' ids [M, 2] -> the reference's statistics frame, indexed by (row, col) with the columns `displacement`
+        mean / std / max and `cumulative_displacement` last; slots without a displacement row are dropped, as the groupby
+        drops them.  The reductions along time run on the GPU (k_series.hip); nothing but [M, 5] numbers comes back.
+        `cumulative=True` also returns the running sum [n, M] (device tensor).  `path`: where to write the CSV (this
+        method never writes `displacement_statistics.csv` by itself)."""
+        import torch
+        from .engine import series_stats_f64
+        if disp.dtype == torch.float64:
+            got = series_stats_f64(disp, frame_begin, cumulative)
+        elif engine is None:
+            raise ValueError("analyze_tables: a float32 disp needs the engine that owns its device (engine=...)")
+        else:
+            got = engine.series_stats(disp, frame_begin, cumulative)
+        st = (got[0] if cumulative else got).cpu().numpy()
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1, 2)
+        if ids.shape[0] != st.shape[0]:
+            raise ValueError(f"{ids.shape[0]} ids for {st.shape[0]} slots")
+        keep = st[:, 0] > 0
+        cols = pd.MultiIndex.from_tuples([("displacement", "mean"), ("displacement", "std"), ("displacement", "max"),
+                                          ("cumulative_displacement", "last")])
+        index = pd.MultiIndex.from_arrays([ids[keep, 0], ids[keep, 1]], names=["row", "col"])
+        stats = pd.DataFrame(st[keep][:, [1, 2, 3, 4]], index=index, columns=cols).sort_index()
+        if path is not None:
+            stats.to_csv(path)
+            logger.info(f"Saved displacement statistics: {path}")
+        return (stats, got[1]) if cumulative else stats
+
     # ---- `:405-442` --------------------------------------------------------------------------------
     def run_analysis(self, input_csv: Path) -> None:
         try:
