@@ -131,6 +131,44 @@ int vbs_mjpeg_entropy_batch(const uint8_t* buf, const int64_t* offs, const int32
                             int threads);
 int vbs_mjpeg_reconstruct(const uint32_t* ent, const uint32_t* tab, const int64_t* frame_base, const uint16_t* qt, int n,
                           const int32_t* info, uint8_t* planes, uint8_t* out, int64_t out_frame, int64_t out_row, void* stream);
+/* The entropy decode ON THE DEVICE (opt-in: MjpegDeviceDecoder(entropy="device")): scans WITHOUT restart intervals, decoded
+ * as self-synchronising subsequences (Klein & Wiseman; Weissenberger & Schmidt 2021), one workgroup per frame.
+ * vbs_mjpeg_scan_batch (HOST, `threads` C++ threads, no Huffman decoding): frames buf + offs[i], sizes[i] of a mapping of
+ * buf_size bytes.  A chunk with offs[i] < 0, sizes[i] < 4, sizes[i] > INT32_MAX or offs[i] + sizes[i] > buf_size gets
+ * status[i] = VBS_EINVAL and not one byte of it is read; so does a frame whose header does not parse or whose geometry is not
+ * info's.  Per good frame: qt [n][3][64] as above, and the scan's bytes copied into `stage` WITH THE FF 00 STUFFING REMOVED AND
+ * THE COPY ENDING AT THE FIRST MARKER, starting at scan_off[i] (a multiple of VBS_MJPEG_SCAN_ALIGN; `stage` itself must be
+ * so aligned) and followed by at least VBS_MJPEG_SCAN_GUARD zero bytes (the device reads big-endian 32-bit words, two per
+ * symbol, at most 11 bytes beyond the last scan byte); scan_bits[i] = 8 * the de-stuffed length (0 for a frame that has a
+ * restart interval: the device reports it short and the caller decodes it on the host).  stage_cap must hold the sum over
+ * the good chunks of (sizes[i] + VBS_MJPEG_SCAN_GUARD rounded up to VBS_MJPEG_SCAN_ALIGN), else VBS_EINVAL is returned;
+ * thread t packs its frames from the offset the frames before its first could need at most and reports (first byte, bytes
+ * used) in regions[2 t], regions[2 t + 1] (2 * threads int64): only those spans need to reach the device.  The decode tables
+ * (9-bit look-ahead + canonical maxcode / valptr / mincode rows, by component; csrc/jpeg_huff_common.h) are built once per
+ * DISTINCT set of the batch: sets = room for n * VBS_MJPEG_HUFF_SET_BYTES, *n_sets of them are written, table_set[i] = the
+ * frame's.  Returns the number of frames that failed, or VBS_EINVAL.
+ * vbs_mjpeg_huffman_device: DEVICE copies of stage, scan_off, scan_bits, table_set, sets -> ent, tab, frame_base exactly as
+ * vbs_mjpeg_reconstruct reads them, every block dense: ent (n * info[6] / 2 words) is zero-filled and gets the int16
+ * coefficients in natural order, tab[i][b] = (32 b) << 7 | 127, frame_base[i] = i * info[6] / 2.  subseq_bits: 0 (default,
+ * VBS_MJPEG_SUBSEQ_BITS) or a multiple of 32 in [128, 65536].  status[i] (device, written by the frame's workgroup): VBS_OK;
+ * VBS_MJPEG_SHORT when the scan's bits end before the last block is complete (libjpeg and the host decoder pad such a scan
+ * with zero bits; the device does NOT reproduce that tail) or the scan is longer than VBS_MJPEG_DEVICE_BITS_MAX; VBS_EINVAL
+ * when the true decode chain meets an impossible step (no code of <= 16 bits, a run beyond coefficient 63, a DC category
+ * above 11) or table_set[i] is outside [0, n_sets).  A frame whose status is not VBS_OK has undefined ent contents: the
+ * caller decodes it with vbs_mjpeg_entropy_batch and uploads the result into the frame's span of ent and its row of tab.
+ * info[5] (restart interval) must be 0.  Asynchronous on `stream`; three launches (zero-fill, k_jpeg_huff, k_jpeg_dc). */
+#define VBS_MJPEG_SCAN_ALIGN      16
+#define VBS_MJPEG_SCAN_GUARD      16
+#define VBS_MJPEG_HUFF_SET_BYTES  8928
+#define VBS_MJPEG_SUBSEQ_BITS     1024
+#define VBS_MJPEG_DEVICE_BITS_MAX 2147418112
+#define VBS_MJPEG_SHORT           1   /* per-frame status of vbs_mjpeg_huffman_device, not an error of the call */
+int vbs_mjpeg_scan_batch(const uint8_t* buf, int64_t buf_size, const int64_t* offs, const int64_t* sizes, int n, const int32_t* info,
+                         uint8_t* stage, int64_t stage_cap, int64_t* scan_off, int64_t* scan_bits, int32_t* table_set, void* sets,
+                         int32_t* n_sets, int64_t* regions, uint16_t* qt, int32_t* status, int threads);
+int vbs_mjpeg_huffman_device(const uint8_t* stage, const int64_t* scan_off, const int64_t* scan_bits, const int32_t* table_set,
+                             const void* sets, int n_sets, int n, const int32_t* info, int subseq_bits, uint32_t* ent, uint32_t* tab,
+                             int64_t* frame_base, int32_t* status, void* stream);
 /* The annotated tracking video (`_tracked.avi`, marker_detection.py:69-76,453) as Motion-JPEG, encoded on the device.
  * vbs_jpeg_encode: n BGR frames [dev] uint8 (frame / row strides in bytes, 3 bytes per pixel; a crop view is fine) -> one
  * complete JFIF file per frame, equal byte for byte to Pillow's `Image.save(buf, "JPEG", quality=quality)` (libjpeg-turbo

@@ -9,6 +9,7 @@ VBS_OK, VBS_EINVAL, VBS_ECAPACITY, VBS_EHIP, VBS_ENOMEM, VBS_EINTERNAL = 0, -1, 
 DET_COLS, TABLE_COLS, DISP_COLS, PLANE_COLS, DEVPLANE_COLS = 6, 10, 5, 5, 9
 FLAG_TRACKED, FLAG_XYZ = 1, 2
 JPEG_BLOCK_BITS_MAX, JPEG_HEADER_BYTES = 1660, 623
+MJPEG_SCAN_ALIGN, MJPEG_SCAN_GUARD, MJPEG_HUFF_SET_BYTES, MJPEG_SUBSEQ_BITS, MJPEG_SHORT = 16, 16, 8928, 1024, 1
 SERIES_CHUNK, SERIES_REC_COLS, STATS_COLS, WINDOW_COLS = 32, 5, 5, 4
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
@@ -21,7 +22,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_stage_tables", "vbs_deviation_plane", "vbs_format_csv", "vbs_mjpeg_probe", "vbs_mjpeg_entropy_batch",
            "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking",
            "vbs_series_chunks", "vbs_series_stats", "vbs_series_stats_f64", "vbs_series_partial", "vbs_series_merge",
-           "vbs_window_means", "vbs_displacement_from_frame")
+           "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device")
 
 
 class Camera(C.Structure):
@@ -103,6 +104,8 @@ def lib():
         "vbs_mjpeg_probe": (i32, [vp, i64, vp]),
         "vbs_mjpeg_entropy_batch": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32]),
         "vbs_mjpeg_reconstruct": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i64, i64, vp]),
+        "vbs_mjpeg_scan_batch": (i32, [vp, i64, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32]),
+        "vbs_mjpeg_huffman_device": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
         "vbs_jpeg_encode_workspace": (i32, [i32, i32, i32, vp, vp, vp]),
         "vbs_jpeg_encode": (i32, [vp, i32, i32, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, vp]),
         "vbs_draw_tracking": (i32, [vp, i32, i32, i32, i64, i64, vp, i32, vp, vp, i32, vp, vp, vp]),

@@ -9,11 +9,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <thread>
 #include <vector>
 
 #include "../../include/vbs.h"
+#include "jpeg_huff_common.h"
+
+static_assert(sizeof(vbs_huff_set) == VBS_MJPEG_HUFF_SET_BYTES, "vbs.h states the size of one table set");
 
 namespace {
 
@@ -514,6 +518,51 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const unsigned char* __restr
     o[2] = (unsigned char)min(max(R, 0), 255);
 }
 
+// ---- the device entropy path: host half --------------------------------------------------------------------------------
+// what makes two frames' table sets the same: code lengths and symbols of the six tables by component
+struct SetKey {
+    uint8_t b[6][17 + 256];
+    bool operator==(const SetKey& o) const { return memcmp(b, o.b, sizeof b) == 0; }
+};
+
+void fill_table(const Huff& h, vbs_huff_table* t) {
+    for (int l = 0; l < 18; ++l) t->maxcode[l] = l >= 1 ? h.maxcode[l] : -1;
+    for (int l = 0; l < 17; ++l) { t->valptr[l] = l >= 1 ? h.valptr[l] : 0; t->mincode[l] = l >= 1 ? h.mincode[l] : 0; }
+    memcpy(t->look, h.look, sizeof t->look);
+    memcpy(t->vals, h.vals, sizeof t->vals);
+}
+
+void frame_tables(const Frame& f, SetKey* key, vbs_huff_set* set) {
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < f.ncomp ? c : 0;
+        const Huff& d = f.dc[f.td[cc]];
+        const Huff& a = f.ac[f.ta[cc]];
+        if (key) {
+            memcpy(key->b[c], d.bits, 17); memcpy(key->b[c] + 17, d.vals, 256);
+            memcpy(key->b[3 + c], a.bits, 17); memcpy(key->b[3 + c] + 17, a.vals, 256);
+        }
+        if (set) { fill_table(d, &set->dc[c]); fill_table(a, &set->ac[c]); }
+    }
+}
+
+// the scan's bytes with FF 00 -> FF, up to the first marker (what Bits::fill hands the host decoder before its zero padding)
+int64_t destuff(const uint8_t* p, const uint8_t* end, uint8_t* dst) {
+    uint8_t* o = dst;
+    while (p < end) {
+        const uint8_t* q = (const uint8_t*)memchr(p, 0xFF, (size_t)(end - p));
+        if (!q) q = end;
+        memcpy(o, p, (size_t)(q - p));
+        o += q - p;
+        p = q;
+        if (p == end) break;
+        if (p + 1 < end && p[1] == 0x00) { *o++ = 0xFF; p += 2; }
+        else break;                                      // a marker (or FF as the last byte)
+    }
+    return o - dst;
+}
+
+inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
 }  // namespace
 
 // info[8]: width, height, components, luma h, luma v, restart interval, coefficients per frame, planes bytes per frame
@@ -577,6 +626,185 @@ extern "C" int vbs_mjpeg_entropy_batch(const uint8_t* buf, const int64_t* offs, 
     for (int i = 0; i < n; ++i) bad += status[i] != VBS_OK;
     return bad;
 }
+
+// Host half of the device entropy path (include/vbs.h): per frame the header parse, the quantisation tables and the scan's bytes,
+// de-stuffed and cut at the first marker, into `stage`; the decode tables once per distinct set of the batch.  Thread t packs
+// its frames from the offset that the frames before its first one could need at most, and reports (first byte, bytes used) in
+// regions[2 t], regions[2 t + 1].  No Huffman decoding happens here.
+extern "C" int vbs_mjpeg_scan_batch(const uint8_t* buf, int64_t buf_size, const int64_t* offs, const int64_t* sizes, int n,
+                                    const int32_t* info, uint8_t* stage, int64_t stage_cap, int64_t* scan_off, int64_t* scan_bits,
+                                    int32_t* table_set, void* sets, int32_t* n_sets, int64_t* regions, uint16_t* qt, int32_t* status,
+                                    int threads) {
+    if (!buf || buf_size < 0 || !offs || !sizes || !info || !stage || !scan_off || !scan_bits || !table_set || !sets || !n_sets ||
+        !regions || !qt || !status || n < 0 || threads < 1 || ((uintptr_t)stage & (VBS_MJPEG_SCAN_ALIGN - 1)))
+        return VBS_EINVAL;
+    *n_sets = 0;
+    for (int t = 0; t < threads; ++t) regions[2 * t] = regions[2 * t + 1] = 0;
+    // a chunk outside the mapping is refused before anything of it is read
+    std::vector<int64_t> room((size_t)n + 1, 0);          // room[i]: staged bytes the frames before i need at most
+    for (int i = 0; i < n; ++i) {
+        const bool in = offs[i] >= 0 && sizes[i] >= 4 && sizes[i] <= INT32_MAX && offs[i] <= buf_size && sizes[i] <= buf_size - offs[i];
+        status[i] = in ? VBS_OK : VBS_EINVAL;
+        scan_off[i] = 0; scan_bits[i] = 0; table_set[i] = 0;
+        room[i + 1] = room[i] + (in ? align_up(sizes[i] + VBS_MJPEG_SCAN_GUARD, VBS_MJPEG_SCAN_ALIGN) : 0);
+    }
+    if (room[n] > stage_cap) return VBS_EINVAL;
+    const int nt = std::max(1, std::min(threads, n));
+    struct Local { std::vector<SetKey> keys; std::vector<vbs_huff_set> sets; };
+    std::vector<Local> local((size_t)nt);
+    std::vector<int> first((size_t)nt + 1, 0);
+    for (int t = 0; t <= nt; ++t) first[t] = (int)((int64_t)n * t / nt);
+    auto work = [&](int t) {
+        Local& L = local[t];
+        int64_t at = room[first[t]];
+        regions[2 * t] = at;
+        for (int i = first[t]; i < first[t + 1]; ++i) {
+            if (status[i] != VBS_OK) continue;
+            Frame f;
+            int rc = parse(buf + offs[i], sizes[i], &f);
+            if (rc == VBS_OK && (f.w != info[0] || f.h != info[1] || f.ncomp != info[2] || f.hs[0] != info[3] || f.vs[0] != info[4]))
+                rc = VBS_EINVAL;
+            status[i] = rc;
+            if (rc != VBS_OK) continue;
+            for (int c = 0; c < 3; ++c) memcpy(qt + ((int64_t)i * 3 + c) * 64, f.qt[f.tq[c < f.ncomp ? c : 0]], 128);
+            SetKey key;
+            frame_tables(f, &key, nullptr);
+            if (L.keys.empty() || !(L.keys.back() == key)) {
+                L.keys.push_back(key);
+                L.sets.emplace_back();
+                frame_tables(f, nullptr, &L.sets.back());
+            }
+            table_set[i] = (int32_t)L.keys.size() - 1;    // (the thread's own numbering: made the batch's below)
+            // (a frame with restart intervals inside a clip without: nothing staged, the device reports it short and the
+            //  caller's host decoder takes it)
+            const int64_t len = f.restart ? 0 : destuff(f.scan, f.end, stage + at);       // <= sizes[i]
+            memset(stage + at + len, 0, (size_t)(align_up(len + VBS_MJPEG_SCAN_GUARD, VBS_MJPEG_SCAN_ALIGN) - len));
+            scan_off[i] = at;
+            scan_bits[i] = 8 * len;
+            at += align_up(len + VBS_MJPEG_SCAN_GUARD, VBS_MJPEG_SCAN_ALIGN);
+        }
+        regions[2 * t + 1] = at - regions[2 * t];
+    };
+    if (nt <= 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t) th.emplace_back(work, t);
+        for (auto& x : th) x.join();
+    }
+    // the threads' sets -> the batch's distinct ones, in frame order
+    std::vector<SetKey> keys;
+    vbs_huff_set* out = (vbs_huff_set*)sets;
+    int bad = 0;
+    for (int t = 0; t < nt; ++t) {
+        std::vector<int32_t> global(local[t].keys.size());
+        for (size_t k = 0; k < local[t].keys.size(); ++k) {
+            size_t g = keys.size();
+            while (g > 0 && !(keys[g - 1] == local[t].keys[k])) --g;
+            if (g == 0) {
+                keys.push_back(local[t].keys[k]);
+                memcpy(out + keys.size() - 1, &local[t].sets[k], sizeof(vbs_huff_set));
+                g = keys.size();
+            }
+            global[k] = (int32_t)g - 1;
+        }
+        for (int i = first[t]; i < first[t + 1]; ++i)
+            if (status[i] == VBS_OK) table_set[i] = global[table_set[i]];
+    }
+    for (int i = 0; i < n; ++i) bad += status[i] != VBS_OK;
+    *n_sets = (int32_t)keys.size();
+    return bad;
+}
+
+#ifdef VBS_DEBUG_KNOBS
+// The five phases of k_jpeg_huff / k_jpeg_dc over ONE staged frame, with plain loops in place of threads and barriers and the
+// same decode step (jpeg_huff_common.h): debug library only, not declared in vbs.h - the product library has no CPU decoder.
+// scan: the frame's staged bytes (4-byte aligned, guard behind them); coef [info[6] / 64][64] int16, natural order, expanded.
+// counters[4]: chunks, rounds of phase 2 summed over the chunks, the most rounds one chunk took, the longest chain (the
+// subsequences a thread decoded before it retired, its own included).  Returns the frame's status.
+extern "C" int vbs_dbg_mjpeg_huffman_emulate(const uint8_t* scan, int64_t scan_bits64, const void* set, const int32_t* info,
+                                             int subseq_bits, int chunk_threads, int16_t* coef, int64_t* counters) {
+    if (!scan || !set || !info || !coef || !counters || scan_bits64 < 0 || subseq_bits < 32 || (subseq_bits & 31) ||
+        chunk_threads < 1 || chunk_threads > 256 || ((uintptr_t)scan & 3))
+        return VBS_EINVAL - 100;
+    vbs_huff_geom g;
+    vbs_huff_geom_init(g, info, ZIGZAG);
+    const vbs_huff_set& T = *(const vbs_huff_set*)set;
+    const uint32_t* words = (const uint32_t*)scan;
+    memset(coef, 0, (size_t)g.nblk * 128);
+    counters[0] = counters[1] = counters[2] = counters[3] = 0;
+    if (scan_bits64 > VBS_MJPEG_DEVICE_BITS_MAX) return VBS_EINVAL;
+    const uint32_t scan_bits = (uint32_t)scan_bits64, S = (uint32_t)subseq_bits;
+    const int64_t nsub = ((int64_t)scan_bits + S - 1) / S;
+    const int NT = chunk_threads;
+    std::vector<vbs_huff_state> s((size_t)NT + 1), run((size_t)NT);
+    std::vector<uint32_t> cnt((size_t)NT), b0((size_t)NT);
+    std::vector<char> active((size_t)NT);
+    std::vector<int> chain((size_t)NT);
+    vbs_huff_state carry{0, 0};
+    uint32_t base_blocks = 0;
+    uint64_t fail = ~0ull;                                // (first failing subsequence << 2 | step status): the lowest wins
+    for (int64_t sub0 = 0; sub0 < nsub && base_blocks < (uint32_t)g.nblk; sub0 += NT) {
+        const int nt = (int)std::min<int64_t>(NT, nsub - sub0);
+        const uint32_t cbase = (uint32_t)(sub0 * S);
+        auto end_of = [&](int j) { return (uint32_t)std::min<uint64_t>((uint64_t)cbase + (uint64_t)(j + 1) * S, scan_bits); };
+        s[0] = carry;
+        for (int i = 0; i < nt; ++i) {                    // 1. speculate
+            vbs_huff_state st = i ? vbs_huff_state{cbase + (uint32_t)i * S, 0} : carry;
+            uint32_t blocks = 0;
+            vbs_huff_run<false>(T, words, scan_bits, g, st, end_of(i), blocks, 0, nullptr);
+            s[i + 1] = st; cnt[i] = blocks; run[i] = st;
+            active[i] = st.cz != VBS_HUFF_INVALID;
+            chain[i] = 1;
+        }
+        int rounds = 0;
+        for (int r = 1; r < nt; ++r) {                    // 2. synchronise
+            bool any = false;
+            for (int i = 0; i < nt; ++i) {
+                const int j = i + r;
+                if (!active[i]) continue;
+                if (j >= nt) { active[i] = 0; continue; }
+                uint32_t blocks = 0;
+                vbs_huff_run<false>(T, words, scan_bits, g, run[i], end_of(j), blocks, 0, nullptr);
+                const bool eq = vbs_huff_same(run[i], s[j + 1]);
+                s[j + 1] = run[i]; cnt[j] = blocks;
+                ++chain[i];
+                if (eq || run[i].cz == VBS_HUFF_INVALID) active[i] = 0;
+                any = any || active[i];
+            }
+            ++rounds;
+            if (!any) break;
+        }
+        uint32_t acc = base_blocks;                       // 3. count
+        for (int i = 0; i < nt; ++i) { b0[i] = acc; acc += cnt[i]; }
+        for (int i = 0; i < nt; ++i) {                    // 4. write
+            if (b0[i] >= (uint32_t)g.nblk) continue;
+            vbs_huff_state st = s[i];
+            int rc = st.cz == VBS_HUFF_INVALID ? VBS_HUFF_STEP_INVALID : VBS_HUFF_STEP_OK;
+            uint32_t blocks = 0;
+            if (rc == VBS_HUFF_STEP_OK) rc = vbs_huff_run<true>(T, words, scan_bits, g, st, end_of(i), blocks, b0[i], coef);
+            if (rc != VBS_HUFF_STEP_OK) fail = std::min(fail, (uint64_t)(sub0 + i) << 2 | (uint64_t)rc);
+        }
+        carry = s[nt];
+        base_blocks = acc;
+        counters[0] += 1; counters[1] += rounds; counters[2] = std::max<int64_t>(counters[2], rounds);
+        for (int i = 0; i < nt; ++i) counters[3] = std::max<int64_t>(counters[3], chain[i]);
+    }
+    int status = VBS_OK;
+    if (fail != ~0ull) status = (fail & 3) == VBS_HUFF_STEP_SHORT ? VBS_MJPEG_SHORT : VBS_EINVAL;
+    else if (base_blocks < (uint32_t)g.nblk) status = VBS_MJPEG_SHORT;
+    if (status != VBS_OK) return status;
+    for (int c = 0; c < g.ncomp; ++c) {                   // 5. DC: differences -> values, per component in its scan order
+        const int32_t count = c ? g.mcux * g.mcuy : g.base[1];
+        int pred = 0;
+        for (int32_t k = 0; k < count; ++k) {
+            int16_t* d = coef + (int64_t)vbs_huff_dc_block(g, c, k) * 64;
+            pred += *d;
+            *d = (int16_t)pred;
+        }
+    }
+    return VBS_OK;
+}
+#endif
 
 // Device half: ent / tab / frame_base / qt as vbs_mjpeg_entropy_batch left them (DEVICE copies) -> BGR frames out [n] (out_frame
 // / out_row strides in bytes, 3 bytes per pixel); planes = scratch of n * info[7] bytes.  Asynchronous on `stream`.

@@ -376,7 +376,9 @@ class MarkerTracker:
         """`process` on the package's own AVI reader (no OpenCV): batch k + 1 is decoded while batch k is computed and
         turned into rows.  A Motion-JPEG clip of the variant the native decoder takes (`video_io.MjpegDeviceDecoder`:
         baseline Huffman, 4:4:4 / 4:2:2 / 4:2:0 or gray) is entropy-decoded by C++ threads and reconstructed on the device
-        (`config["mjpeg_on_device"]`, default on; `self.decode_path` says which ran); anything else goes through the
+        (`config["mjpeg_on_device"]`, default on; `self.decode_path` says which ran; `config["mjpeg_entropy"] = "device"`
+        moves the Huffman decode of a clip without restart intervals onto the GPU too, `self.entropy_path` says where it
+        ran); anything else goes through the
         reader's Pillow thread pool into one of two page-locked buffers."""
         from concurrent.futures import ThreadPoolExecutor
         dec = None
@@ -386,10 +388,12 @@ class MarkerTracker:
                 from .video_io import MjpegDeviceDecoder
                 dev = torch.device(self.config.get("device") or "cuda:0")
                 if dev.type == "cuda":
-                    dec = MjpegDeviceDecoder(self.cap, dev, batch, self.config.get("decode_threads"))
+                    dec = MjpegDeviceDecoder(self.cap, dev, batch, self.config.get("decode_threads"),
+                                             entropy=self.config.get("mjpeg_entropy", "host"))
             except (ValueError, MemoryError):               # a JPEG variant outside the native decoder, or no room for its
                 dec = None                                  # page-locked buffers: Pillow, as before
         self.decode_path = "device" if dec is not None else "pillow"
+        self.entropy_path = dec.entropy_path if dec is not None else "host"      # where the Huffman decode runs
         if dec is not None:
             def ahead_of(slot): return dec.entropy(slot)
             def frames_of(slot, m): return dec.reconstruct(slot)

@@ -220,9 +220,18 @@ class MjpegDeviceDecoder:
     `ValueError` at construction, and the caller stays with Pillow.
 
     Two slots of host / device buffers, so that `entropy(slot)` of batch k + 1 can run on a helper thread while
-    `reconstruct(slot)` and the tracker work on batch k."""
+    `reconstruct(slot)` and the tracker work on batch k.
 
-    def __init__(self, reader: "AviReader", device, batch: int, threads: int | None = None):
+    `entropy="device"` (opt-in; the default `"host"` is the path above) moves the Huffman decode to the GPU as well
+    (csrc/k_jpeg_huff.hip, self-synchronising subsequences, one workgroup per frame): `entropy(slot)` then only parses the
+    headers and copies every scan, de-stuffed, into a page-locked buffer (`vbs_mjpeg_scan_batch`), `reconstruct(slot)`
+    uploads those bytes, decodes them on the device, reads the per-frame status words back and runs the host entropy
+    decode for exactly the frames the device handed back (a scan that ends early, which libjpeg pads with zero bits; a
+    broken one, which raises the same `IOError`).  A clip with restart intervals stays on the host path whatever was
+    asked: `entropy_path` says which one runs."""
+
+    def __init__(self, reader: "AviReader", device, batch: int, threads: int | None = None, entropy: str = "host",
+                 subseq_bits: int = 0):
         import ctypes as C
         import os
 
@@ -265,6 +274,34 @@ class MjpegDeviceDecoder:
         self._planes = torch.empty((self.batch, self._pl), dtype=torch.uint8, device=self.device)
         self._out = [torch.empty((self.batch, self.height, self.width, 3), dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.uploaded_bytes = 0                                        # what crossed to the device so far (all batches)
+        if entropy not in ("host", "device"):
+            raise ValueError("entropy must be 'host' or 'device'")
+        # restart intervals are outside the device entropy decoder: such a clip keeps the host path
+        self.entropy_path = "device" if entropy == "device" and self._info[5] == 0 else "host"
+        self.subseq_bits = int(subseq_bits)
+        self.host_fallback_frames = 0                                  # frames the device handed back to the host decoder
+        if self.entropy_path == "device":
+            self._buf_size = len(reader._buf)
+            biggest = max(size for _, size in reader._frames)
+            per = (biggest + L.MJPEG_SCAN_GUARD + L.MJPEG_SCAN_ALIGN - 1) // L.MJPEG_SCAN_ALIGN * L.MJPEG_SCAN_ALIGN
+            self._stage_cap = self.batch * per
+            self._stage = [torch.empty(self._stage_cap, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
+            self._soff = [torch.empty(self.batch, dtype=torch.int64, pin_memory=pin) for _ in range(2)]
+            self._sbits = [torch.empty(self.batch, dtype=torch.int64, pin_memory=pin) for _ in range(2)]
+            self._tset = [torch.empty(self.batch, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+            self._sets = [torch.empty((self.batch, L.MJPEG_HUFF_SET_BYTES), dtype=torch.uint8) for _ in range(2)]
+            self._nsets = [C.c_int32(0), C.c_int32(0)]
+            self._first = [0, 0]                                       # clip index of the slot's first frame
+            self._frames_of = [None, None]                             # the slot's (offset, size) list, for the frames handed back
+            self._dstage = torch.empty(self._stage_cap, dtype=torch.uint8, device=self.device)
+            self._dsoff = torch.empty(self.batch, dtype=torch.int64, device=self.device)
+            self._dsbits = torch.empty(self.batch, dtype=torch.int64, device=self.device)
+            self._dtset = torch.empty(self.batch, dtype=torch.int32, device=self.device)
+            self._dsets = torch.empty((self.batch, L.MJPEG_HUFF_SET_BYTES), dtype=torch.uint8, device=self.device)
+            self._dstatus = torch.empty(self.batch, dtype=torch.int32, device=self.device)
+            # one frame's worth of the host decoder's buffers, for the frames handed back
+            self._fent = torch.empty(self._cap, dtype=torch.int32, pin_memory=pin)
+            self._ftab = torch.empty(self._nblk, dtype=torch.int32, pin_memory=pin)
 
     def entropy(self, slot: int, n: int | None = None) -> int:
         """Host half for the reader's next up to `n` (default: batch) frames into `slot`.  Returns the count (0 at the end).
@@ -277,8 +314,24 @@ class MjpegDeviceDecoder:
         fr = r._frames[r._next:r._next + m]
         r._next += m
         offs = np.asarray([f[0] for f in fr], dtype=np.int64)
-        sizes = np.asarray([f[1] for f in fr], dtype=np.int32)
         st = self._status[slot]
+        if self.entropy_path == "device":
+            import ctypes as C
+            sizes = np.asarray([f[1] for f in fr], dtype=np.int64)
+            self._first[slot], self._frames_of[slot] = r._next - m, fr
+            bad = self._lib.vbs_mjpeg_scan_batch(self._base, self._buf_size, offs.ctypes.data, sizes.ctypes.data, m, self._info,
+                                                 self._stage[slot].data_ptr(), self._stage_cap, self._soff[slot].data_ptr(),
+                                                 self._sbits[slot].data_ptr(), self._tset[slot].data_ptr(),
+                                                 self._sets[slot].data_ptr(), C.byref(self._nsets[slot]),
+                                                 self._regions[slot].ctypes.data, self._qt[slot].data_ptr(), st.ctypes.data,
+                                                 self.threads)
+            if bad < 0:
+                raise RuntimeError(f"vbs_mjpeg_scan_batch failed ({bad})")
+            if bad:
+                i = int(np.flatnonzero(st[:m])[0])
+                raise IOError(f"Motion-JPEG frame {r._next - m + i}: corrupt or not of the clip's JPEG variant (status {int(st[i])})")
+            return m
+        sizes = np.asarray([f[1] for f in fr], dtype=np.int32)
         bad = self._lib.vbs_mjpeg_entropy_batch(self._base, offs.ctypes.data, sizes.ctypes.data, m, self._info,
                                                 self._ent[slot].data_ptr(), self._tab[slot].data_ptr(), self._fb[slot].data_ptr(),
                                                 self._regions[slot].ctypes.data, self._qt[slot].data_ptr(), st.ctypes.data,
@@ -298,6 +351,9 @@ class MjpegDeviceDecoder:
         out = self._out[slot]
         if not m:
             return out[:0]
+        if self.entropy_path == "device":
+            self._huffman_on_device(slot, m)
+            return self._reconstruct(slot, m)
         ent, reg = self._ent[slot], self._regions[slot]
         for t in range(self.threads):                                  # only the words the host threads wrote
             a, u = int(reg[2 * t]), int(reg[2 * t + 1])
@@ -308,6 +364,53 @@ class MjpegDeviceDecoder:
         self._dfb[:m].copy_(self._fb[slot][:m], non_blocking=True)
         self._dqt[:m].copy_(self._qt[slot][:m], non_blocking=True)
         self.uploaded_bytes += m * (4 * self._nblk + 8 + 384)
+        return self._reconstruct(slot, m)
+
+    def _huffman_on_device(self, slot: int, m: int):
+        """The device entropy decode of what `entropy(slot)` staged: leaves ent / tab / frame_base / qt on the device as the
+        host path's upload would, the frames the device hands back decoded by the host and uploaded into their places."""
+        import torch
+        stage, reg = self._stage[slot], self._regions[slot]
+        for t in range(self.threads):                                  # only the bytes the host threads staged
+            a, u = int(reg[2 * t]), int(reg[2 * t + 1])
+            if u:
+                self._dstage[a:a + u].copy_(stage[a:a + u], non_blocking=True)
+                self.uploaded_bytes += u
+        ns = int(self._nsets[slot].value)
+        self._dsoff[:m].copy_(self._soff[slot][:m], non_blocking=True)
+        self._dsbits[:m].copy_(self._sbits[slot][:m], non_blocking=True)
+        self._dtset[:m].copy_(self._tset[slot][:m], non_blocking=True)
+        self._dqt[:m].copy_(self._qt[slot][:m], non_blocking=True)
+        self._dsets[:ns].copy_(self._sets[slot][:ns], non_blocking=True)
+        self.uploaded_bytes += m * (8 + 8 + 4 + 384) + ns * self._dsets.shape[1]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.vbs_mjpeg_huffman_device(self._dstage.data_ptr(), self._dsoff.data_ptr(), self._dsbits.data_ptr(),
+                                                self._dtset.data_ptr(), self._dsets.data_ptr(), ns, m, self._info, self.subseq_bits,
+                                                self._dent.data_ptr(), self._dtab.data_ptr(), self._dfb.data_ptr(),
+                                                self._dstatus.data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError(f"vbs_mjpeg_huffman_device failed ({rc})")
+        status = self._dstatus[:m].cpu().numpy()                       # (waits for the kernels: the host must know whom to redo)
+        for i in np.flatnonzero(status).tolist():
+            off, size = self._frames_of[slot][i]
+            offs, sizes = np.asarray([off], dtype=np.int64), np.asarray([size], dtype=np.int32)
+            fb, reg1, st1 = np.zeros(1, np.int64), np.zeros(2, np.int64), np.zeros(1, np.int32)
+            qt1 = np.zeros((1, 3, 64), np.uint16)
+            bad = self._lib.vbs_mjpeg_entropy_batch(self._base, offs.ctypes.data, sizes.ctypes.data, 1, self._info,
+                                                    self._fent.data_ptr(), self._ftab.data_ptr(), fb.ctypes.data, reg1.ctypes.data,
+                                                    qt1.ctypes.data, st1.ctypes.data, 1)
+            if bad:
+                raise IOError(f"Motion-JPEG frame {self._first[slot] + i}: corrupt or not of the clip's JPEG variant "
+                              f"(status {int(st1[0])}, device status {int(status[i])})")
+            u = int(reg1[1])
+            self._dent[i * self._cap:i * self._cap + u].copy_(self._fent[:u])      # (blocking: the one-frame buffers are reused)
+            self._dtab[i].copy_(self._ftab)
+            self.uploaded_bytes += 4 * u + 4 * self._nblk
+            self.host_fallback_frames += 1
+
+    def _reconstruct(self, slot: int, m: int):
+        import torch
+        out = self._out[slot]
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
         rc = self._lib.vbs_mjpeg_reconstruct(self._dent.data_ptr(), self._dtab.data_ptr(), self._dfb.data_ptr(), self._dqt.data_ptr(), m,
                                              self._info, self._planes.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), stream)
