@@ -203,6 +203,11 @@ int vbs_draw_tracking(const uint8_t* frames, int n, int height, int width, int64
  * number of CHAIN_APPROX_SIMPLE vertices it contributes (bit d of the index = neighbour in chain
  * direction d is foreground; 0=E,1=NE,2=N,...,7=SE). */
 int vbs_contour_lut(uint8_t out[256]);
+/* host-only helper, the counterpart of vbs_contour_lut for the diameter validation: the 256-entry table of a border pixel's
+ * OUTGOING chain steps (same index).  Bits 4 d .. 4 d + 3 of an entry = how many times the outer border leaves the pixel in
+ * chain direction d; summed over the border pixels of hole-free foreground this is the full (unapproximated) chain of every
+ * outer border: its unit and diagonal step counts and, with sum x dy - y dx over the steps, twice its signed area. */
+int vbs_step_lut(uint32_t out[256]);
 /* host-only helper: the body (no header line) of the tracker's CSV - `pandas.DataFrame(rows).to_csv(index=False)`,
  * marker_detection.py:464-468 - for n rows of three int64 columns (frameno, row, col) and nf float64 columns (Ox, Oy, Cx,
  * Cy, major_axis, minor_axis, angle), byte for byte: floats as Python's repr writes them (shortest digits that round-trip,
@@ -302,6 +307,42 @@ int vbs_calculate_3d(int device, const double* uvd, int n, const vbs_camera* cam
  * counts [dev] int32 [n] = number of rows, or a negative status for that frame. */
 int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8_t* area_mask, int n,
                       double* det, int32_t* counts, void* stream);
+
+/* ---- Marker diameter validation (code/Precision_Validation/DiameterValidation.py) ------------------------------------------
+ * vbs_measure_markers - main's GaussianBlur (:218) and measure_markers (:113-144) with the statistics of :169-170 / :233-234,
+ * for every frame of a batch (frames as for vbs_find_markers; BGR goes through the BGR2GRAY of :211 first; undistortion
+ * set on the handle is NOT applied).  GaussianBlur(gray, (5,5), 0) = the fixed kernel (1, 4, 6, 4, 1) / 16 in the fixed-point
+ * model of the other blurs (its standing against cv2 itself: restated, unpinned) -> THRESH_BINARY_INV (:115: blur <= threshold,
+ * level floor(threshold)) -> external contours (:116; 8-connected components, holes ignored, in findContours' order) ->
+ * contourArea (:122), arcLength (:126), circularity (:129), the filters area < min_area (:123), perimeter == 0 (:127),
+ * circularity < min_circularity (:130) -> minEnclosingCircle (:134) -> diameter_mm = 2 radius / scale_px_per_mm + offset_mm
+ * (:135-138).
+ *   rec [dev] float64 [n,max_markers,VBS_DIAM_COLS], one row per surviving contour in the reference's order:
+ *     0 cx, 1 cy, 2 radius_px (the EXACT minimum enclosing circle of the pixel centres, float64; cv2 returns float32),
+ *     3 diameter_mm, 4 area (= |area2| / 2), 5 perimeter (= n_axis + n_diag sqrt 2 in float64), 6 circularity,
+ *     7 n_axis, 8 n_diag (unit / diagonal steps of the full border chain), 9 first pixel (y * width + x),
+ *     10 number of support points (1, 2 or 3), 11-16 their (x, y), 17 pixels of the component (holes filled),
+ *     18-21 bounding box x0, y0, x1, y1 (inclusive), 22 area2 = the signed shoelace sum over the chain, 23 component id.
+ *   counts [dev] int32 [n] = rows, or a negative status; stats [dev] float64 [n,VBS_DIAM_STATS_COLS] = count, mean, std
+ *     (np.std, ddof 0), min, max of diameter_mm (NaN at count 0 or a negative status), summed in a fixed order.
+ * Capacity: the labelling's (VBS_ECAPACITY beyond 30720 runs, max_markers or 512 components per frame), and a SURVIVING
+ * contour whose bounding box exceeds VBS_DIAM_MAX_EXTENT pixels in either direction reports VBS_ECAPACITY for its frame: the
+ * circle kernel keeps two candidate points per row of the box in a 4 KB LDS array, coordinates packed into 16 bits each (the
+ * exact integer tests themselves would hold for a larger box).  A contour the filters reject - the chessboard of a
+ * validation shot - never counts against it.  Six launches per pass (clear, threshold, k_label, measure, circle, statistics;
+ * seven for BGR), no allocation (BGR: the gray plane, as above).
+ * The call runs in the handle's FIRST pass workspace and overwrites its bit planes, run tables and per-frame statistics:
+ * afterwards vbs_frame_stats and vbs_stage_tables describe this call's last pass, not the last tracking pass.
+ * vbs_threshold_bits (stage entry for parity tests): the first step alone -> bits [dev] uint64 [n,height,ceil(width/64)],
+ * bit x % 64 of word x / 64 = pixel x. */
+#define VBS_DIAM_COLS        24
+#define VBS_DIAM_STATS_COLS   5
+#define VBS_DIAM_MAX_EXTENT 512
+int vbs_threshold_bits(vbs_handle* h, const uint8_t* frames, int n, int channels, int64_t stride_n, int64_t stride_row,
+                       double threshold, uint64_t* bits, void* stream);
+int vbs_measure_markers(vbs_handle* h, const uint8_t* frames, int n, int channels, int64_t stride_n, int64_t stride_row,
+                        double threshold, double min_area, double min_circularity, double scale_px_per_mm, double offset_mm,
+                        double* rec, int32_t* counts, double* stats, void* stream);
 
 /* MarkerTracker._track_markers (marker_detection.py:349-396): per reference ID the nearest
  * detection (first on ties), dropped when farther than min_dist.  ref_xy [dev] float64 [m_ref,2]

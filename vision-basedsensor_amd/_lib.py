@@ -11,6 +11,7 @@ FLAG_TRACKED, FLAG_XYZ = 1, 2
 JPEG_BLOCK_BITS_MAX, JPEG_HEADER_BYTES = 1660, 623
 MJPEG_SCAN_ALIGN, MJPEG_SCAN_GUARD, MJPEG_HUFF_SET_BYTES, MJPEG_SUBSEQ_BITS, MJPEG_SHORT = 16, 16, 8928, 1024, 1
 SERIES_CHUNK, SERIES_REC_COLS, STATS_COLS, WINDOW_COLS = 32, 5, 5, 4
+DIAM_COLS, DIAM_STATS_COLS, DIAM_MAX_EXTENT = 24, 5, 512
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -22,7 +23,8 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_stage_tables", "vbs_deviation_plane", "vbs_format_csv", "vbs_mjpeg_probe", "vbs_mjpeg_entropy_batch",
            "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking",
            "vbs_series_chunks", "vbs_series_stats", "vbs_series_stats_f64", "vbs_series_partial", "vbs_series_merge",
-           "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device")
+           "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device",
+           "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers")
 
 
 class Camera(C.Structure):
@@ -116,6 +118,9 @@ def lib():
         "vbs_series_merge": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "vbs_window_means": (i32, [vp, vp, i32, i32, vp, i32, vp, vp]),
         "vbs_displacement_from_frame": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "vbs_step_lut": (i32, [vp]),
+        "vbs_threshold_bits": (i32, [vp, vp, i32, i32, i64, i64, f64, vp, vp]),
+        "vbs_measure_markers": (i32, [vp, vp, i32, i32, i64, i64, f64, f64, f64, f64, f64, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

@@ -84,6 +84,12 @@ extern "C" int vbs_contour_lut(uint8_t out[256]) {
     return VBS_OK;
 }
 
+extern "C" int vbs_step_lut(uint32_t out[256]) {
+    if (!out) return VBS_EINVAL;
+    make_step_lut(out);
+    return VBS_OK;
+}
+
 extern "C" int vbs_gaussian_taps_q8(int ksize, double sigma, int32_t* out) {
     if (!out || ksize < 1 || !(ksize & 1) || !(sigma > 0)) return VBS_EINVAL;
     std::vector<int> k = gaussian_taps_q8(ksize, sigma);
@@ -185,6 +191,7 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
 #define ALLOC(field, count) if ((rc = dev_alloc(h, &h->field, (count))) != VBS_OK) return rc
     ALLOC(ncc_rx, (size_t)width); ALLOC(ncc_ry, (size_t)height);
     ALLOC(lut, 256);
+    ALLOC(step_lut, 256);
     ALLOC(blur_frags, frags.size() / 4);
     if (!frags16h.empty()) { ALLOC(blur16_h, frags16h.size() / 4); ALLOC(blur16_v, frags16v.size() / 4); }
     std::vector<u32> nfrags = ncc_mfma_fragments(h->ncc, bp.ncc_l);
@@ -209,6 +216,9 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
     HIPCHK(h, hipMemcpy(h->ncc_rx, rx.data(), width * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->ncc_ry, ry.data(), height * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->lut, lut, 256, hipMemcpyHostToDevice));
+    u32 steps[256];
+    make_step_lut(steps);
+    HIPCHK(h, hipMemcpy(h->step_lut, steps, sizeof(steps), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->blur_frags, frags.data(), frags.size() * sizeof(u32), hipMemcpyHostToDevice));
     if (h->blur16_h) {
         HIPCHK(h, hipMemcpy(h->blur16_h, frags16h.data(), frags16h.size() * sizeof(u32), hipMemcpyHostToDevice));
@@ -271,15 +281,16 @@ static int need_gray(vbs_handle* h, Workspace& w, hipStream_t s) {
 
 // The per-frame statistics of a pass <- 0; for a pass of a few frames also what launch_labelling would clear (k_stage_lat's
 // headers, the slow counter and flags lie in front of fstat in one allocation): one launch instead of two
-static void clear_pass(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
+// (`labelling_follows` = false: the pass does not go through launch_labelling, which is what consumes `pass_cleared`)
+static void clear_pass(vbs_handle* h, Workspace& w, int nb, hipStream_t s, bool labelling_follows = true) {
     h->last_ws = &w;                                     // every pass records its workspace: vbs_frame_stats / vbs_stage_tables
     if (nb <= h->lat_frames && (h->stage_impl == 0 || h->stage_impl >= 3) && nb <= w.lat_slots) {
         launch_fill(w.lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + 4 + (size_t)h->maxb + (size_t)nb * 8, s);
-        w.pass_cleared = true;
+        w.pass_cleared = labelling_follows;
     } else {
         // (the slow counter and the frames' flags lie right in front of the statistics: launch_labelling's fill with this one)
         launch_fill(w.slow_total, 0u, (size_t)4 + (size_t)h->maxb + (size_t)nb * 8, s);
-        w.pass_cleared = true;
+        w.pass_cleared = labelling_follows;
     }
 }
 
@@ -547,6 +558,75 @@ extern "C" int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8
         launch_labelling(h, w, nb, s);
         launch_finalize(h, w, nb, det + (size_t)off * h->maxm * VBS_DET_COLS, counts + off, s);
         int rc = check_launch(h);
+        if (rc != VBS_OK) return rc;
+    }
+    return VBS_OK;
+}
+
+// One pass of the diameter front end: gray (converted first when the frames are BGR) -> blurred, thresholded bits
+static int diam_bits_pass(vbs_handle* h, Workspace& w, const u8* frames, int nb, int channels, int64_t stride_n,
+                          int64_t stride_row, int thr, u64* bits, u64* zero_plane, hipStream_t s) {
+    if (channels == 1) {
+        launch_diam_threshold(h, frames, stride_n, stride_row, nb, thr, bits, zero_plane, s);
+    } else {
+        int rc = need_gray(h, w, s);
+        if (rc != VBS_OK) return rc;
+        launch_gray(h, frames, nb, channels, stride_n, stride_row, w.gray, s);
+        launch_diam_threshold(h, w.gray, (int64_t)h->H * h->P, h->P, nb, thr, bits, zero_plane, s);
+    }
+    return VBS_OK;
+}
+
+static int diam_threshold_level(double threshold) {     // cv2.threshold on uint8: the level is floor(threshold)
+    const double f = std::floor(threshold);
+    return f < -1.0 ? -1 : (f > 255.0 ? 255 : (int)f);
+}
+
+extern "C" int vbs_threshold_bits(vbs_handle* h, const uint8_t* frames, int n, int channels, int64_t stride_n,
+                                  int64_t stride_row, double threshold, uint64_t* bits, void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!frames || !bits || n < 0 || (channels != 1 && channels != 3) || stride_row < (int64_t)h->W * channels ||
+        !std::isfinite(threshold)) {
+        h->err = "vbs_threshold_bits: bad argument";
+        return VBS_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t nw = (size_t)h->H * h->WW;
+    for (int off = 0; off < n; off += h->maxb) {
+        const int nb = std::min(h->maxb, n - off);
+        int rc = diam_bits_pass(h, h->ws[0], frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row,
+                                diam_threshold_level(threshold), (u64*)bits + off * nw, nullptr, s);
+        if (rc == VBS_OK) rc = check_launch(h);
+        if (rc != VBS_OK) return rc;
+    }
+    return VBS_OK;
+}
+
+extern "C" int vbs_measure_markers(vbs_handle* h, const uint8_t* frames, int n, int channels, int64_t stride_n,
+                                   int64_t stride_row, double threshold, double min_area, double min_circularity,
+                                   double scale_px_per_mm, double offset_mm, double* rec, int32_t* counts, double* stats,
+                                   void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!frames || !rec || !counts || !stats || n < 0 || (channels != 1 && channels != 3) ||
+        stride_row < (int64_t)h->W * channels || !std::isfinite(threshold) || !std::isfinite(min_area) ||
+        !std::isfinite(min_circularity) || !(scale_px_per_mm > 0.0) || !std::isfinite(scale_px_per_mm) ||
+        !std::isfinite(offset_mm)) {
+        h->err = "vbs_measure_markers: bad argument";
+        return VBS_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Workspace& w = h->ws[0];
+    HIPCHK(h, hipSetDevice(h->device));
+    for (int off = 0; off < n; off += h->maxb) {
+        const int nb = std::min(h->maxb, n - off);
+        clear_pass(h, w, nb, s, false);
+        int rc = diam_bits_pass(h, w, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row,
+                                diam_threshold_level(threshold), w.open_bits, w.band_bits, s);
+        if (rc != VBS_OK) return rc;
+        launch_diam_measure(h, w, nb, min_area, min_circularity, scale_px_per_mm, offset_mm,
+                            rec + (size_t)off * h->maxm * VBS_DIAM_COLS, counts + off, stats + (size_t)off * VBS_DIAM_STATS_COLS, s);
+        rc = check_launch(h);
         if (rc != VBS_OK) return rc;
     }
     return VBS_OK;

@@ -100,6 +100,7 @@ struct vbs_handle {
     float2* ncc_rowf;  // [H] {rows of the NCC window inside the image, (float) ncc_ry}: border tiles of k_ncc_mfma
     double* ncc_tab;   // [VBS_NCC_MAXL] g, then [VBS_NCC_MAXL + 1] cg: the exact path of k_ncc_mfma reads them from memory
     u8* lut;           // [256] contour vertex table
+    u32* step_lut = nullptr;   // [256] outgoing chain steps of a border pixel (make_step_lut, k_diameter.hip)
     short* umap1;      // [H][W][2] int16 undistortion source pixel (CV_16SC2)
     unsigned short* umap2;   // [H][W] fractional index into the bilinear weight table
     int* uwtab;        // [1024][4] bilinear weights in 1/32768
@@ -180,6 +181,15 @@ void launch_deviation_plane(vbs_handle* h, const float* vs, const float* ve, con
 void launch_assign_ids(vbs_handle* h, const double* det, const int32_t* count, int num_layers, int full_mode,
                        int32_t* ids_out, double* xy_out, int cap, int32_t* m_out, hipStream_t s);
 void make_contour_lut(u8 out[256]);
+void make_step_lut(u32 out[256]);
+// k_label<0> over EVERY frame of the pass (band_bits / open_bits as they lie in the workspace), nothing else
+void launch_label_all(vbs_handle* h, Workspace& w, int nb, hipStream_t s);
+// k_diameter.hip: blur + inverse threshold of gray frames -> bits [nb][H][WW] (zero_plane, if given, <- 0), and the chain from
+// the bits in w.open_bits (w.band_bits empty) to records, counts and statistics
+void launch_diam_threshold(vbs_handle* h, const u8* gray, int64_t stride_n, int64_t stride_row, int nb, int thr, u64* bits,
+                           u64* zero_plane, hipStream_t s);
+void launch_diam_measure(vbs_handle* h, Workspace& w, int nb, double min_area, double min_circ, double scale, double offset_mm,
+                         double* rec, int32_t* counts, double* stats, hipStream_t s);
 std::vector<u32> ncc_mfma_fragments(const NccConst& nc, int l);
 std::vector<u32> blur_mfma_fragments(const std::vector<int>& taps_a, const std::vector<int>& taps_b, int nk,
                                      int sa0, int nka);

@@ -1308,3 +1308,12 @@ void launch_finalize_track(vbs_handle* h, Workspace& w, int nb, double* det, int
                w.area_sums, w.probe, w.fstat, w.ell, w.det64, w.cnt, det, counts, h->H, h->W, h->WW, h->maxm,
                h->force_seq_match ? 1 : 0, ref_xy, m_ref, min_dist, table, cam ? 1 : 0, c, min_size);
 }
+
+// The general kernel alone over every frame of the pass: what vbs_measure_markers labels its thresholded bits with (the
+// same instance as above, so no code is generated for it)
+void launch_label_all(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
+    VBS_LAUNCH(h, s, "k_label", k_label<0>, dim3(nb < 64 ? nb : 64), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase,
+               w.node_pos, w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat,
+               h->lut, w.slow_flag, (const u32*)nullptr, w.probe, nb, 1, h->H, h->W, h->WW, h->maxm, 0,
+               (const u64*)nullptr, (const u64*)nullptr, 0, 0, 0, 0);
+}

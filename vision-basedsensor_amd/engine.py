@@ -212,6 +212,31 @@ class Engine:
         return det, counts
 
     # ---- a15 ---------------------------------------------------------------------------------
+    # ---- diameter validation (Precision_Validation/DiameterValidation.py) ------------------------
+    def threshold_bits(self, frames, threshold):
+        """The first step of `measure_markers` alone: GaussianBlur 5x5 + THRESH_BINARY_INV as bit-packed masks, int64 tensor
+        [n, H, ceil(W / 64)] (the words are unsigned; bit x % 64 of word x // 64 = pixel x)."""
+        frames, n, ch, sn, sr = self._frames(frames)
+        bits = torch.zeros((n, self.H, (self.W + 63) // 64), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_threshold_bits(self._h, _ptr(frames), n, ch, sn, sr, float(threshold), _ptr(bits),
+                                                    self._stream()), "vbs_threshold_bits")
+        return bits
+
+    def measure_markers(self, frames, threshold, scale, min_area=100, min_circularity=0.85, offset_mm=0.0):
+        """`measure_markers` (DiameterValidation.py:113-144, after the blur of :218) for every frame of a batch: records
+        [n, max_markers, DIAM_COLS] float64 (include/vbs.h lists the columns), counts [n] int32 (rows per frame, or a negative
+        status), stats [n, 5] float64 (count, mean, np.std, min, max of diameter_mm).  Device tensors, no synchronisation."""
+        frames, n, ch, sn, sr = self._frames(frames)
+        rec = torch.zeros((n, self.max_markers, L.DIAM_COLS), dtype=torch.float64, device=self.device)
+        counts = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        stats = torch.zeros((n, L.DIAM_STATS_COLS), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_measure_markers(self._h, _ptr(frames), n, ch, sn, sr, float(threshold), float(min_area),
+                                                     float(min_circularity), float(scale), float(offset_mm), _ptr(rec),
+                                                     _ptr(counts), _ptr(stats), self._stream()), "vbs_measure_markers")
+        return rec, counts, stats
+
     def track(self, det, counts, ref_xy, min_dist=20.0):
         ref = torch.as_tensor(ref_xy, dtype=torch.float64, device=self.device).contiguous().reshape(-1, 2)
         if det.dtype != torch.float64 or not det.is_contiguous() or det.device != self.device or det.dim() != 3 \
