@@ -8,10 +8,10 @@ properties the class claims (checked by tests/test_label_cases.py, relied on by 
 
 Capacity rule (`expected_capacity`), restated from the general labelling kernel k_label.hip, which every route hands a
 frame to when its own tables give out, so that the rule is the same on every route:
-  * k_label.hip:573  `nruns > VBS_RUN_CAP` (30 720, common.h:16) for any mask it labels -> VBS_ECAPACITY.  The masks
+  * k_label.hip:335  `nruns > VBS_RUN_CAP` (30 720, common.h:16) for any mask it labels -> VBS_ECAPACITY.  The masks
     are the band mask, the opened area mask and - only when the opened mask has holes - its complement.  A run is a
     maximal horizontal run of 1-pixels in one row.
-  * k_label.hip:646  band components > max_markers; opened components > max_markers, > 1024, or
+  * k_label.hip:407  band components > max_markers; opened components > max_markers, > 1024, or
     `ncomp * NMOM * 8 > sizeof(parent) / 2` (NMOM = 15, parent = u32[VBS_RUN_CAP]: 15 * 8 * ncomp > 61 440, that is more
     than 512 contours); components of the complement > 1024 -> VBS_ECAPACITY.
 Holes are background components (4-connected, the complement of 8-connected components as cv2.findContours sees them)
@@ -26,8 +26,8 @@ from scipy import ndimage
 from oracle import stages as O
 
 RUN_CAP = 30720              # VBS_RUN_CAP, common.h:16
-OPEN_CAP = 512               # 61 440 / (NMOM * 8), k_label.hip:646
-COMP_CAP = 1024              # k_label.hip:646 (the complement's components; max_markers is at most 1024 too)
+OPEN_CAP = 512               # 61 440 / (NMOM * 8), k_label.hip:407
+COMP_CAP = 1024              # k_label.hip:407 (the complement's components; max_markers is at most 1024 too)
 
 EIGHT = np.ones((3, 3), bool)
 

@@ -279,26 +279,21 @@ static int need_gray(vbs_handle* h, Workspace& w, hipStream_t s) {
     return VBS_OK;
 }
 
-// The per-frame statistics of a pass <- 0; for a pass of a few frames also what launch_labelling would clear (k_stage_lat's
-// headers, the slow counter and flags lie in front of fstat in one allocation): one launch instead of two
-// (`labelling_follows` = false: the pass does not go through launch_labelling, which is what consumes `pass_cleared`)
-static void clear_pass(vbs_handle* h, Workspace& w, int nb, hipStream_t s, bool labelling_follows = true) {
+// THE clear of a pass, one launch: the slow counter, the frames' flags and their statistics <- 0 (one behind the other in one
+// allocation), for the few-frames route k_stage_lat's headers in front of them as well.  Passes that do not label clear alike.
+static void clear_pass(vbs_handle* h, Workspace& w, int nb, const LabelPlan& plan, hipStream_t s) {
     h->last_ws = &w;                                     // every pass records its workspace: vbs_frame_stats / vbs_stage_tables
-    if (nb <= h->lat_frames && (h->stage_impl == 0 || h->stage_impl >= 3) && nb <= w.lat_slots) {
-        launch_fill(w.lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + 4 + (size_t)h->maxb + (size_t)nb * 8, s);
-        w.pass_cleared = labelling_follows;
-    } else {
-        // (the slow counter and the frames' flags lie right in front of the statistics: launch_labelling's fill with this one)
-        launch_fill(w.slow_total, 0u, (size_t)4 + (size_t)h->maxb + (size_t)nb * 8, s);
-        w.pass_cleared = labelling_follows;
-    }
+    const size_t n = (size_t)4 + (size_t)h->maxb + (size_t)nb * 8;
+    if (plan.route == LABEL_LAT) launch_fill(w.lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + n, s);
+    else launch_fill(w.slow_total, 0u, n, s);
 }
 
 // One internal pass of the detection stage: the blur reads gray frames directly, others are converted or remapped first.
-static int detect_pass(vbs_handle* h, Workspace& w, const u8* frames, int nb, int channels, int64_t stride_n,
+// (`plan`: the pass's label_plan - its clear happens here, so a caller that labels hands the same plan to launch_labelling)
+static int detect_pass(vbs_handle* h, Workspace& w, const u8* frames, int nb, const LabelPlan& plan, int channels, int64_t stride_n,
                        int64_t stride_row, u8* mask_u8, u8* area_u8, double* ncc_out, hipStream_t s) {
     if (h->undist || channels != 1) { int rc = need_gray(h, w, s); if (rc != VBS_OK) return rc; }
-    clear_pass(h, w, nb, s);
+    clear_pass(h, w, nb, plan, s);
     if (h->undist) {                                    // marker_detection.py:88-89: undistort, then cvtColor
         launch_remap(h, frames, nb, channels, stride_n, stride_row, w.gray, 1, s);
         launch_blur(h, w, w.gray, (int64_t)h->H * h->P, h->P, nb, area_u8, s);
@@ -318,7 +313,8 @@ static int detect_loop(vbs_handle* h, const u8* frames, int n, int channels, int
     HIPCHK(h, hipSetDevice(h->device));
     const size_t hw = (size_t)h->H * h->W;
     for (int off = 0; off < n; off += h->maxb) {
-        int rc = detect_pass(h, h->ws[0], frames + (int64_t)off * stride_n, std::min(h->maxb, n - off), channels, stride_n,
+        const int nb = std::min(h->maxb, n - off);
+        int rc = detect_pass(h, h->ws[0], frames + (int64_t)off * stride_n, nb, label_plan(h, h->ws[0], nb), channels, stride_n,
                              stride_row, mask ? mask + off * hw : nullptr, area_mask ? area_mask + off * hw : nullptr,
                              ncc ? ncc + off * hw : nullptr, s);
         if (rc != VBS_OK) return rc;
@@ -365,7 +361,7 @@ extern "C" int vbs_normxcorr2(vbs_handle* h, const uint8_t* area_mask, int n, do
     const size_t hw = (size_t)h->H * h->W;
     for (int off = 0; off < n; off += h->maxb) {
         int nb = std::min(h->maxb, n - off);
-        clear_pass(h, w, nb, s);
+        clear_pass(h, w, nb, label_plan(h, w, nb), s);
         launch_threshold(h, w, area_mask + off * hw, area_mask + off * hw, nb, s);
         launch_popcount(h, w, nb, s);
         launch_ncc(h, w, nb, mask ? mask + off * hw : nullptr, ncc ? ncc + off * hw : nullptr, s);
@@ -553,9 +549,10 @@ extern "C" int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8
     const size_t hw = (size_t)h->H * h->W;
     for (int off = 0; off < n; off += h->maxb) {
         int nb = std::min(h->maxb, n - off);
-        clear_pass(h, w, nb, s);
+        const LabelPlan plan = label_plan(h, w, nb);
+        clear_pass(h, w, nb, plan, s);
         launch_threshold(h, w, mask + off * hw, area_mask + off * hw, nb, s);
-        launch_labelling(h, w, nb, s);
+        launch_labelling(h, w, nb, plan, s);
         launch_finalize(h, w, nb, det + (size_t)off * h->maxm * VBS_DET_COLS, counts + off, s);
         int rc = check_launch(h);
         if (rc != VBS_OK) return rc;
@@ -620,7 +617,7 @@ extern "C" int vbs_measure_markers(vbs_handle* h, const uint8_t* frames, int n, 
     HIPCHK(h, hipSetDevice(h->device));
     for (int off = 0; off < n; off += h->maxb) {
         const int nb = std::min(h->maxb, n - off);
-        clear_pass(h, w, nb, s, false);
+        clear_pass(h, w, nb, label_plan(h, w, nb), s);
         int rc = diam_bits_pass(h, w, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row,
                                 diam_threshold_level(threshold), w.open_bits, w.band_bits, s);
         if (rc != VBS_OK) return rc;
@@ -737,11 +734,12 @@ extern "C" int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int 
         nb = std::min(k == 0 ? lead : h->maxb, n - off);
         Workspace& w = h->ws[(two && (k & 1)) ? 1 : 0];
         hipStream_t ss = (two && (k & 1)) ? h->stream2 : s;
-        int rc = detect_pass(h, w, frames + (int64_t)off * stride_n, nb, channels, stride_n, stride_row, nullptr, nullptr, nullptr,
-                             ss);
+        const LabelPlan plan = label_plan(h, w, nb);
+        int rc = detect_pass(h, w, frames + (int64_t)off * stride_n, nb, plan, channels, stride_n, stride_row, nullptr, nullptr,
+                             nullptr, ss);
         if (rc != VBS_OK) return join(rc);
-        launch_labelling(h, w, nb, ss);
-        if (table && nb <= h->lat_frames)                // a few frames: detections and tracking rows in one launch
+        launch_labelling(h, w, nb, plan, ss);
+        if (table && plan.few)                           // a few frames: detections and tracking rows in one launch
                                                          // (for a batch pass the one launch measured nothing: 282.1 k against 283.1 k frames/s)
             launch_finalize_track(h, w, nb, det ? det + (size_t)off * h->maxm * VBS_DET_COLS : nullptr, counts ? counts + off : nullptr,
                                   ref_xy, m_ref, min_dist, table + (size_t)off * m_ref * VBS_TABLE_COLS, cam, min_marker_size_px, ss);

@@ -80,7 +80,6 @@ struct Workspace {
     u32* fstat;        // [maxb][8]  0: area popcount, 1: ambiguous ncc pixels, 2: status
     unsigned char* lat_scratch = nullptr;   // [VBS_LAT_MAXN][stage_lat_scratch()] what the workgroups of a frame share; null = path not available
     int lat_slots = 0;              // frames lat_scratch holds (min(max_batch, VBS_LAT_MAXN), fewer for very large frames)
-    bool pass_cleared = false;      // detect_pass cleared the labelling headers / flags of this pass together with fstat
 };
 
 struct vbs_handle {
@@ -109,11 +108,11 @@ struct vbs_handle {
     // ---- options (vbs_set_option) ----
     int blur_impl = 0;              // VBS_OPT_BLUR_IMPL: 0 k_blur16 where it applies, 1 always k_blur_mfma
     int pass_streams = 2;           // VBS_OPT_PASS_STREAMS
-    int stage_impl = 0;             // VBS_OPT_STAGE_IMPL: 0 fused k_stage, 1 the round-2 kernels (k_morph + k_ccl), 2 k_label for every frame, 3 / 4 fused at 768 / 256 threads
+    int stage_impl = 0;             // VBS_OPT_STAGE_IMPL, 0..4: read and documented by label_plan (labelling.hip)
     int gray_bits = 15;             // VBS_OPT_GRAY_COEFFS, the BGR2GRAY fixed-point coefficient set: 15 (OpenCV 4) | 14 (OpenCV <= 3.4.1)
     bool force_seq_match = false;   // VBS_OPT_FORCE_SEQ_MATCH
     int ncc_margin_ppm = 0;         // VBS_OPT_NCC_MARGIN: test hook, widens the float32 filter's margin
-    int lat_frames = 24;            // VBS_OPT_LATENCY_FRAMES: passes of <= this many frames take k_stage_lat (0: never)
+    int lat_frames = 24;            // VBS_OPT_LATENCY_FRAMES: passes of <= this many frames take k_stage_lat (0: never); label_plan
     // dynamic LDS declared (hipFuncSetAttribute) for k_stage / k_ccl<0|1> / k_stage_lat through this handle
     size_t stage_lds_set[2] = {0, 0}, ccl_lds_set[2] = {0, 0}, lat_lds_set = 0;
     // ---- per-pass workspaces ----
@@ -166,7 +165,21 @@ void launch_ncc(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, double* ncc_ou
 void launch_points(int which, const double* in, int n, const vbs_camera& cam, double* out, int32_t* ok,
                    hipStream_t s);
 void launch_threshold(vbs_handle* h, Workspace& w, const u8* mask, const u8* area, int nb, hipStream_t s);
-void launch_labelling(vbs_handle* h, Workspace& w, int nb, hipStream_t s);    // band / open planes, their components and sums (a9 - a12)
+// Labelling (a9 - a12: band / open planes, their components and sums).  How a pass does it is decided ONCE, by label_plan
+// (labelling.hip); clear_pass (api.hip) and launch_labelling take that plan, so what is cleared and what runs cannot disagree.
+enum LabelRoute { LABEL_LAT, LABEL_FUSED, LABEL_CCL, LABEL_GENERAL };     // k_stage_lat | k_stage | k_morph + k_ccl | k_label<0> for every frame
+// stage_threads: k_stage's threads per frame (LABEL_LAT / LABEL_FUSED); few: at most VBS_OPT_LATENCY_FRAMES frames, whatever the route
+struct LabelPlan { LabelRoute route; int stage_threads; bool few; };
+LabelPlan label_plan(const vbs_handle* h, const Workspace& w, int nb);
+// The caller has run clear_pass with THIS plan for this workspace on this stream: no launcher below clears anything.
+void launch_labelling(vbs_handle* h, Workspace& w, int nb, const LabelPlan& plan, hipStream_t s);
+int stage_threads(const vbs_handle* h, int nb);          // k_stage.hip: 768 or 256
+bool launch_stage_lat(vbs_handle* h, Workspace& w, int nb, hipStream_t s);     // false: not for this pass (geometry, scratch, LDS refused)
+bool launch_stage(vbs_handle* h, Workspace& w, int nb, int nt, hipStream_t s);   // false: geometry outside the fused path
+bool launch_ccl(vbs_handle* h, Workspace& w, int nb, hipStream_t s);           // false: geometry outside the round-2 fast path
+void launch_morph(vbs_handle* h, Workspace& w, int nb, const u32* only, hipStream_t s);    // `only`: just the frames flagged there
+struct MorphStrips { int G, strips, rps, wpf; };         // morph_wave's split of a frame: strips per wave, strips, rows per strip, waves
+void launch_label(vbs_handle* h, Workspace& w, int nb, int all, const u32* nslow, const MorphStrips* ms, hipStream_t s);
 void launch_finalize(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, hipStream_t s);
 void launch_track(vbs_handle* h, const double* det, const int32_t* counts32, int nb,
                   const double* ref_xy, int m_ref, double min_dist, float* table, hipStream_t s);
@@ -182,8 +195,6 @@ void launch_assign_ids(vbs_handle* h, const double* det, const int32_t* count, i
                        int32_t* ids_out, double* xy_out, int cap, int32_t* m_out, hipStream_t s);
 void make_contour_lut(u8 out[256]);
 void make_step_lut(u32 out[256]);
-// k_label<0> over EVERY frame of the pass (band_bits / open_bits as they lie in the workspace), nothing else
-void launch_label_all(vbs_handle* h, Workspace& w, int nb, hipStream_t s);
 // k_diameter.hip: blur + inverse threshold of gray frames -> bits [nb][H][WW] (zero_plane, if given, <- 0), and the chain from
 // the bits in w.open_bits (w.band_bits empty) to records, counts and statistics
 void launch_diam_threshold(vbs_handle* h, const u8* gray, int64_t stride_n, int64_t stride_row, int nb, int thr, u64* bits,

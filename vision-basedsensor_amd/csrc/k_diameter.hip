@@ -24,7 +24,7 @@
 
 // Outgoing chain steps of a border pixel of hole-free foreground from its 8-neighbourhood (bit d = neighbour in chain
 // direction d is foreground; 0 = E, 1 = NE, 2 = N, .. 7 = SE, y down): 4 bits per direction, the number of times the outer
-// border leaves the pixel in that direction.  The arcs are those of make_contour_lut (k_label.hip): one visit per maximal arc
+// border leaves the pixel in that direction.  The arcs are those of make_contour_lut (k_morph.hip): one visit per maximal arc
 // of background neighbours that holds a 4-neighbour, leaving to the foreground neighbour that follows the arc.  An isolated
 // pixel (0) and an interior one (255) have no step.
 void make_step_lut(u32 out[256]) {
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(64) void k_diam_stats(const double* __restrict__ re
 // label + measure + circle + statistics of the nb frames whose bits lie in w.open_bits (w.band_bits empty)
 void launch_diam_measure(vbs_handle* h, Workspace& w, int nb, double min_area, double min_circ, double scale, double offset_mm,
                          double* rec, int32_t* counts, double* stats, hipStream_t s) {
-    launch_label_all(h, w, nb, s);
+    launch_label(h, w, nb, 1, nullptr, nullptr, s);      // k_label<0> over EVERY frame, planes as they lie in the workspace
     VBS_LAUNCH(h, s, "k_diam_measure", k_diam_measure, dim3(nb), dim3(CCL_NT), 0, s, w.open_bits, w.wbase, w.node_pos, w.node_comp,
                w.ncomp, w.area_first, w.fstat, h->step_lut, rec, counts, h->H, h->W, h->WW, h->maxm, min_area, min_circ);
     VBS_LAUNCH(h, s, "k_diam_circle", k_diam_circle, dim3(std::min(h->maxm, CCL_OPEN_COMPS), nb), dim3(64), 0, s, w.open_bits,

@@ -1,257 +1,16 @@
-// a9-a13: _marker_center (marker_detection.py:166-249) on bit-packed masks.
-//
-//   k_threshold : uint8 mask / area_mask -> 1 bit per pixel (the HBM-streaming stage: 16 px per lane
-//                 per load, SWAR non-zero test, v_dot4 bit gather, 4 lanes -> one 64-bit word)
-//   k_morph     : band = mask & ~erode_ns(mask)   (maximum/minimum_filter :171-174, window -ns/2..ns/2-1,
-//                 pixels outside the image ignored == scipy 'reflect' for a min/max filter)
-//                 open = dilate5(erode5(area))    (cv2.morphologyEx MORPH_OPEN 5x5 :195)
+// a11 / a12: the general labelling kernel (marker_detection.py:176-196 on bit-packed planes), behind every faster route.
 //   k_label     : one workgroup per (frame, mask): runs of 1-bits are the union-find nodes, parents
 //                 live in LDS, unions between adjacent rows with LDS atomicMin; the root of a
 //                 component is its first run in raster order, so component ids come out in
 //                 ndimage.label order (:176) and reversed they are cv2.findContours' order (:196).
 //                 band mask (4-connectivity): count / sum x / sum y per component (center_of_mass :181)
 //                 open mask (8-connectivity): integer moments up to order 4 of the CHAIN_APPROX_SIMPLE
-//                 contour vertices, classified per border pixel from its 8-neighbourhood by a LUT.
-//   k_finalize  : per frame: centroids, fitEllipse (:208) from the vertex moments via two normal-
-//                 equation solves in float64, then the sequential contour <-> centre matching (:203-243).
+//                 contour vertices, classified per border pixel from its 8-neighbourhood by a LUT (make_contour_lut).
 #include <algorithm>
 #include <cstdlib>
 
-#include "ccl_common.h"
+#include "morph_wave.h"
 
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 nz4(u32 x) {       // 4 bytes -> 4 bits (byte != 0)
-    u32 t = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) >> 7;
-    return __builtin_amdgcn_udot4(t & 0x01010101u, 0x08040201u, 0u, false);
-}
-
-__device__ __forceinline__ u32 nz16(uint4 v) {
-    return nz4(v.x) | (nz4(v.y) << 4) | (nz4(v.z) << 8) | (nz4(v.w) << 12);
-}
-
-__global__ __launch_bounds__(256) void k_threshold(const u8* __restrict__ mask,
-                                                   const u8* __restrict__ area,
-                                                   u64* __restrict__ mbits, u64* __restrict__ abits,
-                                                   int nb, int H, int W, int P, int WW, int vec_ok) {
-    // frames are folded into one index space so that every wave is full; no early return because
-    // the 4-lane word assembly below shuffles across lanes.
-    const int per_row = P / 16;
-    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = gid < (int64_t)nb * H * per_row;
-    int n = 0, y = 0, t = 0;
-    if (live) {
-        n = (int)(gid / ((int64_t)H * per_row));
-        int64_t r = gid - (int64_t)n * H * per_row;
-        y = (int)(r / per_row);
-        t = (int)(r - (int64_t)y * per_row);
-    }
-    const int x0 = t * 16;
-    u32 bm = 0, ba = 0;
-    if (live && x0 < W) {
-        int64_t off = ((int64_t)n * H + y) * W + x0;
-        if (vec_ok && x0 + 16 <= W) {
-            bm = nz16(*reinterpret_cast<const uint4*>(mask + off));
-            ba = nz16(*reinterpret_cast<const uint4*>(area + off));
-        } else {
-            for (int k = 0; k < 16 && x0 + k < W; ++k) {
-                bm |= (u32)(mask[off + k] != 0) << k;
-                ba |= (u32)(area[off + k] != 0) << k;
-            }
-        }
-    }
-    u64 wm = (u64)bm | ((u64)__shfl_down(bm, 1) << 16) | ((u64)__shfl_down(bm, 2) << 32) |
-             ((u64)__shfl_down(bm, 3) << 48);
-    u64 wa = (u64)ba | ((u64)__shfl_down(ba, 1) << 16) | ((u64)__shfl_down(ba, 2) << 32) |
-             ((u64)__shfl_down(ba, 3) << 48);
-    if (live && (t & 3) == 0) {
-        int64_t o = ((int64_t)n * H + y) * WW + (t >> 2);
-        mbits[o] = wm;
-        abits[o] = wa;
-    }
-}
-
-void launch_threshold(vbs_handle* h, Workspace& w, const u8* mask, const u8* area, int nb, hipStream_t s) {
-    int64_t total = (int64_t)nb * h->H * (h->P / 16);
-    int vec_ok = (h->W % 16 == 0) && (((uintptr_t)mask | (uintptr_t)area) % 16 == 0);
-    VBS_LAUNCH(h, s, "k_threshold", k_threshold, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mask, area,
-                       w.mask_bits, w.area_bits, nb, h->H, h->W, h->P, h->WW, vec_ok);
-}
-
-// ------------------------------------------------------------------------------------------------
-// horizontal window AND / OR of one row word over dx in [lo, hi] (lo <= 0 <= hi, hi - lo < 64) given its left / right
-// neighbour words.  The 128 bits from position lo on are combined with themselves shifted by 1, 2, 4, ... (AND and OR
-// are idempotent, so the last shift may overlap): log2(window) steps instead of one per offset.
-template <bool ERODE>
-__device__ __forceinline__ u64 hmorph(u64 wl, u64 wc, u64 wr, int lo, int hi) {
-    const int pre = -lo, n = hi - lo + 1;               // bit p of (ulo, uhi) = pixel p - pre
-    u64 ulo = pre ? ((wl >> (64 - pre)) | (wc << pre)) : wc;
-    u64 uhi = pre ? ((wc >> (64 - pre)) | (wr << pre)) : wr;
-    int have = 1;
-    while (have < n) {
-        const int s = min(have, n - have);
-        const u64 slo = (ulo >> s) | (uhi << (64 - s)), shi = uhi >> s;      // (positions past the 128 bits are never used)
-        ulo = ERODE ? (ulo & slo) : (ulo | slo);
-        uhi = ERODE ? (uhi & shi) : (uhi | shi);
-        have += s;
-    }
-    return ulo;                                          // bit i = AND / OR of pixels i + lo .. i + hi
-}
-
-// band = mask & ~erode_ns(mask) and open = dilate5(erode5(area)), separably, as a stream down the image:
-// a wave holds G = 64 / WW strips of rows side by side (lane = strip * WW + word column) and takes one image row per
-// step; the horizontal passes get their neighbour words by DPP lane shifts, the vertical passes are delay lines in
-// registers (the ns-row AND by doubling: 2, 4, 8, ns rows).  No LDS, no barrier; a strip re-reads only the ns - 1 rows
-// above / below it.  (The first version staged 32-row tiles in LDS behind four barriers: 0.31 us per 1280x1024 frame.)
-// Outside the image erosion sees 1s (pixels ignored), dilation sees 0s - scipy 'reflect' / cv2's default border.
-// one wave: the G strips `wv` G .. of frame n
-template <int NS14>                                      // ns = 14 (large frames) or 8 (small)
-__device__ __forceinline__ void morph_wave(const u64* __restrict__ mbits, const u64* __restrict__ abits,
-                                           u64* __restrict__ band, u64* __restrict__ opn, int H, int W, int WW, int G, int strips,
-                                           int rows_per_strip, int n, int wv) {
-    const int lane = threadIdx.x & 63;
-    const int sidx = wv * G + lane / WW, j = lane % WW;
-    const bool act = lane < G * WW && sidx < strips;
-    const int ra = min(sidx * rows_per_strip, H), rb = min(ra + rows_per_strip, H);
-    const int64_t fo = (int64_t)n * H * WW;
-    const u64* M = mbits + fo;
-    const u64* A = abits + fo;
-    const u64 vm = valid_mask(j, W);
-    const bool hasl = j > 0, hasr = j + 1 < WW;
-    constexpr int LO = -(NS14 / 2), HI = NS14 / 2 - 1;    // window rows / columns y + LO .. y + HI
-    // every lane runs the same number of steps (DPP moves need all lanes): the longest strip of the wave
-    // input rows ra + LO .. : the band row yb needs rows up to yb + HI, the opened row yo rows up to yo + 4
-    const int nsteps = rows_per_strip + (NS14 - 1 > 4 - LO ? NS14 - 1 : 4 - LO);
-    // delay lines (index 0 = newest)
-    u64 h1 = ~0ull, a2[2] = {~0ull, ~0ull}, a4[4] = {~0ull, ~0ull, ~0ull, ~0ull}, a8[6] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};
-    u64 e5[4] = {~0ull, ~0ull, ~0ull, ~0ull}, d5[4] = {0, 0, 0, 0};
-    // rows are loaded three steps ahead of their use (nothing else hides the load latency: there is no other work between
-    // two steps of a wave)
-    auto ld = [&](const u64* src, int row, bool ok) { return (ok && row >= 0 && row < H) ? src[(int64_t)row * WW + j] : 0ull; };
-    auto ldc = [&](int row) { return (act && row >= ra && row < rb) ? M[(int64_t)row * WW + j] : 0ull; };
-    const int tb = ra + LO;
-    u64 mq0 = ld(M, tb, act), mq1 = ld(M, tb + 1, act), mq2 = ld(M, tb + 2, act);
-    u64 aq0 = ld(A, tb, act), aq1 = ld(A, tb + 1, act), aq2 = ld(A, tb + 2, act);
-    u64 cq0 = ldc(tb - HI), cq1 = ldc(tb + 1 - HI), cq2 = ldc(tb + 2 - HI);
-    for (int k = 0; k < nsteps; ++k) {
-        const int t = tb + k;                            // input row of this step
-        const bool tin = act && t >= 0 && t < H;
-        const u64 mw = mq0, aw = aq0, mc = cq0;
-        mq0 = mq1; mq1 = mq2; mq2 = ld(M, t + 3, act);
-        aq0 = aq1; aq1 = aq2; aq2 = ld(A, t + 3, act);
-        cq0 = cq1; cq1 = cq2; cq2 = ldc(t + 3 - HI);
-        const int yb = t - HI;                           // band row completed by this step (window yb + LO .. yb + HI = t)
-        const bool bout = act && yb >= ra && yb < rb;
-        // ---- horizontal erosions (neighbour words by lane shift; rows outside the image are all ones) ----
-        u64 hm, ha;
-        {
-            const u64 wc = tin ? (mw | ~vm) : ~0ull, wl_ = dpp_shr1(wc), wr_ = dpp_shl1(wc);
-            hm = hmorph<true>(hasl ? wl_ : ~0ull, wc, hasr ? wr_ : ~0ull, LO, HI);
-            const u64 ac = tin ? (aw | ~vm) : ~0ull, al_ = dpp_shr1(ac), ar_ = dpp_shl1(ac);
-            ha = hmorph<true>(hasl ? al_ : ~0ull, ac, hasr ? ar_ : ~0ull, -2, 2);
-        }
-        // ---- vertical erosion over NS14 rows by doubling: a2[t-1], a4[t-3], a8[t-7], then rows t-NS14+1 .. t ----
-        u64 e14;
-        {
-            const u64 n2 = h1 & hm;                      // rows t-1, t
-            const u64 n4 = a2[1] & n2;                   // rows t-3 .. t      (a2[1] = rows t-3, t-2)
-            if (NS14 == 14) {
-                const u64 n8 = a4[3] & n4;               // rows t-7 .. t      (a4[3] = rows t-7 .. t-4)
-                e14 = a8[5] & n8;                        // rows t-13 .. t     (a8[5] = rows t-13 .. t-6)
-                a8[5] = a8[4]; a8[4] = a8[3]; a8[3] = a8[2]; a8[2] = a8[1]; a8[1] = a8[0]; a8[0] = n8;
-            } else {
-                e14 = a4[3] & n4;                        // ns = 8: rows t-7 .. t
-            }
-            a4[3] = a4[2]; a4[2] = a4[1]; a4[1] = a4[0]; a4[0] = n4;
-            a2[1] = a2[0]; a2[0] = n2;
-            h1 = hm;
-        }
-        if (bout) band[fo + (int64_t)yb * WW + j] = mc & ~e14 & vm;
-        // ---- open: vertical erosion over 5 rows -> row t-2 (0 outside the image), horizontal dilation, vertical
-        //      dilation over 5 rows -> row t-4 ----
-        {
-            const int ye = t - 2;
-            u64 ve = ha & e5[0] & e5[1] & e5[2] & e5[3];
-            e5[3] = e5[2]; e5[2] = e5[1]; e5[1] = e5[0]; e5[0] = ha;
-            ve = (act && ye >= 0 && ye < H) ? (ve & vm) : 0ull;
-            const u64 vl_ = dpp_shr1(ve), vr_ = dpp_shl1(ve);
-            const u64 hd = hmorph<false>(hasl ? vl_ : 0ull, ve, hasr ? vr_ : 0ull, -2, 2);
-            const u64 o = hd | d5[0] | d5[1] | d5[2] | d5[3];
-            d5[3] = d5[2]; d5[2] = d5[1]; d5[1] = d5[0]; d5[0] = hd;
-            const int yo = t - 4;
-            if (act && yo >= ra && yo < rb) opn[fo + (int64_t)yo * WW + j] = o & vm;
-        }
-    }
-}
-
-template <int NS14>
-__global__ __launch_bounds__(256) void k_morph(const u64* __restrict__ mbits, const u64* __restrict__ abits,
-                                               u64* __restrict__ band, u64* __restrict__ opn, const u32* __restrict__ only,
-                                               const u32* __restrict__ nslow,
-                                               int nb, int H, int W, int WW, int G, int strips, int rows_per_strip,
-                                               int waves_per_frame) {
-    if (nslow && *nslow == 0) return;                    // the fused kernel handed no frame on
-    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int n = gw / waves_per_frame;
-    if (n >= nb || (only && !only[n])) return;           // wave-uniform (`only`: just the frames the fused path handed on)
-    morph_wave<NS14>(mbits, abits, band, opn, H, W, WW, G, strips, rows_per_strip, n, gw - n * waves_per_frame);
-}
-
-static void launch_morph(vbs_handle* h, Workspace& w, int nb, const u32* only, hipStream_t s) {
-    const int G = 64 / h->WW;                            // strips per wave (WW <= 64)
-    // strips per frame: enough waves to fill the chip several times over, but strips much longer than the ns - 1 rows
-    // each re-reads
-    // one round of resident waves when the batch is large (94 / 78 VGPRs: 5 / 6 waves per SIMD on 1024 SIMDs; with 6144
-    // waves the large branch ran a full round and then a 20 % one), else as many as the strip length allows
-    const int resident = (h->bp.ns == 14 ? 5 : 6) * 1024;
-    int wpf = resident / std::max(nb, 1);
-    if (wpf < 4) wpf = (2 * resident + nb - 1) / nb;     // small strips would dominate: take two rounds instead
-    if (VBS_KNOB("VBS_MORPH_WPF")) wpf = VBS_KNOB("VBS_MORPH_WPF");
-    wpf = std::max(1, std::min(wpf, h->H / (2 * h->bp.ns) / G));      // strips of at least 2 ns rows
-    const int strips = wpf * G, rps = (h->H + strips - 1) / strips;
-    const int waves = nb * wpf;
-    dim3 grid((waves + 3) / 4);
-    if (h->bp.ns == 14)
-        VBS_LAUNCH(h, s, "k_morph", k_morph<14>, grid, dim3(256), 0, s, w.mask_bits, w.area_bits, w.band_bits, w.open_bits,
-                   only, only ? w.slow_total : nullptr, nb, h->H, h->W, h->WW, G, strips, rps, wpf);
-    else
-        VBS_LAUNCH(h, s, "k_morph", k_morph<8>, grid, dim3(256), 0, s, w.mask_bits, w.area_bits, w.band_bits, w.open_bits,
-                   only, only ? w.slow_total : nullptr, nb, h->H, h->W, h->WW, G, strips, rps, wpf);
-}
-
-// ------------------------------------------------------------------------------------------------
-// CHAIN_APPROX_SIMPLE vertex multiplicity of a border pixel from its 8-neighbourhood (bit d = neighbour
-// in chain direction d is foreground).  The outer border visits the pixel once per maximal arc of
-// background neighbours that contains a 4-neighbour (an arc made of one diagonal pixel is stepped
-// over diagonally); arriving from the foreground neighbour that precedes the arc and leaving to the
-// one that follows it, the point is kept iff the two step directions differ.
-void make_contour_lut(u8 out[256]) {
-    for (int p = 0; p < 256; ++p) {
-        int cnt = 0;
-        if (p == 0) {
-            cnt = 1;                                     // isolated pixel: written once
-        } else if (p != 255) {
-            for (int a = 0; a < 8; ++a) {
-                // arc starts at direction a: a is background, a-1 is foreground
-                if (((p >> a) & 1) || !((p >> ((a + 7) & 7)) & 1)) continue;
-                int b = a;
-                bool has4 = false;
-                while (!((p >> (b & 7)) & 1)) {
-                    if (((b & 7) & 1) == 0) has4 = true;
-                    ++b;
-                }
-                if (!has4) continue;
-                int q = (a + 7) & 7;                      // neighbour before the arc
-                int r = b & 7;                            // neighbour after the arc
-                int dir_in = (q + 4) & 7;                 // step q -> p
-                int dir_out = r;                          // step p -> r
-                if (dir_in != dir_out) ++cnt;
-            }
-        }
-        out[p] = (u8)cnt;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // find with path halving.  Parents only ever move to a smaller-indexed member of the same set (hooking is an
 // atomicMin on a root, halving stores an ancestor), so the racy 32-bit stores are benign: a lost hook is
 // re-established by uf_union's retry with the value atomicMin returned.
@@ -881,439 +640,13 @@ __global__ __launch_bounds__(1024) void k_label(u64* band_bits,
     }                                                   // frames
 }
 
-bool launch_ccl(vbs_handle* h, Workspace& w, int nb, hipStream_t s);   // false: geometry outside the round-2 fast path
-bool launch_stage(vbs_handle* h, Workspace& w, int nb, hipStream_t s);  // false: geometry outside the fused path
-bool launch_stage_lat(vbs_handle* h, Workspace& w, int nb, hipStream_t s);   // k_stage_lat.hip; false: not for this pass
-
-// a9-a12: band / opened planes, labelling, per-component sums.  The fused kernel (k_stage.hip) takes the pass; k_morph and
-// the general kernel then run over the frames it handed on (none on marker frames: their waves / workgroups find no
-// flagged frame and exit).  Geometries outside the fused path - and VBS_OPT_STAGE_IMPL = 1 - take the round-2 kernels:
-// k_morph over every frame, k_ccl<0|1>, the general kernel over what those hand on.
-void launch_labelling(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
-    // a pass of a few frames (MarkerTracker.process: ONE) spreads each frame over several workgroups: k_stage_lat.hip
-    const bool fused = h->stage_impl == 0 || h->stage_impl >= 3;
-    const bool lat = fused && nb <= h->lat_frames && nb <= w.lat_slots;
-    if (w.pass_cleared) w.pass_cleared = false;          // (detect_pass cleared them with the frame statistics: one launch less)
-    else if (lat) launch_fill(w.lat_hdr, 0u, (size_t)VBS_LAT_MAXN * VBS_LAT_HDR + nb + 4, s);     // its headers, the counter and the flags
-    else launch_fill(w.slow_total, 0u, (size_t)nb + 4, s);                        // the counter and the flags
-    int all = 0;
-    const u32* nslow = nullptr;
-    if (lat && launch_stage_lat(h, w, nb, s)) {
-        // what it hands on: planes and labels by ONE more kernel (k_label<ns> makes the planes itself); no frame on marker frames
-        const int G = 64 / h->WW, wpf = std::max(1, std::min(64, h->H / (2 * h->bp.ns) / G));
-        const int strips = wpf * G, rps = (h->H + strips - 1) / strips;
-#define LABEL_M(NS_)                                                                                                              \
-        VBS_LAUNCH(h, s, "k_label", k_label<NS_>, dim3(nb), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase, w.node_pos,      \
-                   w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat, h->lut, w.slow_flag,      \
-                   w.slow_total, w.probe, nb, 0, h->H, h->W, h->WW, h->maxm, 0, w.mask_bits, w.area_bits, G, strips, rps, wpf)
-        if (h->bp.ns == 14) LABEL_M(14); else LABEL_M(8);
-#undef LABEL_M
-        return;
-    }
-    if (fused && launch_stage(h, w, nb, s)) {
-        launch_morph(h, w, nb, w.slow_flag, s);
-        nslow = w.slow_total;
-    } else {
-        launch_morph(h, w, nb, nullptr, s);
-        all = (h->stage_impl != 2 && launch_ccl(h, w, nb, s)) ? 0 : 1;      // (2: the general kernel labels EVERY frame - its rate, tests)
-    }
-    VBS_LAUNCH(h, s, "k_label", k_label<0>, dim3(nb < 64 ? nb : 64), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase,
-               w.node_pos, w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat,
-               h->lut, w.slow_flag, nslow, w.probe, nb, all, h->H, h->W, h->WW, h->maxm, VBS_KNOB("VBS_LABEL_STOP"),
-               (const u64*)nullptr, (const u64*)nullptr, 0, 0, 0, 0);
-}
-
-// ------------------------------------------------------------------------------------------------
-// fitEllipse from vertex moments (see oracle/stages.py:fit_ellipse for the algorithm being followed)
-// Gaussian elimination with partial pivoting, fully unrolled: the row swap is a chain of predicated exchanges instead of
-// a run-time row index, so the system stays in registers (indexed by a run-time pivot row it lived in scratch memory:
-// 288 bytes per lane).  Same operations in the same order as the rolled form.
-template <int N>
-__device__ __forceinline__ bool solve_sym(double (&A)[N * N], double (&b)[N]) {
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        int p = c;
-        double best = fabs(A[c * N + c]);
-#pragma unroll
-        for (int r = c + 1; r < N; ++r)
-            if (fabs(A[r * N + c]) > best) { best = fabs(A[r * N + c]); p = r; }
-        if (!(best > 1e-300)) return false;
-#pragma unroll
-        for (int r = c + 1; r < N; ++r) {
-            if (p == r) {
-#pragma unroll
-                for (int k = 0; k < N; ++k) { const double t = A[c * N + k]; A[c * N + k] = A[r * N + k]; A[r * N + k] = t; }
-                const double t = b[c]; b[c] = b[r]; b[r] = t;
-            }
-        }
-#pragma unroll
-        for (int r = c + 1; r < N; ++r) {
-            const double f = A[r * N + c] / A[c * N + c];
-#pragma unroll
-            for (int k = c; k < N; ++k) A[r * N + k] -= f * A[c * N + k];
-            b[r] -= f * b[c];
-        }
-    }
-#pragma unroll
-    for (int c = N - 1; c >= 0; --c) {
-        double v = b[c];
-#pragma unroll
-        for (int k = c + 1; k < N; ++k) v -= A[c * N + k] * b[k];
-        b[c] = v / A[c * N + c];
-    }
-    return true;
-}
-
-// m[a][b] (a+b<=4) about a point shifted by (sx, sy): sum (x-sx)^a (y-sy)^b
-__device__ __forceinline__ void shift_moments(const double (&in)[5][5], double sx, double sy, double (&out)[5][5]) {
-    const double C[5][5] = {{1, 0, 0, 0, 0}, {1, 1, 0, 0, 0}, {1, 2, 1, 0, 0}, {1, 3, 3, 1, 0}, {1, 4, 6, 4, 1}};
-    const double px[5] = {1, -sx, sx * sx, -sx * sx * sx, sx * sx * sx * sx};
-    const double py[5] = {1, -sy, sy * sy, -sy * sy * sy, sy * sy * sy * sy};
-    // (every loop has constant bounds and is unrolled: the tables stay in registers)
-#pragma unroll
-    for (int a = 0; a <= 4; ++a)
-#pragma unroll
-        for (int b = 0; b <= 4; ++b) {
-            if (a + b > 4) continue;
-            double v = 0;
-#pragma unroll
-            for (int i = 0; i <= 4; ++i)
-#pragma unroll
-                for (int j = 0; j <= 4; ++j)
-                    if (i <= a && j <= b) v += C[a][i] * C[b][j] * px[a - i] * py[b - j] * in[i][j];
-            out[a][b] = v;
-        }
-}
-
-// out: cx, cy, w, h, angle (float32-rounded, w <= h), nvert, ok
-__device__ void fit_ellipse_moments(const i64* S, int ax, int ay, double* out) {
-    const double PI = 3.14159265358979323846;
-    double n = (double)S[0];
-    out[5] = n;
-    out[6] = 0.0;
-    if (S[0] < 5) return;
-    // float32 mean of the absolute coordinates, like Point2f accumulation in cv2
-    float cx32 = (float)((double)S[0] * ax + (double)S[1]) / (float)n;
-    float cy32 = (float)((double)S[0] * ay + (double)S[2]) / (float)n;
-    double M0[5][5] = {{0}}, M[5][5];
-    M0[0][0] = (double)S[0];
-    M0[1][0] = (double)S[1];  M0[0][1] = (double)S[2];
-    M0[2][0] = (double)S[3];  M0[1][1] = (double)S[4];  M0[0][2] = (double)S[5];
-    M0[3][0] = (double)S[6];  M0[2][1] = (double)S[7];  M0[1][2] = (double)S[8];  M0[0][3] = (double)S[9];
-    M0[4][0] = (double)S[10]; M0[3][1] = (double)S[11]; M0[2][2] = (double)S[12]; M0[1][3] = (double)S[13];
-    M0[0][4] = (double)S[14];
-    shift_moments(M0, (double)cx32 - ax, (double)cy32 - ay, M);
-    double r2 = (M[2][0] + M[0][2]) / n;
-    if (!(r2 > 0.0)) return;
-    double scale = 100.0 / (n * sqrt(r2) * 1.2732395447351628);
-    double sp[5] = {1, scale, scale * scale, scale * scale * scale, scale * scale * scale * scale};
-    double m[5][5];
-#pragma unroll
-    for (int a = 0; a <= 4; ++a)
-#pragma unroll
-        for (int b = 0; b <= 4; ++b)
-            if (a + b <= 4) m[a][b] = M[a][b] * sp[a + b];
-    double A[25] = {
-        m[4][0],  m[2][2],  m[3][1],  -m[3][0], -m[2][1],
-        m[2][2],  m[0][4],  m[1][3],  -m[1][2], -m[0][3],
-        m[3][1],  m[1][3],  m[2][2],  -m[2][1], -m[1][2],
-        -m[3][0], -m[1][2], -m[2][1], m[2][0],  m[1][1],
-        -m[2][1], -m[0][3], -m[1][2], m[1][1],  m[0][2]};
-    double g[5] = {-1e4 * m[2][0], -1e4 * m[0][2], -1e4 * m[1][1], 1e4 * m[1][0], 1e4 * m[0][1]};
-    // conditioning guard, in the spirit of cv2's singular-value test (w[0]*FLT_EPSILON > w[4])
-    double tr = A[0] + A[6] + A[12] + A[18] + A[24];
-    if (!solve_sym<5>(A, g)) return;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) if (!isfinite(g[i])) return;
-    (void)tr;
-    double det = 4.0 * g[0] * g[1] - g[2] * g[2];
-    if (!(fabs(det) > 1e-300)) return;
-    double rp0 = (2.0 * g[1] * g[3] - g[2] * g[4]) / det;
-    double rp1 = (2.0 * g[0] * g[4] - g[2] * g[3]) / det;
-    double mu[5][5];
-    shift_moments(m, rp0, rp1, mu);
-    double A3[9] = {mu[4][0], mu[2][2], mu[3][1], mu[2][2], mu[0][4], mu[1][3], mu[3][1], mu[1][3], mu[2][2]};
-    double g3[3] = {mu[2][0], mu[0][2], mu[1][1]};
-    if (!solve_sym<3>(A3, g3)) return;
-    const double min_eps = 1e-8;
-    double ang = -0.5 * atan2(g3[2], g3[1] - g3[0]);
-    double t;
-    if (fabs(g3[2]) > min_eps) t = g3[2] / sin(-2.0 * ang);
-    else t = g3[1] - g3[0];
-    double r_2 = fabs(g3[0] + g3[1] - t);
-    if (r_2 > min_eps) r_2 = sqrt(2.0 / r_2);
-    double r_3 = fabs(g3[0] + g3[1] + t);
-    if (r_3 > min_eps) r_3 = sqrt(2.0 / r_3);
-    float ecx = (float)(rp0 / scale) + cx32;
-    float ecy = (float)(rp1 / scale) + cy32;
-    float wd = (float)(r_2 * 2.0 / scale);
-    float ht = (float)(r_3 * 2.0 / scale);
-    float fang = (float)(ang * 180.0 / PI);
-    if (wd > ht) {
-        float tt = wd; wd = ht; ht = tt;
-        fang = (float)(90.0 + ang * 180.0 / PI);
-    }
-    if (fang < -180.f) fang += 360.f;
-    if (fang > 360.f) fang -= 360.f;
-    if (!(isfinite(wd) && isfinite(ht) && isfinite(ecx) && isfinite(ecy))) return;
-    out[0] = ecx; out[1] = ecy; out[2] = wd; out[3] = ht; out[4] = fang;
-    out[6] = 1.0;
-}
-
-// cv2.pointPolygonTest(contour, pt, False) >= 0 for the outer border polygon of component cid, decided from the 2x2
-// pixel cell around the (float32-rounded) point; pr = component ids of the cell's pixels (x, y), (x+1, y), (x, y+1),
-// (x+1, y+1) as left by k_ccl / k_probe_slow (0xFFFF = background or outside the image).
-__device__ bool inside_polygon(const unsigned short* __restrict__ pr, double px, double py, u32 cid) {
-    const float xf = (float)px, yf = (float)py;
-    const float fx = xf - floorf(xf), fy = yf - floorf(yf);
-    const bool c00 = pr[0] == cid;
-    if (fx == 0.f && fy == 0.f) return c00;
-    if (fy == 0.f) return c00 && pr[1] == cid;
-    if (fx == 0.f) return c00 && pr[2] == cid;
-    const bool c10 = pr[1] == cid, c01 = pr[2] == cid, c11 = pr[3] == cid;
-    const int cnt = (int)c00 + c10 + c01 + c11;
-    if (cnt == 4) return true;
-    if (cnt == 3) {
-        if (!c11) return fx + fy <= 1.f;
-        if (!c00) return fx + fy >= 1.f;
-        if (!c10) return fy >= fx;
-        return fx >= fy;
-    }
-    if (cnt == 2) {
-        if (c00 && c11) return fx == fy;
-        if (c10 && c01) return fx + fy == 1.f;
-    }
-    return false;
-}
-
-// frame n, by one workgroup of 256 threads
-__device__ __forceinline__ void finalize_frame(int n, const u32* __restrict__ ncomp_all,
-                                               const u64* __restrict__ band_sums,
-                                               const u32* __restrict__ area_first,
-                                               const i64* __restrict__ area_sums,
-                                               const unsigned short* __restrict__ probe_all,
-                                               const u32* __restrict__ fstat, double* __restrict__ ell_all,
-                                               double* __restrict__ det64, int32_t* __restrict__ cnt64,
-                                               double* __restrict__ det32, int32_t* __restrict__ cnt32,
-                                               int H, int W, int WW, int maxm, int stop, int force_seq) {
-    __shared__ double bx[1024], by[1024];
-    __shared__ u8 unmatched[1024];
-    __shared__ int claim[1024], wsum[4];
-    // per opened component (at most CCL_OPEN_COMPS = 512 of them: k_stage, k_stage_lat and k_label all stop there)
-    __shared__ int best_of[CCL_OPEN_COMPS];
-    __shared__ double thr_s[CCL_OPEN_COMPS], ecx_s[CCL_OPEN_COMPS], ecy_s[CCL_OPEN_COMPS];   // (:219) threshold, ellipse centre
-    __shared__ u64 best_d[CCL_OPEN_COMPS];
-    __shared__ int dup_s;
-    const int tid = threadIdx.x;
-    int status = (int)fstat[n * 8 + 2];
-    if (status != 0) {
-        if (tid == 0) { cnt64[n] = status; if (cnt32) cnt32[n] = status; }
-        return;
-    }
-    const int nb_ = min((int)ncomp_all[n * 2 + 0], 1024), na = min((int)ncomp_all[n * 2 + 1], CCL_OPEN_COMPS);   // (never past the tables)
-    const u64* bs = band_sums + (int64_t)n * maxm * 4;
-    for (int i = tid; i < nb_; i += blockDim.x) {
-        double c = (double)bs[i * 4 + 0];
-        bx[i] = (double)bs[i * 4 + 1] / c;             // center_of_mass: integer sums, one division
-        by[i] = (double)bs[i * 4 + 2] / c;
-        unmatched[i] = 1;
-    }
-    double* ell = ell_all + (int64_t)n * maxm * 8;
-    const u32* af = area_first + (int64_t)n * maxm;
-    for (int i = tid; i < na; i += blockDim.x) {
-        u32 fp = af[i];
-        fit_ellipse_moments(area_sums + ((int64_t)n * maxm + i) * VBS_AREA_SUMS, fp % W, fp / W, ell + i * 8);
-    }
-    __syncthreads();
-    if (stop == 1) return;
-    const unsigned short* probe = probe_all + (int64_t)n * maxm * 4;
-    double* d64 = det64 + (int64_t)n * maxm * 6;
-    double* d32 = det32 ? det32 + (int64_t)n * maxm * 6 : nullptr;
-
-    // ---- matching (:203-243).  The reference walks the contours in order and gives each the nearest
-    // still-unmatched centre inside it.  Every contour first gets its nearest admissible centre among
-    // ALL centres, in parallel; if no centre is claimed twice, the sequential walk would have made exactly
-    // these choices (a contour loses its first choice only to an earlier contour with the same choice).
-    // Otherwise (never seen on marker frames) one wave replays the reference's sequential loop.
-    // A centre can only lie inside the polygon of a component that owns a pixel of the 2x2 cell around it (every
-    // accepting branch of inside_polygon needs one), so the search runs from the centres: a thread per centre tries the
-    // at most four components of its probe cell, and a contour keeps the smallest (distance, index) offered to it - the
-    // order the reference's strict "<" over ascending indices produces - through two LDS atomic minima: the distance's
-    // bit pattern (monotone for non-negative doubles), then the index among the centres at that distance.
-    for (int i = tid; i < nb_; i += blockDim.x) claim[i] = 0;
-    for (int c = tid; c < na; c += blockDim.x) {
-        const double* e = ell + c * 8;
-        double thr = -1.0;
-        if (e[6] != 0.0 && e[5] >= 5.0) {               // len(contour) >= 5 (:204) and a valid fit
-            const double w = e[2], hh = e[3], minor = (w > hh) ? hh : w;
-            if (!(minor < 5.0)) thr = (minor / 10.0) * (minor / 10.0);     // (:219)
-        }
-        thr_s[c] = thr;
-        ecx_s[c] = e[0]; ecy_s[c] = e[1];               // (the matching below reads the centres a few times: not from memory)
-        best_d[c] = ~0ull;
-        best_of[c] = 0x7FFFFFFF;
-    }
-    if (tid == 0) dup_s = force_seq;
-    __syncthreads();
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int i = tid; i < nb_; i += blockDim.x) {
-            const unsigned short* pr = probe + i * 4;
-            const double cx = bx[i], cy = by[i];
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const u32 cid = pr[q4];
-                if (cid >= (u32)na) continue;
-                bool seen = false;
-#pragma unroll
-                for (int q5 = 0; q5 < 4; ++q5) seen |= (q5 < q4) && (pr[q5] == cid);
-                if (seen) continue;
-                const double thr = thr_s[cid];
-                if (!(thr >= 0.0)) continue;
-                const double dx = cx - ecx_s[cid], dy = cy - ecy_s[cid], d = dx * dx + dy * dy;
-                if (!(d < thr) || !inside_polygon(pr, cx, cy, cid)) continue;
-                const u64 key = (u64)__double_as_longlong(d);
-                if (pass == 0) atomicMin(&best_d[cid], key);
-                else if (key == best_d[cid]) atomicMin(&best_of[cid], i);
-            }
-        }
-        __syncthreads();
-    }
-    for (int c = tid; c < na; c += blockDim.x) {
-        const int bi = best_of[c] == 0x7FFFFFFF ? -1 : best_of[c];
-        best_of[c] = bi;
-        if (bi >= 0 && atomicAdd(&claim[bi], 1) > 0) dup_s = 1;
-    }
-    __syncthreads();
-    if (!dup_s) {
-        // output order = contour order = descending component id; rank by a block scan over reversed ids
-        const int per = (na + blockDim.x - 1) / blockDim.x;
-        const int r0 = tid * per, r1 = min(r0 + per, na);
-        int mine = 0;
-        for (int r = r0; r < r1; ++r) mine += (best_of[na - 1 - r] >= 0);
-        int inc = mine;
-        const int lane = tid & 63, wave = tid >> 6;
-        for (int d = 1; d < 64; d <<= 1) { int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int base = inc - mine;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
-        for (int r = r0; r < r1; ++r) {
-            int ci = na - 1 - r, bi = best_of[ci];
-            if (bi < 0) continue;
-            const double* e = ell + ci * 8;
-            double w = e[2], hh = e[3], ang = e[4], major, minor, eang;
-            if (w > hh) { major = w; minor = hh; eang = ang; }
-            else { major = hh; minor = w; eang = ang + 90.0; }
-            double* o = d64 + base * 6;
-            o[0] = bx[bi]; o[1] = by[bi]; o[2] = major; o[3] = minor; o[4] = eang; o[5] = bi + 1;
-            if (d32) {
-                double* f = d32 + base * 6;
-                f[0] = bx[bi]; f[1] = by[bi]; f[2] = major; f[3] = minor; f[4] = eang; f[5] = bi + 1;
-            }
-            ++base;
-        }
-        if (tid == (int)blockDim.x - 1) { cnt64[n] = base; if (cnt32) cnt32[n] = base; }
-        return;
-    }
-    if (tid >= 64) return;
-    // ---- sequential replay in cv2 contour order (last component found first), one wave -------------
-    int count = 0;
-    for (int ci = na - 1; ci >= 0; --ci) {
-        const double* e = ell + ci * 8;
-        if (e[6] == 0.0 || e[5] < 5.0) continue;       // len(contour) < 5 (:204) or no fit
-        double ecx = e[0], ecy = e[1], w = e[2], hh = e[3], ang = e[4];
-        double major, minor, eang;
-        if (w > hh) { major = w; minor = hh; eang = ang; }
-        else { major = hh; minor = w; eang = ang + 90.0; }
-        if (minor < 5.0) continue;                      // (:219)
-        double thr = (minor / 10.0) * (minor / 10.0);
-        double best = 1e300;
-        int bi = -1;
-        for (int i = tid; i < nb_; i += 64) {
-            if (!unmatched[i]) continue;
-            double dx = bx[i] - ecx, dy = by[i] - ecy;
-            double d = dx * dx + dy * dy;
-            if (d < thr && d < best &&
-                inside_polygon(probe + i * 4, bx[i], by[i], (u32)ci)) {
-                best = d; bi = i;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            double ob = __shfl_xor(best, off);
-            int oi = __shfl_xor(bi, off);
-            if (oi >= 0 && (bi < 0 || ob < best || (ob == best && oi < bi))) { best = ob; bi = oi; }
-        }
-        if (bi >= 0) {
-            if (tid == 0) {
-                unmatched[bi] = 0;
-                double* o = d64 + count * 6;
-                o[0] = bx[bi]; o[1] = by[bi]; o[2] = major; o[3] = minor; o[4] = eang; o[5] = bi + 1;
-                if (d32) {
-                    double* f = d32 + count * 6;
-                    f[0] = bx[bi]; f[1] = by[bi]; f[2] = major; f[3] = minor; f[4] = eang; f[5] = bi + 1;
-                }
-            }
-            ++count;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (tid == 0) { cnt64[n] = count; if (cnt32) cnt32[n] = count; }
-}
-
-__global__ __launch_bounds__(256) void k_finalize(const u32* __restrict__ ncomp_all, const u64* __restrict__ band_sums,
-                                                  const u32* __restrict__ area_first, const i64* __restrict__ area_sums,
-                                                  const unsigned short* __restrict__ probe_all,
-                                                  const u32* __restrict__ fstat, double* __restrict__ ell_all,
-                                                  double* __restrict__ det64, int32_t* __restrict__ cnt64,
-                                                  double* __restrict__ det32, int32_t* __restrict__ cnt32,
-                                                  int H, int W, int WW, int maxm, int stop, int force_seq) {
-    finalize_frame(blockIdx.x, ncomp_all, band_sums, area_first, area_sums, probe_all, fstat, ell_all, det64, cnt64, det32, cnt32,
-                   H, W, WW, maxm, stop, force_seq);
-}
-
-void launch_finalize(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_finalize", k_finalize, dim3(nb), dim3(256), 0, s, w.ncomp, w.band_sums, w.area_first,
-                       w.area_sums, w.probe, w.fstat, w.ell, w.det64,
-                       w.cnt, det, counts, h->H, h->W, h->WW, h->maxm, VBS_KNOB("VBS_FINAL_STOP"),
-                       h->force_seq_match ? 1 : 0);                 // (vbs_set_option: exercises the sequential replay)
-}
-
-// The few-frames path: a13 and a15 (+ a19 / a20) of a frame in ONE launch - the same workgroup fits and matches the
-// frame's detections, then tracks them against the reference IDs (a launch on a dependent stream costs ~ 5 us, as much as
-// either kernel works on one frame).  Same code, same results as k_finalize followed by k_track.
-#include "track_common.h"
-__global__ __launch_bounds__(256) void k_finalize_track(const u32* __restrict__ ncomp_all, const u64* __restrict__ band_sums,
-                                                        const u32* __restrict__ area_first, const i64* __restrict__ area_sums,
-                                                        const unsigned short* __restrict__ probe_all,
-                                                        const u32* __restrict__ fstat, double* __restrict__ ell_all,
-                                                        double* __restrict__ det64, int32_t* __restrict__ cnt64,
-                                                        double* __restrict__ det32, int32_t* __restrict__ cnt32,
-                                                        int H, int W, int WW, int maxm, int force_seq,
-                                                        const double* __restrict__ ref_xy, int m_ref, double min_dist,
-                                                        float* __restrict__ table, int do3d, CamD cam, double min_size) {
-    finalize_frame(blockIdx.x, ncomp_all, band_sums, area_first, area_sums, probe_all, fstat, ell_all, det64, cnt64, det32, cnt32,
-                   H, W, WW, maxm, 0, force_seq);
-    // (the frame's detections and count were written by THIS workgroup: the barrier's workgroup-scope release / acquire is
-    //  all their readers need - an agent-scope fence here writes back and invalidates the XCD's L2 for nothing)
-    __syncthreads();
-    track_frame(blockIdx.x, det64, cnt64, maxm, ref_xy, m_ref, min_dist, table, do3d, cam, min_size);
-}
-
-void launch_finalize_track(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* counts, const double* ref_xy, int m_ref,
-                           double min_dist, float* table, const vbs_camera* cam, double min_size, hipStream_t s) {
-    CamD c{};
-    if (cam) c = make_cam(*cam);
-    VBS_LAUNCH(h, s, "k_finalize_track", k_finalize_track, dim3(nb), dim3(256), 0, s, w.ncomp, w.band_sums, w.area_first,
-               w.area_sums, w.probe, w.fstat, w.ell, w.det64, w.cnt, det, counts, h->H, h->W, h->WW, h->maxm,
-               h->force_seq_match ? 1 : 0, ref_xy, m_ref, min_dist, table, cam ? 1 : 0, c, min_size);
-}
-
-// The general kernel alone over every frame of the pass: what vbs_measure_markers labels its thresholded bits with (the
-// same instance as above, so no code is generated for it)
-void launch_label_all(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_label", k_label<0>, dim3(nb < 64 ? nb : 64), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase,
-               w.node_pos, w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat,
-               h->lut, w.slow_flag, (const u32*)nullptr, w.probe, nb, 1, h->H, h->W, h->WW, h->maxm, 0,
-               (const u64*)nullptr, (const u64*)nullptr, 0, 0, 0, 0);
+// ms == null: k_label<0> over the frames flagged in w.slow_flag (`all`: every frame), planes as they lie in the workspace; with
+// `nslow` it leaves at once when that counts no frame.  ms (behind k_stage_lat): k_label<ns>, which makes the planes itself.
+void launch_label(vbs_handle* h, Workspace& w, int nb, int all, const u32* nslow, const MorphStrips* ms, hipStream_t s) {
+    const auto kernel = !ms ? k_label<0> : h->bp.ns == 14 ? k_label<14> : k_label<8>;      // (one signature)
+    const MorphStrips m = ms ? *ms : MorphStrips{0, 0, 0, 0};
+    VBS_LAUNCH(h, s, "k_label", kernel, dim3(ms ? nb : std::min(nb, 64)), dim3(1024), 0, s, w.band_bits, w.open_bits, w.wbase,
+               w.node_pos, w.node_comp, w.ncomp, w.band_first, w.band_sums, w.area_first, w.area_sums, w.fstat, h->lut, w.slow_flag,
+               nslow, w.probe, nb, all, h->H, h->W, h->WW, h->maxm, ms ? 0 : VBS_KNOB("VBS_LABEL_STOP"),
+               (const u64*)(ms ? w.mask_bits : nullptr), (const u64*)(ms ? w.area_bits : nullptr), m.G, m.strips, m.rps, m.wpf);
 }

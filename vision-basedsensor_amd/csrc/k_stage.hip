@@ -31,7 +31,7 @@
 //           segment that holds it (requests posted through a small LDS mailbox); ids follow once the components are known
 // Frames the fast path cannot take (more than K segments alive in a tile or 8 in all, too many records / pairs /
 // components, holes in the opened mask, a vertex of multiplicity > 2, a crowded mailbox) set their slow flag (the value
-// says why): k_morph and k_label (k_label.hip) redo them.
+// says why): k_morph (k_morph.hip) and k_label (k_label.hip) redo them.
 #include "stage_common.h"
 
 #define ST_NT_SMALL 256           // small frames: four waves, THREE workgroups per CU (see stage_threads)
@@ -656,7 +656,7 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
 // smaller tables hold takes the general kernels, like any frame beyond the large ones; a handle whose max_markers makes
 // the tables too large for three workgroups (1024) keeps 768.  VBS_OPT_STAGE_IMPL = 3 keeps 768 everywhere (test hook: the
 // two shapes must agree bit for bit).
-static int stage_threads(const vbs_handle* h, int nb) {
+int stage_threads(const vbs_handle* h, int nb) {
     if (h->stage_impl == 3) return ST_NT;
     const int G = 64 / h->WW, R768 = (h->H + (ST_NT / 64) * G - 1) / ((ST_NT / 64) * G);
     if (h->bp.ns == 8) return R768 <= 8 ? ST_NT_SMALL : ST_NT;
@@ -726,10 +726,10 @@ static bool stage_launch_t(vbs_handle* h, Workspace& w, int nb, const StageGeom&
 }
 
 // false: geometry outside the fused path (or the LDS it needs was refused): the caller runs the round-2 kernels
-bool launch_stage(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
+bool launch_stage(vbs_handle* h, Workspace& w, int nb, int nt, hipStream_t s) {
     StageGeom g;
     size_t lds = 0;
-    if (stage_threads(h, nb) < ST_NT && stage_geom(h, w, &g, &lds, ST_NT_SMALL) &&
+    if (nt < ST_NT && stage_geom(h, w, &g, &lds, ST_NT_SMALL) &&
         (h->bp.ns == 14 ? stage_launch_t<14, ST_NT_SMALL>(h, w, nb, g, lds, s) : stage_launch_t<8, ST_NT_SMALL>(h, w, nb, g, lds, s))) {
         // Its taller tiles and smaller tables give out earlier on dense layouts (17 x 17 dots at a pitch of 56 px in 1280x1024:
         // every frame); those frames get a second chance on 768 threads before the general kernels (11.1 -> 4.7 us per frame

@@ -40,7 +40,7 @@
 #ifndef LT_ROWS
 #define LT_ROWS 6                  // rows per thread aimed at (8: 50.8 us for a 1280x1024 frame, 6: 49.0, 5: 48.6 - with C at its cap)
 #endif
-// header words of a frame (VBS_LAT_HDR each, cleared by launch_labelling's fill together with the slow flags)
+// header words of a frame (VBS_LAT_HDR each, cleared by clear_pass's fill together with the slow flags)
 #define LH_ARRIVE1 0
 #define LH_ARRIVE2 1
 #define LH_FLAG 2                  // 1: the band components and sums are out; 2: the band plane handed the frame on

@@ -1,5 +1,5 @@
 // a15 (+ a19 / a20 fused): the tracking of one frame against the reference IDs, shared by k_track (k_solve.hip) and the
-// one-launch form of the few-frames path, k_finalize_track (k_label.hip).  Float64 without contraction, as the reference
+// one-launch form of the few-frames path, k_finalize_track (k_finalize.hip).  Float64 without contraction, as the reference
 // computes; the contraction mode of the including file is restored to the compiler's default at the end.
 #pragma once
 #include "common.h"
