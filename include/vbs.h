@@ -297,6 +297,43 @@ int vbs_undistort_points(int device, const double* pts, int n, const vbs_camera*
 int vbs_calculate_3d(int device, const double* uvd, int n, const vbs_camera* cam, double* xyz,
                      int32_t* ok, void* stream);
 
+/* ---- Extrinsic calibration (code/Marker_Calibration/extrinsic_calibration.py) -------------------------------------------------
+ * vbs_pnp_ransac - calibrate_camera_extrinsics (extrinsic_calibration.py:81-123): cv2.solvePnPRansac(SOLVEPNP_ITERATIVE,
+ * reprojectionError, iterationsCount) (:97-106), projectPoints and the mean reprojection error (:117-118), for n_problems
+ * problems at once - one per frame of a recording - that share their world points and their sample table.  No handle needed.
+ *   world [dev] float64 [n_points,3], n_points <= VBS_PNP_MAX_POINTS; exactly one of
+ *   image [dev] float64 [n_problems,n_points,2] pixel positions (a non-finite one is invalid), or
+ *   table [dev] float32 [n_problems,n_points,VBS_TABLE_COLS] as vbs_track_to_3d writes it: Cx, Cy of the rows with VBS_FLAG_TRACKED;
+ *   valid [dev] uint8 [n_problems,n_points] (may be NULL = all): 0 removes a correspondence;
+ *   cam: K and dist only (k1 k2 p1 p2 k3); samples [dev] int32 [n_hyp,VBS_PNP_SAMPLE], n_hyp <= VBS_PNP_MAX_HYPOTHESES: the
+ *   point indices of every hypothesis, drawn by the caller (the same draws serve every problem, so a run is deterministic).
+ * Every hypothesis: normalised points (the inverse model of vbs_undistort_points) -> planar homography of its first 4 points
+ * (Z ignored, 8 x 8 elimination with partial pivoting) -> nearest rotation -> 10 Gauss-Newton steps on all 6 with their Z ->
+ * the number of valid points whose pixel error through the forward Brown-Conrady model is <= reproj_px.  A hypothesis is VOID
+ * (count -1) when its sample repeats an index, touches an invalid point, is singular, or puts a sample point behind the camera.
+ *   hyp_count [dev] int32 [n_problems,n_hyp], hyp_pose [dev] float64 [n_problems,n_hyp,12] = R row-major, then T (outputs).
+ * Every problem: the winner = highest count, ties to the lowest index; Levenberg-Marquardt (at most 20 steps, analytic Jacobian)
+ * on the pixel error of the winner's inliers.  cv2 shortens the iteration count by its confidence and draws EPnP hypotheses from
+ * 5 points: poses agree up to the optimiser, not bit for bit.
+ *   status [dev] int32 [n_problems]: VBS_OK, VBS_PNP_FEW_POINTS (fewer than 4 valid points, :89-91) or VBS_PNP_NO_HYPOTHESIS
+ *     (every hypothesis void: also fewer than VBS_PNP_SAMPLE valid points); a failed problem has NaN pose and errors, count 0,
+ *     winner -1, and does not touch its neighbours;
+ *   pose [dev] float64 [n_problems,12] = R_world_to_cam row-major, T_world_to_cam; inlier_count [dev] int32 [n_problems];
+ *   inlier_mask [dev] uint8 [n_problems,n_points]: the WINNING HYPOTHESIS's inliers (not recomputed after the refit, as cv2);
+ *   errors [dev] float64 [n_problems,2] = mean pixel error over ALL valid points (what :118 computes), RMS over the inliers;
+ *   winner [dev] int32 [n_problems]: index of the winning hypothesis.
+ * Float64, no atomics, fixed summation order: two runs give the same bits and a problem does not depend on its batch.
+ * n_problems is not limited (more than 65535 run as several launch pairs); the hypothesis buffers are what grows with it. */
+#define VBS_PNP_SAMPLE            6
+#define VBS_PNP_MAX_POINTS     1024
+#define VBS_PNP_MAX_HYPOTHESES 4096
+#define VBS_PNP_FEW_POINTS        1
+#define VBS_PNP_NO_HYPOTHESIS     2
+int vbs_pnp_ransac(int device, const double* world, int n_points, const double* image, const float* table,
+                   const uint8_t* valid, int n_problems, const vbs_camera* cam, const int32_t* samples, int n_hyp,
+                   double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
+                   int32_t* inlier_count, uint8_t* inlier_mask, double* errors, int32_t* winner, void* stream);
+
 /* MarkerTracker._marker_center (marker_detection.py:166-249): band = mask AND NOT erode(mask)
  * (maximum/minimum_filter :171-174) -> 4-connected labels (:176) -> centroids (:181); 5x5 open
  * (:195) -> external contours (:196) -> fitEllipse (:208) -> contour/centre matching (:222-243).

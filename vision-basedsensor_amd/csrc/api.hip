@@ -539,6 +539,22 @@ extern "C" int vbs_calculate_3d(int device, const double* uvd, int n, const vbs_
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+extern "C" int vbs_pnp_ransac(int device, const double* world, int n_points, const double* image, const float* table,
+                              const uint8_t* valid, int n_problems, const vbs_camera* cam, const int32_t* samples, int n_hyp,
+                              double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
+                              int32_t* inlier_count, uint8_t* inlier_mask, double* errors, int32_t* winner, void* stream) {
+    if (!world || (!image) == (!table) || !cam || !samples || !hyp_count || !hyp_pose || !status || !pose || !inlier_count ||
+        !inlier_mask || !errors || !winner)
+        return VBS_EINVAL;
+    if (n_points < 1 || n_points > VBS_PNP_MAX_POINTS || n_hyp < 1 || n_hyp > VBS_PNP_MAX_HYPOTHESES || n_problems < 0 || !(reproj_px >= 0.0) || !std::isfinite(reproj_px) || !(cam->K[0] > 0) || !(cam->K[4] > 0))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (n_problems)
+        launch_pnp(world, n_points, image, table, valid, n_problems, *cam, samples, n_hyp, reproj_px, hyp_count, hyp_pose, status,
+                   pose, inlier_count, inlier_mask, errors, winner, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 extern "C" int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8_t* area_mask, int n,
                                  double* det, int32_t* counts, void* stream) {
     if (!h) return VBS_EINVAL;

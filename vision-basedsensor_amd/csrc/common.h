@@ -230,6 +230,10 @@ void launch_series_cumsum64(const double* disp, int n, int m_ref, int frame_begi
 void launch_window_means(vbs_handle* h, const float* table, int m_ref, const int32_t* windows, int nw, int pieces, double* part,
                          double* means, hipStream_t s);
 void launch_disp_from_frame(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, double* out, hipStream_t s);
+// k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
+void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
+                const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
+                int32_t* inlier_count, u8* inlier_mask, double* errors, int32_t* winner, hipStream_t s);
 int setup_undistort(vbs_handle* h, const double* K9, const double* dist, int ndist, hipStream_t s);
 void launch_remap(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n, int64_t stride_row,
                   u8* out, int to_gray, hipStream_t s);

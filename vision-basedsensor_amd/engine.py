@@ -482,6 +482,69 @@ def undistort_points(points, cam: L.Camera, device=None):
     return out
 
 
+def pnp_samples(n: int, iterations: int = 1000, seed: int = 0) -> np.ndarray:
+    """The sample table of `pnp_ransac`: int32 [iterations, 6], per hypothesis 6 distinct indices out of n, drawn from
+    `np.random.default_rng(seed)`.  Fewer than 6 points: every row is -1 (void)."""
+    n, iterations = int(n), int(iterations)
+    if n < 1 or not 1 <= iterations <= L.PNP_MAX_HYPOTHESES:
+        raise ValueError(f"pnp_samples: n >= 1 and 1 <= iterations <= {L.PNP_MAX_HYPOTHESES}")
+    out = np.full((iterations, L.PNP_SAMPLE), -1, dtype=np.int32)
+    if n >= L.PNP_SAMPLE:
+        rng = np.random.default_rng(seed)
+        for h in range(iterations):
+            out[h] = rng.choice(n, size=L.PNP_SAMPLE, replace=False)
+    return out
+
+
+def pnp_ransac(world, image_or_table, cam: L.Camera, iterations: int = 1000, reproj_px: float = 8.0, seed: int = 0, valid=None,
+               device=None, samples=None):
+    """`calibrate_camera_extrinsics` (`extrinsic_calibration.py:81-123`) for a batch of problems on the GPU (`vbs_pnp_ransac`).
+    world [N,3]; image_or_table: float64 [B,N,2] (or [N,2]) pixel positions, or a float32 tracker table [B,N,10] (Cx, Cy of the
+    rows with FLAG_TRACKED); valid: optional [B,N] mask.  Returns a dict of device tensors: status [B], R [B,3,3], T [B,3],
+    inlier_count [B], inlier_mask [B,N] uint8, mean_error [B], inlier_rms [B], winner [B], and per hypothesis hyp_count [B,H],
+    hyp_pose [B,H,12]; `samples` (int32 [H,6], default `pnp_samples(N, iterations, seed)`) is returned as given."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    w = _dev_f64(world, dev, 3)
+    n = w.shape[0]
+    x = image_or_table if isinstance(image_or_table, torch.Tensor) else torch.as_tensor(np.asarray(image_or_table))
+    if x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3 or x.shape[1] != n or x.shape[2] not in (2, L.TABLE_COLS):
+        raise ValueError(f"image_or_table must be [B, {n}, 2] or [B, {n}, {L.TABLE_COLS}]")
+    is_table = x.shape[2] == L.TABLE_COLS
+    x = x.to(device=dev, dtype=torch.float32 if is_table else torch.float64).contiguous()
+    b = x.shape[0]
+    v = None
+    if valid is not None:
+        v = torch.as_tensor(valid, device=dev).reshape(b, n).ne(0).to(torch.uint8).contiguous()
+    smp = pnp_samples(n, iterations, seed) if samples is None else np.ascontiguousarray(samples, dtype=np.int32)
+    if smp.ndim != 2 or smp.shape[1] != L.PNP_SAMPLE:
+        raise ValueError(f"samples must be [H, {L.PNP_SAMPLE}]")
+    smp_d = torch.as_tensor(smp, device=dev)
+    nh = smp.shape[0]
+    out = {"hyp_count": torch.empty((b, nh), dtype=torch.int32, device=dev),
+           "hyp_pose": torch.empty((b, nh, 12), dtype=torch.float64, device=dev),
+           "status": torch.empty((b,), dtype=torch.int32, device=dev),
+           "inlier_count": torch.empty((b,), dtype=torch.int32, device=dev),
+           "inlier_mask": torch.empty((b, n), dtype=torch.uint8, device=dev),
+           "winner": torch.empty((b,), dtype=torch.int32, device=dev)}
+    pose = torch.empty((b, 12), dtype=torch.float64, device=dev)
+    errors = torch.empty((b, 2), dtype=torch.float64, device=dev)
+    rc = L.lib().vbs_pnp_ransac(dev.index, _ptr(w), n, _ptr(None if is_table else x), _ptr(x if is_table else None), _ptr(v), b,
+                                C.byref(cam), _ptr(smp_d), nh, float(reproj_px), _ptr(out["hyp_count"]), _ptr(out["hyp_pose"]),
+                                _ptr(out["status"]), _ptr(pose), _ptr(out["inlier_count"]), _ptr(out["inlier_mask"]),
+                                _ptr(errors), _ptr(out["winner"]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError(f"vbs_pnp_ransac: bad argument (at most {L.PNP_MAX_POINTS} points and {L.PNP_MAX_HYPOTHESES} "
+                         "hypotheses, positive focal lengths, reproj_px >= 0)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_pnp_ransac failed ({rc})")
+    out.update(R=pose[:, :9].reshape(b, 3, 3), T=pose[:, 9:], mean_error=errors[:, 0], inlier_rms=errors[:, 1], samples=smp)
+    return out
+
+
 def normxcorr2_general(template, image, mode="same", device=None):
     """`_normxcorr2` for arbitrary operands: float64 map of the mode's size on the GPU (`vbs_normxcorr2_general`)."""
     if not torch.cuda.is_available():

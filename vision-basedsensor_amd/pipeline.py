@@ -202,3 +202,22 @@ def to_marker_frame(table, ids, frame_offset=0, path=None):
         from .xlsx_io import dataframe_to_xlsx
         dataframe_to_xlsx(df, path)
     return df
+
+
+def to_pixel_markers(table, ids=None, frame=0, path=None):
+    """The `pixel_marker.csv` sheet `extrinsic_calibration.py`'s main reads (`:266,277`): one row `marker_id, u, v` per slot
+    tracked in `frame` (Cx, Cy of the table), `marker_id` = `ids.marker_ids` (slot number + 1 without `ids`).  `path`: also
+    written as .csv."""
+    import pandas as pd
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if t.ndim != 3 or t.shape[2] != L.TABLE_COLS:
+        raise ValueError(f"table must be [N, M, {L.TABLE_COLS}]")
+    mid = _ids.marker_ids(ids) if ids is not None else np.arange(1, t.shape[1] + 1, dtype=np.int64)
+    if len(mid) != t.shape[1]:
+        raise ValueError(f"table has {t.shape[1]} slots, ids {len(mid)}")
+    row = t[int(frame)]
+    s = np.nonzero((row[:, 0].astype(np.int64) & L.FLAG_TRACKED) != 0)[0]
+    df = pd.DataFrame({"marker_id": mid[s], "u": row[s, 1].astype(np.float64), "v": row[s, 2].astype(np.float64)})
+    if path is not None:
+        df.to_csv(path, index=False)
+    return df
