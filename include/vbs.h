@@ -381,6 +381,46 @@ int vbs_measure_markers(vbs_handle* h, const uint8_t* frames, int n, int channel
                         double threshold, double min_area, double min_circularity, double scale_px_per_mm, double offset_mm,
                         double* rec, int32_t* counts, double* stats, void* stream);
 
+/* ---- Chessboard corners (Marker_Calibration/intrinsic_calibration.py:75-81, Precision_Validation/DiameterValidation.py:50) ----
+ * vbs_chess_corners - cv2.findChessboardCorners(gray, (pw, ph)) for n gray frames at once, restated (cv2 is not available to
+ * this project: DESIGN.md 4.9 and 7 say what is restated and what is recalled).  No handle needed.
+ *   gray [dev] uint8, pixel (i, y, x) at gray + i*stride_n + y*stride_row + x (a crop is a pointer offset); BGR frames go
+ *   through vbs_bgr2gray first.  1 <= h, w <= 16384; 2 <= pw, ph; pw * ph <= VBS_CHESS_MAX_PATTERN, else VBS_ECAPACITY (a
+ *   pattern is never cut short).
+ * Response: the integer ChESS response on a 16-sample ring of radius 5, R = 5 (SR - DR) - |5 sum(ring) - 16 L|, for pixels at
+ * least 5 from every edge (minus infinity elsewhere).  Candidates: R > 0, >= every response of its 9 x 9 neighbourhood and > those
+ * before it in row-major order.  Ordering: the VBS_CHESS_MAX_CANDIDATES strongest by (R desc, y asc, x asc) are the seeds, in
+ * that order, and a seed walks only over candidates with 8 R >= its own R.  Its two steps are its nearest neighbour and its
+ * nearest neighbour between 60 and 120 degrees of that, at most twice as long; positions p + step are walked with the step
+ * re-estimated at every corner, the nearest candidate accepted when 16 d^2 <= |step|^2.  found = 1 only when the maximal
+ * lattice through the seed is exactly pw x ph (a larger or an incomplete one: 0); the first seed that succeeds wins.  Integer
+ * arithmetic throughout: results do not depend on scheduling.
+ *   peaks [dev] int32 [n,pw*ph,2] (x, y): corner (r, c) at r*pw + c, column step x row step > 0 in image axes, and among the
+ *     labellings that satisfy this the one whose corner 0 has the smallest (y, x); -1 where found = 0.
+ *   corners [dev] float64 [n,pw*ph,2]: the peaks through vbs_corner_subpix with window (2,2), 15 iterations, eps 0.1 - the
+ *     refinement findChessboardCorners ends with; NaN where found = 0.
+ *   found [dev] int32 [n]; n_candidates [dev] int32 [n]: ALL candidates of the frame, before the cap.
+ *   response [dev] int32 [n,h,w] or NULL: the response map (INT32_MIN = minus infinity), for tests; otherwise never written.
+ *   workspace [dev]: vbs_chess_workspace(n, h, w) bytes, 8-byte aligned (one 64-bit slot per 5 x 5 cell of every 32 x 16 tile).
+ * vbs_corner_subpix - cv2.cornerSubPix(gray, corners, (wx, wy), (zx, zy), (EPS + MAX_ITER, max_iter, eps)) (:80-81) for k
+ * corners in each of n frames, in place: Gaussian window exp(-(i/wy)^2) exp(-(j/wx)^2), zeroed inside the zero zone (-1, -1 =
+ * none); per iteration a bilinear (2wx+3) x (2wy+3) patch with replicated border, central differences, the sums a, b, c, bb1,
+ * bb2, the 2 x 2 solve; stops at max_iter, at |step| <= eps, on a singular system, or when the corner leaves the image; a
+ * corner that ends further than the window from its start returns to its start.  1 <= wx, wy <= VBS_CHESS_MAX_WIN, n*k < 2^30.
+ * The patch and the window are float32 as in cv2, positions and sums float64 (cv2: float32 positions), one wave per corner,
+ * sums reduced over the lanes in a fixed tree: the same bits run to run and whatever the batch.  A non-finite corner is left
+ * as it is.  iters [dev] int32 [n,k] or NULL: solves done per corner. */
+#define VBS_CHESS_MAX_CANDIDATES 256
+#define VBS_CHESS_MAX_PATTERN    256
+#define VBS_CHESS_MAX_WIN         15
+int64_t vbs_chess_workspace(int n, int h, int w);
+int vbs_chess_corners(int device, const uint8_t* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row, int pw, int ph,
+                      double* corners, int32_t* found, int32_t* peaks, int32_t* n_candidates, int32_t* response,
+                      void* workspace, void* stream);
+int vbs_corner_subpix(int device, const uint8_t* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row,
+                      double* corners, int k, int wx, int wy, int zx, int zy, int max_iter, double eps, int32_t* iters,
+                      void* stream);
+
 /* MarkerTracker._track_markers (marker_detection.py:349-396): per reference ID the nearest
  * detection (first on ties), dropped when farther than min_dist.  ref_xy [dev] float64 [m_ref,2]
  * = (Ox, Oy) in reference-dict order; table [dev] float32 [n,m_ref,VBS_TABLE_COLS]; XYZ columns

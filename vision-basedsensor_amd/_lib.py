@@ -13,6 +13,7 @@ MJPEG_SCAN_ALIGN, MJPEG_SCAN_GUARD, MJPEG_HUFF_SET_BYTES, MJPEG_SUBSEQ_BITS, MJP
 SERIES_CHUNK, SERIES_REC_COLS, STATS_COLS, WINDOW_COLS = 32, 5, 5, 4
 DIAM_COLS, DIAM_STATS_COLS, DIAM_MAX_EXTENT = 24, 5, 512
 PNP_SAMPLE, PNP_MAX_POINTS, PNP_MAX_HYPOTHESES, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS = 6, 1024, 4096, 1, 2
+CHESS_MAX_CANDIDATES, CHESS_MAX_PATTERN, CHESS_MAX_WIN = 256, 256, 15
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -25,7 +26,8 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking",
            "vbs_series_chunks", "vbs_series_stats", "vbs_series_stats_f64", "vbs_series_partial", "vbs_series_merge",
            "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device",
-           "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers", "vbs_pnp_ransac")
+           "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers", "vbs_pnp_ransac",
+           "vbs_chess_workspace", "vbs_chess_corners", "vbs_corner_subpix")
 
 
 class Camera(C.Structure):
@@ -123,6 +125,9 @@ def lib():
         "vbs_threshold_bits": (i32, [vp, vp, i32, i32, i64, i64, f64, vp, vp]),
         "vbs_measure_markers": (i32, [vp, vp, i32, i32, i64, i64, f64, f64, f64, f64, f64, vp, vp, vp, vp]),
         "vbs_pnp_ransac": (i32, [i32, vp, i32, vp, vp, vp, i32, cam_p, vp, i32, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "vbs_chess_workspace": (i64, [i32, i32, i32]),
+        "vbs_chess_corners": (i32, [i32, vp, i32, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "vbs_corner_subpix": (i32, [i32, vp, i32, i32, i32, i64, i64, vp, i32, i32, i32, i32, i32, i32, f64, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

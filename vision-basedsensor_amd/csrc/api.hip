@@ -555,6 +555,38 @@ extern "C" int vbs_pnp_ransac(int device, const double* world, int n_points, con
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+extern "C" int64_t vbs_chess_workspace(int n, int h, int w) {
+    if (n < 0 || h < 1 || w < 1 || h > 16384 || w > 16384) return VBS_EINVAL;
+    return (int64_t)chess_workspace_bytes(n, h, w);
+}
+
+extern "C" int vbs_chess_corners(int device, const uint8_t* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row,
+                                 int pw, int ph, double* corners, int32_t* found, int32_t* peaks, int32_t* n_candidates,
+                                 int32_t* response, void* workspace, void* stream) {
+    if (!gray || !corners || !found || !peaks || !n_candidates || !workspace || n < 0 || h < 1 || w < 1 || h > 16384 ||
+        w > 16384 || stride_row < w || pw < 2 || ph < 2 || ((uintptr_t)workspace & 7))
+        return VBS_EINVAL;
+    if ((int64_t)pw * ph > VBS_CHESS_MAX_PATTERN) return VBS_ECAPACITY;      // never cut short
+    if ((int64_t)n * pw * ph >= (1 << 30)) return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (n) launch_chess(gray, n, h, w, stride_n, stride_row, pw, ph, corners, found, peaks, n_candidates, response, (u64*)workspace,
+                        (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_corner_subpix(int device, const uint8_t* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row,
+                                 double* corners, int k, int wx, int wy, int zx, int zy, int max_iter, double eps, int32_t* iters,
+                                 void* stream) {
+    if (!gray || !corners || n < 0 || k < 0 || h < 1 || w < 1 || h > 16384 || w > 16384 || stride_row < w || wx < 1 || wy < 1 ||
+        wx > VBS_CHESS_MAX_WIN || wy > VBS_CHESS_MAX_WIN || max_iter < 1 || !(eps >= 0.0) || !std::isfinite(eps) ||
+        (int64_t)n * k >= (1 << 30))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (n && k) launch_corner_subpix(gray, n, h, w, stride_n, stride_row, corners, k, wx, wy, zx, zy, max_iter, eps, iters,
+                                     (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 extern "C" int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8_t* area_mask, int n,
                                  double* det, int32_t* counts, void* stream) {
     if (!h) return VBS_EINVAL;

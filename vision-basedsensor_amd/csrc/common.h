@@ -234,6 +234,12 @@ void launch_disp_from_frame(vbs_handle* h, const float* table, int n, int m_ref,
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
                 int32_t* inlier_count, u8* inlier_mask, double* errors, int32_t* winner, hipStream_t s);
+// k_chess.hip (f8): response + candidates + ordering + the finder's own refinement; the refinement alone
+size_t chess_workspace_bytes(int n, int h, int w);
+void launch_chess(const u8* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row, int pw, int ph, double* corners,
+                  int32_t* found, int32_t* peaks, int32_t* n_candidates, int32_t* response, u64* slots, hipStream_t s);
+void launch_corner_subpix(const u8* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row, double* corners, int k,
+                          int wx, int wy, int zx, int zy, int max_iter, double eps, int32_t* iters, hipStream_t s);
 int setup_undistort(vbs_handle* h, const double* K9, const double* dist, int ndist, hipStream_t s);
 void launch_remap(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n, int64_t stride_row,
                   u8* out, int to_gray, hipStream_t s);

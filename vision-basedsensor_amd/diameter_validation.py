@@ -2,9 +2,10 @@
 
 `measure_markers` (:113-144) runs on the GPU (`Engine.measure_markers`: blur, threshold, contours, area, perimeter,
 circularity, minimum enclosing circle, millimetres); `scale_from_corners` is `calculate_scale`'s arithmetic (:54-71) on
-corners the caller supplies.  Out of scope, as SURVEY §2.1 sets out: the trackbar window (`select_threshold_interactive`), the
-plots, and `cv2.findChessboardCorners` - `calculate_scale` itself says so when called.  There is no CPU path: without a GPU
-every compute entry raises `VbsError`.
+corners the caller supplies, and `scale_from_image` is the working form of `calculate_scale` (:48-74): the board is found on the
+device (`Engine.find_chessboard_corners`, the project's restatement of `cv2.findChessboardCorners`).  Out of scope, as SURVEY
+§2.1 sets out: the trackbar window (`select_threshold_interactive`) and the plots; `calculate_scale` itself keeps naming
+`cv2.findChessboardCorners` when called.  There is no CPU path: without a GPU every compute entry raises `VbsError`.
 """
 from __future__ import annotations
 
@@ -60,6 +61,25 @@ def calculate_scale(gray_img, pattern_size, square_mm):
     raise NotImplementedError("calculate_scale locates the chessboard with cv2.findChessboardCorners, which is out of this "
                               "project's scope: find the corners with a detector of your own and pass them to "
                               "scale_from_corners(corners, pattern_size, square_mm)")
+
+
+def scale_from_image(gray_img, pattern_size, square_mm, engine=None):
+    """The working form of `calculate_scale` (:48-74): find the `pattern_size` inner corners of the board in one gray [H,W] or
+    BGR [H,W,3] image on the device and return (pixels per millimetre, corners float32 [k,1,2] as cv2 hands them on), or
+    (None, None) when the board is not found.  Without `engine`, the cached engine of the image's size is used."""
+    import torch
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: diameter_validation has no CPU path")
+    f = _as_batch(gray_img)
+    if f.shape[0] != 1:
+        raise ValueError("scale_from_image takes one image")
+    if engine is None:
+        engine = _engine_for(f.shape[1], f.shape[2], 1)
+    found, corners, _, _ = engine.find_chessboard_corners(f, pattern_size)
+    if not int(found[0].item()):
+        return None, None
+    c = corners[0].cpu().numpy()
+    return scale_from_corners(c, pattern_size, square_mm), c.astype(np.float32).reshape(-1, 1, 2)
 
 
 def _as_batch(frames):

@@ -237,6 +237,69 @@ class Engine:
                                                      _ptr(counts), _ptr(stats), self._stream()), "vbs_measure_markers")
         return rec, counts, stats
 
+    # ---- chessboard corners (Marker_Calibration/intrinsic_calibration.py, DiameterValidation.calculate_scale) ----
+    def _gray_batch(self, frames):
+        """uint8 [H,W] | [H,W,3] | [N,H,W] | [N,H,W,3], array or tensor, strided views included -> gray device tensor [N,H,W]
+        with unit pixel stride (BGR through k_gray)."""
+        f = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.asarray(frames))
+        if f.dtype != torch.uint8:
+            raise ValueError("frames must be uint8")
+        if f.dim() == 2 or (f.dim() == 3 and f.shape[-1] == 3 and tuple(f.shape[:2]) == (self.H, self.W)):
+            f = f.unsqueeze(0)
+        f = f.to(self.device)
+        if f.stride(-1) != 1 or (f.dim() == 4 and f.stride(2) != 3):
+            f = f.contiguous()
+        f, n, ch, _, _ = self._frames(f)
+        return self.bgr2gray(f) if ch == 3 else f
+
+    def find_chessboard_corners(self, frames, pattern_size, want_response=False):
+        """`cv2.findChessboardCorners(gray, pattern_size)` for every frame of a batch (`vbs_chess_corners`; include/vbs.h says
+        what is restated): (found int32 [n], corners float64 [n, pw*ph, 2], peaks int32 [n, pw*ph, 2], n_candidates int32 [n])
+        as device tensors, and the int32 response map [n, H, W] as a fifth with `want_response`.  corners are NaN and peaks -1
+        where found is 0.  No synchronisation."""
+        pw, ph = int(pattern_size[0]), int(pattern_size[1])
+        g = self._gray_batch(frames)
+        n = g.shape[0]
+        k = max(pw * ph, 0)
+        corners = torch.empty((n, k, 2), dtype=torch.float64, device=self.device)
+        peaks = torch.empty((n, k, 2), dtype=torch.int32, device=self.device)
+        found = torch.empty((n,), dtype=torch.int32, device=self.device)
+        ncand = torch.empty((n,), dtype=torch.int32, device=self.device)
+        resp = torch.empty((n, self.H, self.W), dtype=torch.int32, device=self.device) if want_response else None
+        nbytes = int(self.lib.vbs_chess_workspace(n, self.H, self.W))
+        if nbytes < 0:
+            raise ValueError(f"vbs_chess_workspace: frames of {self.H} x {self.W} are outside 1..16384 pixels a side (status {nbytes})")
+        ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vbs_chess_corners(self.device.index, _ptr(g), n, self.H, self.W, g.stride(0), g.stride(1), pw, ph,
+                                            _ptr(corners), _ptr(found), _ptr(peaks), _ptr(ncand), _ptr(resp), _ptr(ws),
+                                            self._stream())
+        if rc == L.VBS_ECAPACITY:
+            raise L.VbsError(f"vbs_chess_corners: a pattern of {pw} x {ph} corners exceeds VBS_CHESS_MAX_PATTERN = "
+                             f"{L.CHESS_MAX_PATTERN} (status {rc})")
+        if rc != L.VBS_OK:
+            raise (ValueError if rc == L.VBS_EINVAL else L.VbsError)(f"vbs_chess_corners: bad argument or HIP error (status {rc})")
+        return (found, corners, peaks, ncand) + ((resp,) if want_response else ())
+
+    def corner_subpix(self, frames, corners, win=(11, 11), zero_zone=(-1, -1), max_iter=30, eps=1e-3, want_iters=False):
+        """`cv2.cornerSubPix(gray, corners, win, zero_zone, (EPS + MAX_ITER, max_iter, eps))` for k corners in each frame of a
+        batch (`vbs_corner_subpix`): corners [n, k, 2] ([k, 2] or cv2's [k, 1, 2] for one frame), array or tensor -> a NEW float64
+        device tensor [n, k, 2]; with `want_iters` also the solves done per corner, int32 [n, k]."""
+        g = self._gray_batch(frames)
+        n = g.shape[0]
+        c = corners if isinstance(corners, torch.Tensor) else torch.from_numpy(np.asarray(corners))
+        c = c.to(device=self.device, dtype=torch.float64).reshape(n, -1, 2).contiguous().clone()
+        k = c.shape[1]
+        iters = torch.zeros((n, k), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vbs_corner_subpix(self.device.index, _ptr(g), n, self.H, self.W, g.stride(0), g.stride(1), _ptr(c), k,
+                                            int(win[0]), int(win[1]), int(zero_zone[0]), int(zero_zone[1]), int(max_iter),
+                                            float(eps), _ptr(iters), self._stream())
+        if rc != L.VBS_OK:
+            raise (ValueError if rc == L.VBS_EINVAL else L.VbsError)(
+                f"vbs_corner_subpix: bad argument (window half-sizes 1..{L.CHESS_MAX_WIN}) or HIP error (status {rc})")
+        return (c, iters) if want_iters else c
+
     def track(self, det, counts, ref_xy, min_dist=20.0):
         ref = torch.as_tensor(ref_xy, dtype=torch.float64, device=self.device).contiguous().reshape(-1, 2)
         if det.dtype != torch.float64 or not det.is_contiguous() or det.device != self.device or det.dim() != 3 \
