@@ -6,13 +6,16 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libvbs.so")
-SOURCES = ("api.hip", "k_blur.hip", "k_ncc.hip", "k_morph.hip", "k_label.hip", "k_finalize.hip", "labelling.hip", "k_ccl.hip", "k_stage.hip", "k_stage_lat.hip", "k_solve.hip", "k_undistort.hip", "k_ids.hip", "host_csv.hip", "host_mjpeg.hip", "k_annotate.hip", "k_jpeg_enc.hip", "k_series.hip", "k_jpeg_huff.hip", "k_diameter.hip", "k_pnp.hip", "k_chess.hip")
+SOURCES = ("api.hip", "k_gray.hip", "k_blur_mfma.hip", "k_blur16.hip", "k_ncc_mfma.hip", "k_ncc_map.hip", "k_ncc_general.hip", "k_morph.hip", "k_label.hip", "k_finalize.hip", "labelling.hip", "k_ccl.hip", "k_stage.hip", "k_stage_lat.hip", "k_solve.hip", "k_undistort.hip", "k_ids.hip", "host_csv.hip", "host_mjpeg.hip", "k_annotate.hip", "k_jpeg_enc.hip", "k_series.hip", "k_jpeg_huff.hip", "k_diameter.hip", "k_pnp.hip", "k_chess.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
-# k_ncc.hip: no SLP pairings (they cost registers, 127 -> 108, and instructions) and no packed float32 instructions at all:
+# k_ncc_mfma.hip: no SLP pairings (they cost registers, 127 -> 108, and instructions) and no packed float32 instructions at all:
 # next to matrix-core instructions a v_pk_fma_f32 costs more than the two v_fma_f32 it replaces (k_ncc_mfma 1.94 ->
 # 1.90 us per frame with its float2 arithmetic split by the compiler)
-FILE_FLAGS = {"k_ncc.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# k_ncc_map.hip: the same flags only because k_ncc was built with them while it shared a file with k_ncc_mfma, and its code
+# differs without them (k_nccg / k_nccg_stats in k_ncc_general.hip do not: profiles/frontend_split_text_equal.txt)
+_NCC_FLAGS = ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"k_ncc_mfma.hip": _NCC_FLAGS, "k_ncc_map.hip": _NCC_FLAGS}
 
 
 def _stale(target, deps):
@@ -25,7 +28,7 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = False, extra_flags=(), suffix: str = "") -> str:
     """`extra_flags` / `suffix`: a second library next to the product one, e.g. tools/ build `libvbs_dbg.so` with
     -DVBS_DEBUG_KNOBS (phase-timing early exits read from the environment); the product library never has them."""
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ccl_common.h"), os.path.join(CSRC, "stage_common.h"), os.path.join(CSRC, "morph_wave.h"), os.path.join(CSRC, "track_common.h"), os.path.join(CSRC, "jpeg_huff_common.h"), os.path.join(CSRC, "pnp_math.h"), os.path.join(CSRC, "..", "..", "include", "vbs.h")]
+    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(CSRC, "..", "..", "include", "vbs.h")]
     lib = LIB.replace(".so", suffix + ".so")
     objs, jobs = [], []
     for src in SOURCES:
@@ -47,7 +50,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), suffix: st
         for warn in ex.map(run, jobs):
             if verbose and warn:
                 print(warn, file=sys.stderr)
-    _check_isa(force or any("k_blur.hip" in " ".join(j) for j in jobs), list(extra_flags), suffix, run)
+    _check_isa(force or any("k_blur16.hip" in " ".join(j) for j in jobs), list(extra_flags), suffix, run)
     if force or jobs or _stale(lib, objs):
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", lib] + objs)
     return lib
@@ -55,15 +58,15 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), suffix: st
 
 def _check_isa(rebuilt: bool, extra_flags, suffix, run):
     """k_blur16's loader keeps loads in flight across inline-asm statements: what the register allocator did with their
-    destination registers is checked in the disassembly after every (re)build of k_blur.hip (vbs_amd/_isa_check.py says
+    destination registers is checked in the disassembly after every (re)build of k_blur16.hip (vbs_amd/_isa_check.py says
     what is checked and why); a violation fails the build."""
     from . import _isa_check
-    src = os.path.join(CSRC, "k_blur.hip")
-    asm = os.path.join(CSRC, "k_blur" + suffix + ".s")
+    src = os.path.join(CSRC, "k_blur16.hip")
+    asm = os.path.join(CSRC, "k_blur16" + suffix + ".s")
     stamp = asm + ".ok"
     if not rebuilt and os.path.exists(stamp) and os.path.getmtime(stamp) >= os.path.getmtime(src):
         return
-    run([HIPCC] + FLAGS + FILE_FLAGS.get("k_blur.hip", []) + extra_flags + ["--cuda-device-only", "-S", src, "-o", asm])
+    run([HIPCC] + FLAGS + FILE_FLAGS.get("k_blur16.hip", []) + extra_flags + ["--cuda-device-only", "-S", src, "-o", asm])
     problems = _isa_check.check_blur16(open(asm).read())
     os.remove(asm)
     if problems:

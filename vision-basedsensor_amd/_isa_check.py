@@ -1,6 +1,6 @@
 """Build-time check of the one place where a kernel's correctness rests on what the register allocator did.
 
-k_blur16's loader wave (csrc/k_blur.hip) keeps four tiles of row loads in flight in four register sets.  The loads and
+k_blur16's loader wave (csrc/k_blur16.hip) keeps four tiles of row loads in flight in four register sets.  The loads and
 the `s_waitcnt vmcnt(12)` that leaves the three younger tiles outstanding are inline assembly (left to the compiler every
 wait is vmcnt(0), because its release / acquire atomics order global memory too), tied to the registers only by asm
 constraints.  Two silent failures were met while that was written: a destination register handed to another

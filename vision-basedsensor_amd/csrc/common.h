@@ -161,7 +161,10 @@ void launch_gray_dense(vbs_handle* h, const u8* frames, int nb, int64_t stride_n
                        hipStream_t s);
 void launch_blur(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
                  u8* area_u8, hipStream_t s);
+void launch_blur_mfma(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
+                      u8* area_u8, hipStream_t s);          // k_blur_mfma.hip: what launch_blur (k_blur16.hip) falls back on
 void launch_ncc(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, double* ncc_out, hipStream_t s);
+void launch_ncc_mfma(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, hipStream_t s);   // k_ncc_mfma.hip: launch_ncc (k_ncc_map.hip) without a map
 void launch_points(int which, const double* in, int n, const vbs_camera& cam, double* out, int32_t* ok,
                    hipStream_t s);
 void launch_threshold(vbs_handle* h, Workspace& w, const u8* mask, const u8* area, int nb, hipStream_t s);

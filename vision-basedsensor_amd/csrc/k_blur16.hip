@@ -1,393 +1,8 @@
-// a3-a5: BGR->gray, two uint8 GaussianBlurs (OpenCV fixed-point model), DoG + 15 (mod 256), inRange.
-// Reference: marker_detection.py:114-129.  Integer arithmetic throughout, so results are
-// independent of summation order and bit-exact against oracle/stages.py:gaussian_blur_u8.
-//
-//   out(y,x) = ( sum_i ky[i] * ( sum_j kx[j] * p(y+i-c, x+j-c) ) + 2^15 ) >> 16,  taps in 1/256
-//
-// k_blur_mfma evaluates both passes of both blurs as banded-Toeplitz products on the int8 matrix cores.
+// a4-a5 for frames whose rows load as aligned dwords: k_blur16, the blurs of k_blur_mfma.hip (model: blur_common.h) on strips
+// of 16 columns with a loader wave, and launch_blur, which chooses between the two kernels.
 #include <algorithm>
-#include <cstdlib>
 
-#include "common.h"
-
-__device__ __forceinline__ int reflect101(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return min(max(i, 0), n - 1);
-}
-
-// gray pixels of 4 consecutive BGR pixels (12 bytes as 3 dwords): cv2's fixed-point weights (common.h gray_coef)
-__device__ __forceinline__ u32 bgr4_to_gray(u32 a, u32 b, u32 c, const GrayCoef& gc) {
-    const u32 g0 = (gc.cb * (a & 255u) + gc.cg * ((a >> 8) & 255u) + gc.cr * ((a >> 16) & 255u) + gc.half) >> gc.shift;
-    const u32 g1 = (gc.cb * (a >> 24) + gc.cg * (b & 255u) + gc.cr * ((b >> 8) & 255u) + gc.half) >> gc.shift;
-    const u32 g2 = (gc.cb * ((b >> 16) & 255u) + gc.cg * (b >> 24) + gc.cr * (c & 255u) + gc.half) >> gc.shift;
-    const u32 g3 = (gc.cb * ((c >> 8) & 255u) + gc.cg * ((c >> 16) & 255u) + gc.cr * (c >> 24) + gc.half) >> gc.shift;
-    return g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
-}
-
-// cvtColor(BGR2GRAY) (or a plain copy for 1 channel) into the pitched gray plane the blur reads: a streaming kernel,
-// 16 pixels per thread (three 16-byte loads, one 16-byte store) when the rows are 16-byte aligned: 0.85-1.0 us per
-// 1280x1024 frame (5.3-6.2 TB/s of its 5.2 MB).  It runs in line in front of the blur (converting a pass ahead on a side
-// stream measured no faster: profiles/NOTES.md section 9).
-// (Converting inside the blur's own loader was built and measured: LDS-DMA staging of the raw bytes kept the matrix
-//  operands in registers only at the price of 50 spilled VGPRs - 5 us per frame against 1.45.)
-__global__ __launch_bounds__(256) void k_gray(const u8* __restrict__ frames, int channels, int64_t stride_n,
-                                              int64_t stride_row, u8* __restrict__ gray, int H, int W, int P, GrayCoef gc,
-                                              int vec_ok, int flat) {
-    __shared__ __align__(16) uint4 raw[2][3 * 256];     // 24 KB: the 48 bytes of each thread's 16 pixels, loaded coalesced
-    const int n = blockIdx.z;
-    if (flat) {
-        // dense BGR frame (row stride 3 W, gray pitch W): one run of H W pixels, 2 x 4096 per block, loaded as consecutive
-        // 16-byte pieces by consecutive lanes (both halves in flight together, streamed past the caches) and handed to
-        // their owners through LDS
-        const int64_t npx = (int64_t)H * W, pb = (int64_t)blockIdx.x * 8192;
-        const u8* src = frames + (int64_t)n * stride_n;
-        u8* dstf = gray + (int64_t)n * H * P;
-        if (pb + 8192 <= npx) {                          // block-uniform
-            const uint4* s4 = reinterpret_cast<const uint4*>(src + pb * 3);
-            uint4 v[6];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) {
-                typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(s4 + q * 256 + threadIdx.x));
-                v[q] = make_uint4(t.x, t.y, t.z, t.w);
-            }
-#pragma unroll
-            for (int q = 0; q < 6; ++q) raw[q / 3][(q % 3) * 256 + threadIdx.x] = v[q];
-            __syncthreads();
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const uint4 r0 = raw[hf][3 * threadIdx.x], r1 = raw[hf][3 * threadIdx.x + 1], r2 = raw[hf][3 * threadIdx.x + 2];
-                *reinterpret_cast<uint4*>(dstf + pb + 4096 * hf + threadIdx.x * 16) =
-                    make_uint4(bgr4_to_gray(r0.x, r0.y, r0.z, gc), bgr4_to_gray(r0.w, r1.x, r1.y, gc),
-                               bgr4_to_gray(r1.z, r1.w, r2.x, gc), bgr4_to_gray(r2.y, r2.z, r2.w, gc));
-            }
-        } else {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const int64_t p0 = pb + 4096 * hf + threadIdx.x * 16;
-                if (p0 >= npx) return;                   // (H W is a multiple of 16 in flat mode)
-                const uint4* s4 = reinterpret_cast<const uint4*>(src + p0 * 3);
-                const uint4 r0 = s4[0], r1 = s4[1], r2 = s4[2];
-                *reinterpret_cast<uint4*>(dstf + p0) =
-                    make_uint4(bgr4_to_gray(r0.x, r0.y, r0.z, gc), bgr4_to_gray(r0.w, r1.x, r1.y, gc),
-                               bgr4_to_gray(r1.z, r1.w, r2.x, gc), bgr4_to_gray(r2.y, r2.z, r2.w, gc));
-            }
-        }
-        return;
-    }
-    // rows with their own stride (a crop view, a pitched plane): thread = (row, 16-pixel piece), pieces of consecutive rows
-    // side by side in a block - a 480-pixel row fills 30 of a block's 256 threads when every block takes one row
-    // (0.73 us per 480x450 BGR frame of the reference's cropped configuration, the largest kernel of that workload)
-    const int ppr = P >> 4, idx = blockIdx.x * 256 + threadIdx.x;
-    const int y = idx / ppr, x0 = (idx - y * ppr) * 16;
-    if (y >= H) return;
-    const u8* src = frames + (int64_t)n * stride_n + (int64_t)y * stride_row;
-    u8* dst = gray + ((int64_t)n * H + y) * P + x0;
-    if (vec_ok && channels == 3 && x0 + 16 <= W) {
-        const uint4* s4 = reinterpret_cast<const uint4*>(src + (int64_t)x0 * 3);
-        const uint4 r0 = s4[0], r1 = s4[1], r2 = s4[2];
-        *reinterpret_cast<uint4*>(dst) = make_uint4(bgr4_to_gray(r0.x, r0.y, r0.z, gc), bgr4_to_gray(r0.w, r1.x, r1.y, gc),
-                                                    bgr4_to_gray(r1.z, r1.w, r2.x, gc), bgr4_to_gray(r2.y, r2.z, r2.w, gc));
-        return;
-    }
-    u32 out[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 16; ++k) {
-        const int x = x0 + k;
-        u32 v = 0;
-        if (x < W) {
-            if (channels == 1) {
-                v = src[x];
-            } else {   // cv2 8-bit BGR2GRAY, fixed point (coefficient set: common.h gray_coef)
-                const u8* p = src + (int64_t)x * channels;
-                v = (gc.cb * p[0] + gc.cg * p[1] + gc.cr * p[2] + gc.half) >> gc.shift;
-            }
-        }
-        out[k >> 2] |= v << (8 * (k & 3));
-    }
-    *reinterpret_cast<uint4*>(dst) = make_uint4(out[0], out[1], out[2], out[3]);
-}
-
-// the cvtColor stage on its own (vbs_bgr2gray): dense [n,H,W] output, one pixel per thread
-__global__ void k_gray_dense(const u8* __restrict__ frames, int64_t stride_n, int64_t stride_row,
-                             u8* __restrict__ out, int H, int W, GrayCoef gc) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
-    if (x >= W) return;
-    const u8* p = frames + (int64_t)n * stride_n + (int64_t)y * stride_row + (int64_t)x * 3;
-    out[((int64_t)n * H + y) * W + x] = (u8)((gc.cb * p[0] + gc.cg * p[1] + gc.cr * p[2] + gc.half) >> gc.shift);
-}
-
-void launch_gray_dense(vbs_handle* h, const u8* frames, int nb, int64_t stride_n, int64_t stride_row, u8* out,
-                       hipStream_t s) {
-    dim3 grid((h->W + 255) / 256, h->H, nb);
-    VBS_LAUNCH(h, s, "k_gray_dense", k_gray_dense, grid, dim3(256), 0, s, frames, stride_n, stride_row, out, h->H, h->W,
-               gray_coef(h->gray_bits));
-}
-
-// ---- MFMA path -------------------------------------------------------------------------------------
-// A 101-tap separable blur is 140 MACs per pixel per pass: compute-bound on the vector ALU (v_dot4 at half
-// rate), but a banded-Toeplitz matrix product for the matrix cores, and exact there: taps < 128 and
-// p - 128 are int8, v_mfma_i32_32x32x32_i8 accumulates in int32.
-//
-//   horizontal  Hs[y][x]  = sum_k (p[y][xw+k] - 128) * tap[k - x - (LEFT - R)]        (A = image rows from LDS,
-//                                                                                       B = Toeplitz, constant)
-//               H = Hs + 128 * 256                                                      (taps sum to 256)
-//   vertical    V[x][y]   = sum_k Hs_hi[k][x] * tap[..] * 256 + sum_k (Hs_lo[k][x] - 128) * tap[..] + const
-//
-// One wave owns a 32-column strip and slides down it 32 rows per step.  The horizontal result tile (column
-// on the lane, 16 rows in the accumulator registers) is split into its signed high byte and its low byte
-// (offset by 128), packed four rows to a dword and used directly as the A operand of the vertical product
-// (X^T * T^T sums over the accumulator's row index, so no lane movement and no LDS).  The last NK tiles are
-// kept in a register ring, so every horizontal tile is computed once.  The vertical result has the output
-// row on the lane and 16 columns in registers: each lane assembles its row's 16 mask bits from sign bits
-// and the two lane halves are OR-ed into the 32-bit half word of the bit image.
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void pack_tile(const v16i& acc, v4i& hi, v4i& lo) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        u32 t01 = __builtin_amdgcn_perm((u32)acc[4 * q + 1], (u32)acc[4 * q + 0], 0x05010400u);
-        u32 t23 = __builtin_amdgcn_perm((u32)acc[4 * q + 3], (u32)acc[4 * q + 2], 0x05010400u);
-        lo[q] = (int)(__builtin_amdgcn_perm(t23, t01, 0x05040100u) ^ 0x80808080u);
-        hi[q] = (int)__builtin_amdgcn_perm(t23, t01, 0x07060302u);
-    }
-}
-
-// reflect-101 bytes of one 16-byte chunk that touches the image border or is not dword aligned
-__device__ __forceinline__ uint4 fetch_chunk_slow(const u8* src, int px, int W) {
-    u32 w[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        u32 v = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) v |= (u32)src[reflect101(px + 4 * d + b, W)] << (8 * b);
-        w[d] = v;
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-template <int NK, int SA0, int NKA, bool U8OUT>
-__global__ __launch_bounds__(256, 2) void k_blur_mfma(const u8* __restrict__ gray, int64_t gstride_n,
-                                                      int64_t gstride_row, const uint4* __restrict__ frags,
-                                                      u64* __restrict__ bits, u8* __restrict__ area_u8,
-                                                      u32* __restrict__ fstat, int H, int W, int WW,
-                                                      int tiles_per_seg, int k3, int k8, int span_i, int dbg_arg) {
-#ifdef VBS_DEBUG_KNOBS
-    const int dbg = dbg_arg;                            // tools/gpu_ncc_phase.py: phase timing by early exit
-#else
-    constexpr int dbg = 0;
-#endif
-    constexpr int LEFT = 32 * ((NK - 1) / 2);
-    constexpr int ROWB = 128 + 32 * (NK - 1);          // bytes staged per image row
-    constexpr int CH = ROWB / 16;
-    constexpr int STRIDE = ROWB + 16;                  // 68 (52) dwords: 16 consecutive rows hit all banks
-    constexpr int NIT = (32 * CH + 255) / 256;
-    __shared__ __align__(16) u8 tile[2][32 * STRIDE];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform, and known to the compiler to be
-    const int hh = lane >> 5, m = lane & 31;
-    const int X0 = blockIdx.x * 128, n = blockIdx.z;
-    const int tilesY = (H + 31) / 32;
-    const int tile0 = blockIdx.y * tiles_per_seg;
-    const int ntiles = min(tiles_per_seg, tilesY - tile0);
-    if (ntiles <= 0) return;
-    const int Y0 = tile0 * 32, nsteps = ntiles + NK - 1;
-    const u8* g = gray + (int64_t)n * gstride_n;
-    const bool aligned = ((gstride_row & 3) == 0) && ((gstride_n & 3) == 0) && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0);
-    const bool rows24 = gstride_row > 0 && gstride_row < (1 << 24) && (int64_t)H * gstride_row < (1ll << 31);   // (uniform)
-
-    v4i bh[NK], bha[NKA], tv[NK], tva[NKA];
-#pragma unroll
-    for (int s = 0; s < NK; ++s) {
-        uint4 a = frags[(0 * NK + s) * 64 + lane], b = frags[(1 * NK + s) * 64 + lane];
-        bh[s] = v4i{(int)a.x, (int)a.y, (int)a.z, (int)a.w};
-        tv[s] = v4i{(int)b.x, (int)b.y, (int)b.z, (int)b.w};
-    }
-#pragma unroll
-    for (int s = 0; s < NKA; ++s) {
-        uint4 a = frags[(2 * NK + s) * 64 + lane], b = frags[(2 * NK + NKA + s) * 64 + lane];
-        bha[s] = v4i{(int)a.x, (int)a.y, (int)a.z, (int)a.w};
-        tva[s] = v4i{(int)b.x, (int)b.y, (int)b.z, (int)b.w};
-    }
-
-    // this thread's chunks of the staged tile: row, pixel offset, LDS offset; fast = plain 16-byte load
-    int c_row[NIT], c_px[NIT], c_lds[NIT];
-    bool c_on[NIT], c_fast[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        int c = tid + 256 * it;
-        c_on[it] = c < 32 * CH;
-        c_row[it] = c / CH;
-        int ch = c - c_row[it] * CH;
-        c_px[it] = X0 - LEFT + 16 * ch;
-        c_lds[it] = c_row[it] * STRIDE + 16 * ch;
-        c_fast[it] = aligned && c_px[it] >= 0 && c_px[it] + 16 <= W;
-    }
-    // plain chunks are loaded a step ahead into registers and written to LDS at the end of the step; border chunks
-    // (few, only in the first / last workgroup of a row) are gathered byte by byte at commit time.  (Two steps ahead,
-    // paid for by reading the small kernel's vertical fragments from LDS: measured slower, 1.65 against 1.44 us.)
-    uint4 stage[NIT];
-    auto row_of = [&](int t, int it) { return g + (int64_t)reflect101(Y0 - LEFT + 32 * t + c_row[it], H) * gstride_row; };
-    auto fetch = [&](int t) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it)
-            if (c_on[it] && c_fast[it]) {
-                // (rows24: the row pitch and a frame's size fit 24 / 31 bits - one full-rate multiply and a 32-bit
-                //  offset from the scalar frame pointer instead of a 64-bit multiply per chunk and step)
-                const u32* s32 = rows24 ? reinterpret_cast<const u32*>(g + (u32)(__mul24(reflect101(Y0 - LEFT + 32 * t + c_row[it], H), (int)gstride_row) + c_px[it]))
-                                        : reinterpret_cast<const u32*>(row_of(t, it) + c_px[it]);
-                stage[it] = make_uint4(s32[0], s32[1], s32[2], s32[3]);
-            }
-    };
-    auto commit = [&](int t, int buf) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            if (!c_on[it]) continue;
-            if (c_fast[it]) {
-                uint4 v = stage[it];
-                v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-                *reinterpret_cast<uint4*>(&tile[buf][c_lds[it]]) = v;
-            } else {
-                uint4 v = fetch_chunk_slow(row_of(t, it), c_px[it], W);
-                v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-                *reinterpret_cast<uint4*>(&tile[buf][c_lds[it]]) = v;
-            }
-        }
-    };
-
-    v4i rLh[NK], rLl[NK], rSh[NK], rSl[NK];            // ring of horizontal tiles: large / small kernel, hi / lo bytes
-#pragma unroll
-    for (int s = 0; s < NK; ++s) rLh[s] = rLl[s] = rSh[s] = rSl[s] = v4i{0, 0, 0, 0};
-    const int xw = X0 + 32 * wave;                     // first column of this wave's strip
-    u32* const bits32 = reinterpret_cast<u32*>(bits) + ((int64_t)n * H * WW + (xw >> 6)) * 2 + ((xw >> 5) & 1);   // (uniform)
-    const u32 colmask = xw + 32 <= W ? 0xFFFFFFFFu : (xw >= W ? 0u : ((1u << (W - xw)) - 1u));
-    // sum tap*H = 256*Dhi + Dlo + 256*(128 + 32768); + 2^15 to round; the large kernel also carries
-    // (15 - thresh) << 16 so that its high word is im_blur_8 + 15 - thresh (mod 2^16)
-    // (host computes k3 = 256*(128+32768) + 2^15, k8 = k3 + (15 - thresh) << 16, span = hi - thresh)
-    const u32 span = (u32)span_i;
-    u32 total = 0, pend_off = 0xFFFFFFFFu, pend_full = 0;
-
-    fetch(0);
-    commit(0, 0);
-    // every load issued so far (the operand fragments above all) has landed: without this the loop's first uses
-    // keep a vmcnt wait that, in steady state, stalls on the prefetch of the next tile instead
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0)
-    __syncthreads();
-    for (int t0 = 0; t0 < nsteps; t0 += NK) {
-#pragma unroll
-        for (int u = 0; u < NK; ++u) {
-            const int t = t0 + u;
-            if (t >= nsteps) break;                    // uniform
-            const bool more = t + 1 < nsteps;
-            if (more) fetch(t + 1);
-            const u8* tb = &tile[t & 1][m * STRIDE + 32 * wave + 16 * hh];
-            v4i a[NK];
-#pragma unroll
-            for (int s = 0; s < NK; ++s) a[s] = *reinterpret_cast<const v4i*>(tb + 32 * s);
-            {
-                v16i acc = {};
-#pragma unroll
-                for (int s = 0; s < NK; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bh[s], acc, 0, 0, 0);
-                pack_tile(acc, rLh[u], rLl[u]);
-            }
-            {
-                v16i acc = {};
-#pragma unroll
-                for (int s = 0; s < NKA; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[SA0 + s], bha[s], acc, 0, 0, 0);
-                pack_tile(acc, rSh[u], rSl[u]);
-            }
-            if (t >= NK - 1 && dbg != 2) {
-                v16i d8 = {}, d3 = {};
-#pragma unroll
-                for (int o = 0; o < NK; ++o) d8 = __builtin_amdgcn_mfma_i32_32x32x32_i8(rLh[(u + 1 + o) % NK], tv[o], d8, 0, 0, 0);
-#pragma unroll
-                for (int o = 0; o < NKA; ++o) d3 = __builtin_amdgcn_mfma_i32_32x32x32_i8(rSh[(u + 1 + SA0 + o) % NK], tva[o], d3, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) d8[i] = (d8[i] << 8) + k8;
-#pragma unroll
-                for (int o = 0; o < NK; ++o) d8 = __builtin_amdgcn_mfma_i32_32x32x32_i8(rLl[(u + 1 + o) % NK], tv[o], d8, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) d3[i] = (d3[i] << 8) + k3;
-#pragma unroll
-                for (int o = 0; o < NKA; ++o) d3 = __builtin_amdgcn_mfma_i32_32x32x32_i8(rSl[(u + 1 + SA0 + o) % NK], tva[o], d3, 0, 0, 0);
-                if (dbg == 1) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) asm volatile("" :: "v"(d8[i]), "v"(d3[i]));
-                } else {
-                u32 sgn = 0;                           // bit i = 1 when register i is OUT of range
-#pragma unroll
-                for (int i = 15; i >= 0; --i) {
-                    u32 dg = (((u32)d8[i] >> 16) - ((u32)d3[i] >> 16)) & 255u;   // (blur_8 - blur_3 + 15 - thresh) mod 256 (:128)
-                    sgn = __builtin_amdgcn_alignbit(sgn, span - dg, 31);
-                }
-                u32 w16 = ~sgn & 0xFFFFu;              // register i = column (i&3) + 8(i>>2) + 4*half
-                u32 w32 = ((w16 & 0xFu) | ((w16 & 0xF0u) << 4) | ((w16 & 0xF00u) << 8) | ((w16 & 0xF000u) << 12)) << (4 * hh);
-                const int y = Y0 + 32 * (t - (NK - 1)) + m;
-                w32 = (y < H) ? (w32 & colmask) : 0u;
-                u32 full = w32 | (u32)__shfl_xor((int)w32, 32);
-                if (hh == 0 && y < H && (xw >> 6) < WW) {    // stored behind this step's commit (below)
-                    pend_off = (u32)__mul24(y, 2 * WW);
-                    pend_full = full;
-                    total += __popc(full);
-                }
-                if (U8OUT && y < H) {                    // uint8 image for the staged API: 4 pixels per store where possible
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int x = xw + 8 * q + 4 * hh;
-                        const u32 nib = (w32 >> (8 * q + 4 * hh)) & 15u;
-                        const u32 four = ((nib * 0x00204081u) & 0x01010101u) * 0xFFu;      // bit r -> byte r = 0 / 255
-                        u8* dst = area_u8 + ((int64_t)n * H + y) * W + x;
-                        if (((W & 3) == 0) && x + 3 < W && ((reinterpret_cast<uintptr_t>(area_u8) & 3) == 0)) {
-                            *reinterpret_cast<u32*>(dst) = four;
-                        } else {
-                            for (int r = 0; r < 4; ++r)
-                                if (x + r < W) dst[r] = (u8)(four >> (8 * r));
-                        }
-                    }
-                }
-                }                                      // (dbg != 1)
-            }
-            if (more) commit(t + 1, (t + 1) & 1);
-            // The mask word goes out only now: issued before the commit, its acknowledgement would be part of the commit's
-            // wait for the prefetched rows, every step and for all four waves at the barrier.
-            if (pend_off != 0xFFFFFFFFu) { bits32[pend_off] = pend_full; pend_off = 0xFFFFFFFFu; }
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) total += __shfl_xor((int)total, off);
-    if (lane == 0 && total) atomicAdd(&fstat[n * 8 + 0], total);
-}
-
-// Toeplitz operand fragments in the lane layout of v_mfma_i32_32x32x32_i8 (lane = 32*half + column; a
-// lane's 16 bytes pair with the other operand's 16 bytes of the same half, so only the pairing matters):
-//   horizontal (B operand, k = pixel of the staged window): byte e of half h is window pixel 32s + 16h + e
-//   vertical   (B operand, k = row of ring tile o):         byte 4q + r of half h is tile row 8q + 4h + r
-std::vector<u32> blur_mfma_fragments(const std::vector<int>& taps_a, const std::vector<int>& taps_b, int nk,
-                                     int sa0, int nka) {
-    const int left = 32 * ((nk - 1) / 2);
-    std::vector<u32> out((size_t)(2 * nk + 2 * nka) * 64 * 4, 0);
-    auto fill = [&](int frag, const std::vector<int>& taps, int kbase, bool vertical) {
-        const int R = (int)taps.size() / 2;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int h = lane >> 5, col = lane & 31;
-            for (int e = 0; e < 16; ++e) {
-                int k = kbase + (vertical ? 8 * (e >> 2) + 4 * h + (e & 3) : 16 * h + e);
-                int idx = k - col - (left - R);
-                u32 v = (idx >= 0 && idx <= 2 * R) ? (u32)taps[idx] : 0u;
-                out[((size_t)frag * 64 + lane) * 4 + (e >> 2)] |= v << (8 * (e & 3));
-            }
-        }
-    };
-    for (int s = 0; s < nk; ++s) { fill(0 * nk + s, taps_b, 32 * s, false); fill(1 * nk + s, taps_b, 32 * s, true); }
-    for (int s = 0; s < nka; ++s) {
-        fill(2 * nk + s, taps_a, 32 * (sa0 + s), false);
-        fill(2 * nk + nka + s, taps_a, 32 * (sa0 + s), true);
-    }
-    return out;
-}
-
+#include "blur_common.h"
 
 // ---- strips of 16 columns ---------------------------------------------------------------------------
 // The same two products on v_mfma_i32_16x16x64_i8, one wave per 16-column strip sliding down 16 rows per step, for the
@@ -444,14 +59,6 @@ template <bool SB> struct B16 {
     static constexpr int NVF = SB ? 8 : 12;              // vertical fragment variants (ring phases of the two kernels)
     static constexpr int WG_LEFT = SB ? 32 : 64;         // the workgroup's window starts this far left of its first strip
 };
-#define B16_LEFT 56                                      // (large branch, host side)
-
-__device__ __forceinline__ void pack16(const v4i& acc, int& hi, int& lo) {
-    const u32 t01 = __builtin_amdgcn_perm((u32)acc[1], (u32)acc[0], 0x05010400u);
-    const u32 t23 = __builtin_amdgcn_perm((u32)acc[3], (u32)acc[2], 0x05010400u);
-    lo = (int)(__builtin_amdgcn_perm(t23, t01, 0x05040100u) ^ 0x80808080u);
-    hi = (int)__builtin_amdgcn_perm(t23, t01, 0x07060302u);
-}
 
 template <bool U8OUT, bool SB, bool SHIFT>               // SHIFT: widths that are 4 (mod 8) - the last workgroup's shifted origin
 __global__ __launch_bounds__(64 * (B16_NSW + 1), 4) void k_blur16(const u8* __restrict__ gray, int64_t gstride_n, int gstride_row,
@@ -845,50 +452,31 @@ static bool blur16_takes(const vbs_handle* h, const u8* gray, int64_t gstride_n,
            gstride_row >= h->W && gstride_row < (1 << 23) && (int64_t)h->H * gstride_row < (1ll << 31);
 }
 
-void launch_gray(vbs_handle* h, const u8* frames, int nb, int channels, int64_t stride_n,
-                 int64_t stride_row, u8* gray, hipStream_t s) {
-    const int vec_ok = (reinterpret_cast<uintptr_t>(frames) % 16 == 0) && (stride_n % 16 == 0) && (stride_row % 16 == 0);
-    const int flat = vec_ok && channels == 3 && stride_row == (int64_t)h->W * 3 && h->P == h->W && ((int64_t)h->H * h->W) % 16 == 0;
-    dim3 grid = flat ? dim3((unsigned)(((int64_t)h->H * h->W + 8191) / 8192), 1, nb)
-                     : dim3((unsigned)(((int64_t)h->H * (h->P / 16) + 255) / 256), 1, nb);
-    VBS_LAUNCH(h, s, "k_gray", k_gray, grid, dim3(256), 0, s, frames, channels, stride_n, stride_row, gray,
-                       h->H, h->W, h->P, gray_coef(h->gray_bits), vec_ok, flat);
-}
-
-void launch_blur(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
-                 u8* area_u8, hipStream_t s) {
+static void launch_blur16(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
+                          u8* area_u8, hipStream_t s) {
     const int k3 = 256 * (128 + 32768) + 32768, k8 = k3 + (15 - h->bp.thresh) * 65536;
-    if (blur16_takes(h, gray, gstride_n, gstride_row)) {
-        const int gx16 = (4 * h->WW + B16_NSW - 1) / B16_NSW, tiles16 = (h->H + 15) / 16;
-        int nseg = std::min(tiles16 / 8, std::max(1, (2048 + gx16 * nb - 1) / (gx16 * nb)));     // few frames: split the columns
-        nseg = std::max(nseg, 1);
-        if (VBS_KNOB("VBS_BLUR16_NSEG")) nseg = VBS_KNOB("VBS_BLUR16_NSEG");
-        const int tps = (tiles16 + nseg - 1) / nseg;
-        nseg = (tiles16 + tps - 1) / tps;
-        // many frames: a 1-D grid that the kernel maps to (frame, strip group, segment) with a frame's workgroups on one XCD
-        const int xcd = nb >= 32 ? nb : 0;
-        dim3 grid16 = xcd ? dim3((unsigned)((nb + 7) / 8 * 8 * gx16 * nseg)) : dim3(gx16, nseg, nb);
+    const int gx16 = (4 * h->WW + B16_NSW - 1) / B16_NSW, tiles16 = (h->H + 15) / 16;
+    int nseg = std::min(tiles16 / 8, std::max(1, (2048 + gx16 * nb - 1) / (gx16 * nb)));     // few frames: split the columns
+    nseg = std::max(nseg, 1);
+    if (VBS_KNOB("VBS_BLUR16_NSEG")) nseg = VBS_KNOB("VBS_BLUR16_NSEG");
+    const int tps = (tiles16 + nseg - 1) / nseg;
+    nseg = (tiles16 + tps - 1) / tps;
+    // many frames: a 1-D grid that the kernel maps to (frame, strip group, segment) with a frame's workgroups on one XCD
+    const int xcd = nb >= 32 ? nb : 0;
+    dim3 grid16 = xcd ? dim3((unsigned)((nb + 7) / 8 * 8 * gx16 * nseg)) : dim3(gx16, nseg, nb);
 #define B16_GO(U8, SB_, SH_)                                                                                                  \
     VBS_LAUNCH(h, s, "k_blur16", (k_blur16<U8, SB_, SH_>), grid16, dim3(64 * (B16_NSW + 1)), 0, s, gray, gstride_n,              \
                (int)gstride_row, h->blur16_h, h->blur16_v, w.area_bits, area_u8, w.fstat, h->H, h->W, h->WW, tps, k3, k8,     \
                h->bp.hi - h->bp.thresh, xcd, gx16, nseg, VBS_KNOB("VBS_BLUR16_DROP"))
 #define B16_GO2(U8, SB_) do { if (h->W & 7) B16_GO(U8, SB_, true); else B16_GO(U8, SB_, false); } while (0)
-        if (h->bp.small) { if (area_u8) B16_GO2(true, true); else B16_GO2(false, true); }
-        else { if (area_u8) B16_GO2(true, false); else B16_GO2(false, false); }
+    if (h->bp.small) { if (area_u8) B16_GO2(true, true); else B16_GO2(false, true); }
+    else { if (area_u8) B16_GO2(true, false); else B16_GO2(false, false); }
 #undef B16_GO2
 #undef B16_GO
-        return;
-    }
-    const int gx = (h->P + 127) / 128, tilesY = (h->H + 31) / 32;
-    int nseg = std::min(tilesY, std::max(1, (1024 + gx * nb - 1) / (gx * nb)));     // few frames: split columns
-    const int tps = (tilesY + nseg - 1) / nseg;
-    nseg = (tilesY + tps - 1) / tps;
-    dim3 grid(gx, nseg, nb);
-#define BLUR_GO(NK, SA0, NKA, U8)                                                                            \
-    VBS_LAUNCH(h, s, "k_blur_mfma", (k_blur_mfma<NK, SA0, NKA, U8>), grid, dim3(256), 0, s, gray, gstride_n, \
-               gstride_row, h->blur_frags, w.area_bits, area_u8, w.fstat, h->H, h->W, h->WW, tps, k3, k8,  \
-               h->bp.hi - h->bp.thresh, VBS_KNOB("VBS_BLUR_DBG"))
-    if (!h->bp.small) { if (area_u8) BLUR_GO(5, 1, 3, true); else BLUR_GO(5, 1, 3, false); }
-    else { if (area_u8) BLUR_GO(3, 0, 3, true); else BLUR_GO(3, 0, 3, false); }
-#undef BLUR_GO
+}
+
+void launch_blur(vbs_handle* h, Workspace& w, const u8* gray, int64_t gstride_n, int64_t gstride_row, int nb,
+                 u8* area_u8, hipStream_t s) {
+    if (blur16_takes(h, gray, gstride_n, gstride_row)) launch_blur16(h, w, gray, gstride_n, gstride_row, nb, area_u8, s);
+    else launch_blur_mfma(h, w, gray, gstride_n, gstride_row, nb, area_u8, s);
 }

@@ -10,224 +10,16 @@
 //     var = 255^2 c - 2 mu 255 c + n mu^2 - (255 c - n mu)^2 / l^2
 //     mask = num / sqrt(var * T2) > 0.1   <=>   var > 0, num > 0, num^2 > 0.01 var T2
 // k_ncc_mfma (the hot path): both passes as Toeplitz products on the float16 matrix cores, a filter in front of the
-//             float64 decision.  k_ncc: the float64 MAP of the diagnostic APIs, horizontal pass from bit runs into LDS.
+//             float64 decision.  k_ncc (k_ncc_map.hip): the float64 MAP of the diagnostic APIs.
 #include <algorithm>
-#include <cstdlib>
+#include <cstddef>
 #include <cstring>
+#include <type_traits>
 
-#include "common.h"
-
-__device__ __forceinline__ u64 load_bits(const u64* __restrict__ row, int WW, int start) {
-    int wi = start >> 6, sh = start & 63;
-    u64 a = (wi >= 0 && wi < WW) ? row[wi] : 0ull;
-    u64 b = (wi + 1 >= 0 && wi + 1 < WW) ? row[wi + 1] : 0ull;
-    return sh ? ((a >> sh) | (b << (64 - sh))) : a;
-}
-
-// Horizontal Gaussian sum of one pixel from the runs of 1-bits in its window (float64): a run [b, e) in
-// window coordinates contributes CG[e] - CG[b], CG the cumulative template factor.
-template <int L, int LO>
-__device__ __forceinline__ double ncc_row_exact(const u64* __restrict__ row, int WW, int x, const double* cg,
-                                                u32* cnt) {
-    u64 w0 = load_bits(row, WW, x + LO), w1 = 0;
-    if (L > 64) w1 = load_bits(row, WW, x + LO + 64) & ((1ull << (L > 64 ? L - 64 : 1)) - 1ull);
-    else w0 &= (1ull << (L < 64 ? L : 0)) - 1ull;
-    *cnt += __popcll(w0) + __popcll(w1);
-    double h = 0.0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        u64 w = half ? w1 : w0;
-        while (w) {
-            int b0 = __ffsll((long long)w) - 1;
-            u64 t = ~(w >> b0);
-            int len = t ? __ffsll((long long)t) - 1 : 64 - b0;
-            w &= (len >= 64) ? 0ull : ~(((1ull << len) - 1ull) << b0);
-            h += cg[half * 64 + b0 + len] - cg[half * 64 + b0];
-        }
-    }
-    return h;
-}
-
-// Exact float64 G(y, x) = sum_i g[i] H(y + LO + i, x), products added in ascending i.  Rare path (pixels the float32
-// filter cannot decide, or the diagnostic map): kept out of line so that its loops are not replicated 8x.
-template <int L, int LO>
-__device__ __attribute__((noinline)) double ncc_exact_G(const u64* fbits, int H, int WW, int y, int x, const double* cg,
-                                                        const double* gsh) {
-    u32 dummy = 0;
-    double Ge = 0.0;
-    for (int i = 0; i < L; ++i) {
-        int yy = y + LO + i;
-        double hrow = (yy >= 0 && yy < H) ? ncc_row_exact<L, LO>(fbits + (int64_t)yy * WW, WW, x, cg, &dummy) : 0.0;
-        Ge = __builtin_fma(gsh[i], hrow, Ge);
-    }
-    return Ge;
-}
-
-// One workgroup = 64 columns x 64 output rows.
-// Phase 1 fills LDS with the horizontal pass of the 64+L-1 rows the tile needs, 8 px per work item from one
-// shared bit window, computed in float64 from runs (2 table lookups per run instead of L multiply-adds) and
-// stored as float32.  Phase 2 is the vertical pass out of LDS in float32 (tap-outer, 8 rows per lane).
-// float32 is only a filter: with e = 1e-5 bounding the relative error of the float32 sum (80 positive
-// products, worst case (L+2) 2^-24 = 4.9e-6 plus the two input roundings), a pixel whose decision is the
-// same for G (1 - e) and G (1 + e) is decided; the others (a handful per frame, on the ncc = 0.1 contour)
-// recompute G in float64 straight from the bits (ncc_row_exact), so every decision equals the float64 one.
-template <int L, int LO>
-__global__ __launch_bounds__(256) void k_ncc(const u64* __restrict__ bits, const double* __restrict__ rx,
-                                             const double* __restrict__ ry, u64* __restrict__ mbits,
-                                             u8* __restrict__ mask_u8, double* __restrict__ ncc_out,
-                                             u32* __restrict__ fstat, int H, int W, int WW, int stop, NccConst nc) {
-    constexpr int RT = 64, HR = RT + L - 1, HI = L - 1 + LO;
-    __shared__ float hxs[HR][64];
-    __shared__ __attribute__((aligned(8))) u8 cxs[HR][64];
-    __shared__ double cg[L + 1];
-    __shared__ double gsh[L];
-    __shared__ float g32[L];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int x0 = blockIdx.x * 64, yb = blockIdx.y * RT, n = blockIdx.z;
-    const u64* fbits = bits + (int64_t)n * H * WW;
-    for (int i = tid; i <= L; i += 256) cg[i] = nc.cg[i];
-    for (int i = tid; i < L; i += 256) { gsh[i] = nc.g[i]; g32[i] = (float)nc.g[i]; }
-    __syncthreads();
-    // phase 1: work item = (row r, 8 consecutive columns); one 64+(L+7-64)-bit window serves all 8
-    for (int p = tid; p < HR * 8; p += 256) {
-        const int r = p >> 3, c8 = p & 7;
-        const int y = yb + LO + r, xs = x0 + 8 * c8;
-        double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        u64 packed = 0;
-        if (y >= 0 && y < H) {
-            const u64* row = fbits + (int64_t)y * WW;
-            const u64 w0 = load_bits(row, WW, xs + LO);
-            const u64 w1 = load_bits(row, WW, xs + LO + 64) & ((1ull << (L + 7 - 64 > 0 ? L + 7 - 64 : 1)) - 1ull) &
-                           (L + 7 > 64 ? ~0ull : 0ull);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                u64 lo = s ? ((w0 >> s) | (w1 << (64 - s))) : w0;
-                u32 c;
-                if (L >= 64) c = __popcll(lo) + __popcll((w1 >> s) & ((1ull << (L >= 64 ? L - 64 : 0)) - 1ull));
-                else c = __popcll(lo & ((1ull << (L < 64 ? L : 0)) - 1ull));
-                packed |= (u64)c << (8 * s);
-            }
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                u64 w = half ? w1 : ((L + 7 >= 64) ? w0 : (w0 & ((1ull << ((L + 7) & 63)) - 1ull)));
-                const int off = half * 64;
-                while (w) {
-                    int b0 = __ffsll((long long)w) - 1;
-                    u64 t = ~(w >> b0);
-                    int len = t ? __ffsll((long long)t) - 1 : 64 - b0;
-                    w &= (len >= 64) ? 0ull : ~(((1ull << len) - 1ull) << b0);
-                    const int rb = off + b0, re = rb + len;     // run [rb, re) in window coordinates
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) {
-                        // clip the run to window s = [s, s+L); an empty intersection gives cg[k] - cg[k] = 0
-                        int lo_ = min(max(rb, s), s + L), hi_ = max(min(re, s + L), lo_);
-                        h[s] += cg[hi_ - s] - cg[lo_ - s];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s) hxs[r][8 * c8 + s] = (float)h[s];
-        *reinterpret_cast<u64*>(&cxs[r][8 * c8]) = packed;
-    }
-    __syncthreads();
-    if (stop == 1) return;
-    const int x = x0 + lane;
-    const double mu = (double)(255ull * (u64)fstat[n * 8 + 0]) / (double)((int64_t)H * W);
-    u32 amb = 0, nexact = 0;
-    for (int oct = 0; oct < RT / 32; ++oct) {
-        const int r0 = wave * (RT / 4) + oct * 8;        // first LDS row of this lane's 8 output rows
-        const int y0 = yb + r0;
-        if (y0 >= H) break;                              // wave-uniform
-        const bool interior = (y0 + LO >= 0) && (y0 + 7 + HI <= H - 1) && (x0 + LO >= 0) && (x0 + 63 + HI <= W - 1);
-        const double full_t = ry[min(max(-LO, 0), H - 1)] * rx[min(max(-LO, 0), W - 1)];   // rows / columns with a full window
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        float vw[8];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) vw[i] = hxs[r0 + i][lane];
-#pragma unroll 1
-        for (int jb = 0; jb < L / 8; ++jb) {             // rolled: keeps the weights' live ranges to one block
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-                const int j = 8 * jb + jj;
-                vw[(jj + 7) & 7] = hxs[r0 + j + 7][lane];
-                const float gj = g32[j];                 // LDS broadcast read
-#pragma unroll
-                for (int s = 0; s < 8; ++s) acc[s] = __builtin_fmaf(gj, vw[(jj + s) & 7], acc[s]);
-            }
-        }
-#pragma unroll
-        for (int j = (L / 8) * 8; j < L; ++j) {          // tail taps (L = 33)
-            vw[(j + 7) & 7] = hxs[r0 + j + 7][lane];
-            const float gj = g32[j];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) acc[s] = __builtin_fmaf(gj, vw[(j + s) & 7], acc[s]);
-        }
-        u32 cs0 = 0, pre[8] = {0, 0, 0, 0, 0, 0, 0, 0}, post[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < L + 7; ++i) {
-            const u32 c = cxs[r0 + i][lane];
-            if (i < L) cs0 += c;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                if (i < s) pre[s] += c;                  // rows above window s
-                if (i >= L && i < L + s) post[s] += c;   // rows that window s gains
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int y = y0 + s;
-            bool pred = false;
-            if (y < H && x < W) {
-                double nn, sum_t;
-                if (interior) {                          // wave-uniform: every window of these 8 rows x 64 columns is
-                    nn = nc.l2; sum_t = full_t;          // inside the image, so n = l*l and sum_W t is the full sum
-                } else {
-                    int ny = min(y + HI, H - 1) - max(y + LO, 0) + 1;
-                    int nx = min(x + HI, W - 1) - max(x + LO, 0) + 1;
-                    nn = (double)(ny * nx);
-                    sum_t = ry[y] * rx[x];
-                }
-                double sum_I = 255.0 * (double)(cs0 - pre[s] + post[s]);
-                double rest = -nc.tbar * sum_I - mu * (sum_t - nn * nc.tbar);       // num = 255 G + rest
-                double s1 = sum_I - nn * mu;
-                double s2 = 255.0 * sum_I - 2.0 * mu * sum_I + nn * mu * mu;
-                double var = s2 - s1 * s1 * nc.inv_l2;
-                double rhs = nc.thr2 * var * nc.T2;
-                if (var > 0.0) {
-                    double G = (double)acc[s];
-                    double nlo = 255.0 * G * (1.0 - 1e-5) + rest, nhi = 255.0 * G * (1.0 + 1e-5) + rest;
-                    bool plo = (nlo > 0.0) && (nlo * nlo > rhs), phi = (nhi > 0.0) && (nhi * nhi > rhs);
-                    pred = plo;
-                    if (plo != phi || ncc_out) {          // undecided by float32 (or a map was asked for): exact
-                        const double Ge = ncc_exact_G<L, LO>(fbits, H, WW, y, x, cg, gsh);
-                        double num = 255.0 * Ge + rest;
-                        pred = (num > 0.0) && (num * num > rhs);
-                        if (var > 1e-6 && num > 0.0 && fabs(num * num - rhs) <= 1e-9 * rhs) amb++;
-                        nexact++;
-                        if (ncc_out) {                   // diagnostic map in the reference's form (:159-163)
-                            double v2 = s2 - s1 * s1 / nc.l2;
-                            double q = num / sqrt((v2 < 0.0 ? 0.0 : v2) * nc.T2);
-                            ncc_out[((int64_t)n * H + y) * W + x] = isfinite(q) ? q : 0.0;
-                        }
-                    }
-                } else if (ncc_out) {
-                    ncc_out[((int64_t)n * H + y) * W + x] = 0.0;      // 0/0 or x/0 -> non-finite -> 0 (:163)
-                }
-            }
-            u64 word = __ballot(pred);
-            if (y < H) {
-                if (lane == 0) mbits[((int64_t)n * H + y) * WW + blockIdx.x] = word;
-                if (mask_u8 && x < W) mask_u8[((int64_t)n * H + y) * W + x] = pred ? 1 : 0;
-            }
-        }
-    }
-    if (amb) atomicAdd(&fstat[n * 8 + 1], amb);
-    if (nexact) atomicAdd(&fstat[n * 8 + 3], nexact);
-}
+#include "ncc_common.h"
 
 // ---- matrix-core path ------------------------------------------------------------------------------
-// G and the window count c are banded-Toeplitz products, like the blurs (k_blur.hip), here in float16 operands
+// G and the window count c are banded-Toeplitz products, like the blurs (k_blur_mfma.hip, k_blur16.hip), here in float16 operands
 // with float32 accumulation on v_mfma_f32_16x16x32_f16:
 //   horizontal  h[y][x]  = sum_k b[y][xw+k] * w[k - x]          A = image bits expanded to 0.0 / 1.0 (exact),
 //               ch[y][x] = sum_k b[y][xw+k] * 1[k - x]          B = Toeplitz of w = 1024 g, split w = whi + wlo
@@ -250,25 +42,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
-#define NCC_WSCALE 1024.0                               // weights are scaled so that every wlo is a normal float16
-#define NCC_REL 2e-5f
-#define NCC_NEVER 3e38                                  // "no G reaches this" (finite, so G - theta stays ordered)
-#define NCC_ABS 1e-3f                                   // in units of G * 2^20: far below any theta with c >= 1
-
-// theta on 2^20 G for a window with c foreground and nn in-image samples (+inf where var <= 0)
-__device__ __forceinline__ double ncc_theta(double c, double nn, double sum_t, double mu, const NccConst& nc) {
-    double sum_I = 255.0 * c;
-    double rest = -nc.tbar * sum_I - mu * (sum_t - nn * nc.tbar);
-    double s1 = sum_I - nn * mu;
-    double s2 = 255.0 * sum_I - 2.0 * mu * sum_I + nn * mu * mu;
-    double var = s2 - s1 * s1 * nc.inv_l2;
-    double rhs = nc.thr2 * var * nc.T2;
-    if (!(var > 0.0)) return NCC_NEVER;
-    // an empty window has G = 0 exactly on both paths: decide it here
-    if (c == 0.0) return (rest > 0.0 && rest * rest > rhs) ? -NCC_NEVER : NCC_NEVER;
-    return (sqrt(rhs) - rest) * (NCC_WSCALE * NCC_WSCALE / 255.0);
-}
-
 typedef int i4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) u8 gl_u8;                  // global memory, stated (see load_rows)
 typedef __attribute__((address_space(1))) unsigned short gl_u16;
@@ -845,6 +618,20 @@ __global__ __launch_bounds__(256, 4) void k_ncc_mfma(const u64* __restrict__ bit
 }
 #undef wide
 
+// NccKArgs against the kernel: its members are the parameter list, type for type and in order (top-level __restrict__ is not
+// part of a function type, so the comparison is exact), and they lie where the kernarg segment puts them: ten pointers, five
+// ints and a float, then NccConst at its alignment of 8.  A parameter added, removed, retyped or moved fails the build here.
+using NccKernelFn = void (*)(decltype(NccKArgs::bits), decltype(NccKArgs::rx), decltype(NccKArgs::ry), decltype(NccKArgs::wfrag),
+                             decltype(NccKArgs::tab), decltype(NccKArgs::rowf), decltype(NccKArgs::mbits), decltype(NccKArgs::mask_u8),
+                             decltype(NccKArgs::fstat), decltype(NccKArgs::tot), decltype(NccKArgs::H), decltype(NccKArgs::W),
+                             decltype(NccKArgs::WW), decltype(NccKArgs::tiles_per_seg), decltype(NccKArgs::dbg_arg),
+                             decltype(NccKArgs::rel_arg), decltype(NccKArgs::nc));
+static_assert(std::is_same_v<decltype(&k_ncc_mfma<80, -40, true>), NccKernelFn> && std::is_same_v<decltype(&k_ncc_mfma<80, -40, false>), NccKernelFn> &&
+              std::is_same_v<decltype(&k_ncc_mfma<33, -16, true>), NccKernelFn> && std::is_same_v<decltype(&k_ncc_mfma<33, -16, false>), NccKernelFn>,
+              "NccKArgs does not mirror k_ncc_mfma's parameter list");
+static_assert(std::is_standard_layout_v<NccKArgs> && offsetof(NccKArgs, nc) == 104 && alignof(NccConst) == 8,
+              "NccKArgs does not lay out as the kernarg segment does");
+
 // Toeplitz fragments of k_ncc_mfma in the lane layout of v_mfma_f32_16x16x32_f16 (lane = 16 g + column, element j
 // pairs with the other operand's element j of the same g): weight index (32 s + 8 g + j) - column.  The same
 // fragments serve as B operand of the horizontal and as A operand of the vertical product.
@@ -876,146 +663,22 @@ std::vector<u32> ncc_mfma_fragments(const NccConst& nc, int l) {
     return out;
 }
 
-// ---- _normxcorr2 for ARBITRARY operands (marker_detection.py:146-164) -------------------------------------------------
-// Any float64 template / image, mode 'full' | 'same' | 'valid', evaluated directly in the spatial domain in float64
-// (the reference goes through three FFT convolutions; the two agree to the FFT's rounding, ~1e-12 of the map's scale).
-// Not on the hot path: the pipeline's own operands (binary area_mask, Gaussian template) take k_ncc_mfma / k_ncc.
-//   stats[0] = mean(template), stats[1] = mean(image), stats[2] = sum((template - mean)^2)
-__global__ __launch_bounds__(1024) void k_nccg_stats(const double* __restrict__ T, int nt, const double* __restrict__ I, int ni,
-                                                     double* __restrict__ stats) {
-    __shared__ double part[1024];
-    const int tid = threadIdx.x;
-    auto block_sum = [&](double v) {                    // fixed order: the result does not depend on scheduling
-        part[tid] = v;
-        __syncthreads();
-        for (int s = 512; s > 0; s >>= 1) { if (tid < s) part[tid] += part[tid + s]; __syncthreads(); }
-        const double r = part[0];
-        __syncthreads();
-        return r;
-    };
-    double a = 0;
-    for (int i = tid; i < nt; i += 1024) a += T[i];
-    const double mt = block_sum(a) / (double)nt;
-    a = 0;
-    for (int i = tid; i < ni; i += 1024) a += I[i];
-    const double mi = block_sum(a) / (double)ni;
-    a = 0;
-    for (int i = tid; i < nt; i += 1024) { const double d = T[i] - mt; a += d * d; }
-    const double t2 = block_sum(a);
-    if (tid == 0) { stats[0] = mt; stats[1] = mi; stats[2] = t2; }
-}
-
-// block = 8 output rows x 64 output columns; for every template row the image rows under it are staged in LDS
-#define NCCG_MAXTW 256
-__global__ __launch_bounds__(512) void k_nccg(const double* __restrict__ T, int th, int tw, const double* __restrict__ I, int h,
-                                              int w, int oy, int ox, int oh, int ow, const double* __restrict__ stats,
-                                              double* __restrict__ out) {
-    __shared__ double rows[8][64 + NCCG_MAXTW];
-    __shared__ double trow[NCCG_MAXTW];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int x = blockIdx.x * 64 + tx, y = blockIdx.y * 8 + ty;
-    const double mt = stats[0], mi = stats[1], t2 = stats[2];
-    double s_it = 0, s_i = 0, s_ii = 0;
-    for (int u = 0; u < th; ++u) {
-        __syncthreads();
-        const int yy = y + oy + u;
-        for (int k = tx; k < 64 + tw - 1; k += 64) {
-            const int xx = blockIdx.x * 64 + ox + k;
-            rows[ty][k] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? I[(int64_t)yy * w + xx] - mi : 0.0;   // zero padding AFTER
-        }                                                                                                  // the mean went
-        for (int k = threadIdx.x; k < tw; k += 512) trow[k] = T[(int64_t)u * tw + k] - mt;
-        __syncthreads();
-        for (int v = 0; v < tw; ++v) {
-            const double iv = rows[ty][tx + v];
-            s_it = __builtin_fma(iv, trow[v], s_it);
-            s_i += iv;
-            s_ii = __builtin_fma(iv, iv, s_ii);
-        }
-    }
-    if (x >= ow || y >= oh) return;
-    double var = s_ii - s_i * s_i / ((double)th * (double)tw);
-    if (var < 0.0) var = 0.0;
-    double r = s_it / sqrt(var * t2);
-    if (!isfinite(r)) r = 0.0;
-    out[(int64_t)y * ow + x] = r;
-}
-
-int launch_ncc_general(const double* T, int th, int tw, const double* I, int h, int w, int mode, double* out,
-                       double* stats, hipStream_t s) {
-    if (tw > NCCG_MAXTW) return VBS_EINVAL;
-    // scipy.signal.fftconvolve output window: 0 full, 1 same (size of the image, start (t - 1) // 2), 2 valid
-    const int sy = mode == 0 ? 0 : mode == 1 ? (th - 1) / 2 : th - 1, sx = mode == 0 ? 0 : mode == 1 ? (tw - 1) / 2 : tw - 1;
-    const int oh = mode == 0 ? h + th - 1 : mode == 1 ? h : h - th + 1, ow = mode == 0 ? w + tw - 1 : mode == 1 ? w : w - tw + 1;
-    if (oh < 1 || ow < 1) return VBS_EINVAL;
-    hipLaunchKernelGGL(k_nccg_stats, dim3(1), dim3(1024), 0, s, T, th * tw, I, h * w, stats);
-    hipLaunchKernelGGL(k_nccg, dim3((ow + 63) / 64, (oh + 7) / 8), dim3(512), 0, s, T, th, tw, I, h, w, sy - (th - 1),
-                       sx - (tw - 1), oh, ow, stats, out);
-    return VBS_OK;
-}
-
-// area popcount per frame (feeds the global mean of _normxcorr2 :153) when the bits did not come from k_blur_v
-__global__ __launch_bounds__(256) void k_popcount(const u64* __restrict__ bits, u32* __restrict__ fstat, int NW) {
-    __shared__ u32 part[4];
-    const int n = blockIdx.x;
-    u32 c = 0;
-    for (int i = threadIdx.x; i < NW; i += 256) c += __popcll(bits[(int64_t)n * NW + i]);
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) fstat[n * 8 + 0] = part[0] + part[1] + part[2] + part[3];
-}
-
-// running totals over every internal pass since the last vbs_ncc_counters(reset): {pixels within the ambiguity band of
-// the 0.1 threshold, pixels re-evaluated in float64, frames}
-__global__ __launch_bounds__(256) void k_stat_accum(const u32* __restrict__ fstat, u64* __restrict__ tot, int nb) {
-    u64 a = 0, e = 0;
-    for (int n = blockIdx.x * 256 + threadIdx.x; n < nb; n += gridDim.x * 256) { a += fstat[n * 8 + 1]; e += fstat[n * 8 + 3]; }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); e += __shfl_xor(e, off); }
-    if ((threadIdx.x & 63) == 0) {
-        if (a) atomicAdd(&tot[0], a);
-        if (e) atomicAdd(&tot[1], e);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&tot[2], (u64)nb);
-}
-
-static void launch_stat_accum(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_stat_accum", k_stat_accum, dim3(1), dim3(256), 0, s, w.fstat, w.ncc_tot, nb);
-}
-
-void launch_popcount(vbs_handle* h, Workspace& w, int nb, hipStream_t s) {
-    VBS_LAUNCH(h, s, "k_popcount", k_popcount, dim3(nb), dim3(256), 0, s, w.area_bits, w.fstat, h->H * h->WW);
-}
-
-void launch_ncc(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, double* ncc_out, hipStream_t s) {
-    if (!ncc_out && !VBS_KNOB("VBS_NCC_VALU")) {
-        const int tilesY = (h->H + 15) / 16;
-        // few frames: split the columns - into as many segments as keep every workgroup resident at once (256 CUs x 4): a
-        // second, partly filled round costs a one-frame call more than the longer segments (21.0 -> 18.1 us at 1280x1024)
-        const int want = h->WW * nb <= 512 ? 1024 : 2048;
-        int nseg = std::min(tilesY, std::max(1, want == 1024 ? want / (h->WW * nb) : (want + h->WW * nb - 1) / (h->WW * nb)));
-        if (VBS_KNOB("VBS_NCC_NSEG")) nseg = VBS_KNOB("VBS_NCC_NSEG");
-        const int tps = (tilesY + nseg - 1) / nseg;
-        nseg = (tilesY + tps - 1) / tps;
-        dim3 grid(h->WW, nseg, nb);
+void launch_ncc_mfma(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, hipStream_t s) {
+    const int tilesY = (h->H + 15) / 16;
+    // few frames: split the columns - into as many segments as keep every workgroup resident at once (256 CUs x 4): a
+    // second, partly filled round costs a one-frame call more than the longer segments (21.0 -> 18.1 us at 1280x1024)
+    const int want = h->WW * nb <= 512 ? 1024 : 2048;
+    int nseg = std::min(tilesY, std::max(1, want == 1024 ? want / (h->WW * nb) : (want + h->WW * nb - 1) / (h->WW * nb)));
+    if (VBS_KNOB("VBS_NCC_NSEG")) nseg = VBS_KNOB("VBS_NCC_NSEG");
+    const int tps = (tilesY + nseg - 1) / nseg;
+    nseg = (tilesY + tps - 1) / tps;
+    dim3 grid(h->WW, nseg, nb);
 #define NCC_GO(L_, LO_, U8)                                                                                      \
     VBS_LAUNCH(h, s, "k_ncc_mfma", (k_ncc_mfma<L_, LO_, U8>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx,     \
                h->ncc_ry, h->ncc_frags, h->ncc_tab, h->ncc_rowf, w.mask_bits, mask_u8, w.fstat, w.ncc_tot,       \
                h->H, h->W, h->WW, tps,                                                                           \
                VBS_KNOB("VBS_NCC_DBG"), std::max(NCC_REL, 1e-6f * (float)h->ncc_margin_ppm), h->ncc)
-        if (!h->bp.small) { if (mask_u8) NCC_GO(80, -40, true); else NCC_GO(80, -40, false); }
-        else { if (mask_u8) NCC_GO(33, -16, true); else NCC_GO(33, -16, false); }
+    if (!h->bp.small) { if (mask_u8) NCC_GO(80, -40, true); else NCC_GO(80, -40, false); }
+    else { if (mask_u8) NCC_GO(33, -16, true); else NCC_GO(33, -16, false); }
 #undef NCC_GO
-        return;
-    }
-    dim3 grid(h->WW, (h->H + 63) / 64, nb);
-    const int stop = VBS_KNOB("VBS_NCC_STOP");
-    if (!h->bp.small) {
-        VBS_LAUNCH(h, s, "k_ncc", (k_ncc<80, -40>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx, h->ncc_ry,
-                   w.mask_bits, mask_u8, ncc_out, w.fstat, h->H, h->W, h->WW, stop, h->ncc);
-    } else {
-        VBS_LAUNCH(h, s, "k_ncc", (k_ncc<33, -16>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx, h->ncc_ry,
-                   w.mask_bits, mask_u8, ncc_out, w.fstat, h->H, h->W, h->WW, stop, h->ncc);
-    }
-    launch_stat_accum(h, w, nb, s);                         // (k_ncc_mfma adds to the running totals itself)
 }
