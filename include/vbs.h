@@ -334,6 +334,43 @@ int vbs_pnp_ransac(int device, const double* world, int n_points, const double* 
                    double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
                    int32_t* inlier_count, uint8_t* inlier_mask, double* errors, int32_t* winner, void* stream);
 
+/* ---- Intrinsic calibration (code/Marker_Calibration/intrinsic_calibration.py) ---------------------------------------------------
+ * vbs_calibrate_camera - cv2.calibrateCamera(obj_points, img_points, img_size, None, None) (intrinsic_calibration.py:97-98) for one
+ * planar board seen in n_views views, as n_problems problems at once that each use a subset of the views (all of them, each one
+ * left out, random subsets) and share the corners.  No handle needed, nothing is allocated: the homographies are an output.
+ *   obj [dev] float64 [n_points,2]: the board, Z = 0; 4 <= n_points <= VBS_CHESS_MAX_PATTERN;
+ *   img [dev] float64 [n_views,n_points,2]: the corners of every view; 1 <= n_views <= VBS_CALIB_MAX_VIEWS;
+ *   view_mask [dev] uint8 [n_problems,n_views] or NULL: problem b uses the views with a non-zero entry (NULL: every problem uses
+ *     all views); w, h: the image size (the initial principal point is its centre); max_iter >= 1 (cv2: 30).
+ * Every view, once per call: homography by Hartley-normalised normal equations with h33 = 1 (the 8 x 8 elimination of
+ * vbs_pnp_ransac), then 5 Gauss-Newton steps on the transfer error.  VOID when a pivot falls below 1e-9 of the largest entry
+ * or the corners lie on one line (determinant of their scatter below 1e-9 of the product of its diagonal).
+ *   homography [dev] float64 [n_views,9] (NaN where void), view_void [dev] int32 [n_views] (outputs).
+ * Every problem: cv2's closed form for a planar target with flags = 0 (cx, cy at the centre; 1 / fx^2, 1 / fy^2 from two rows per
+ * view, 2 x 2 normal equations summed in view order; recalled from cvInitIntrinsicParams2D, unverified: DESIGN.md 7), a pose per
+ * view from K^-1 H, then Levenberg-Marquardt on the pixel error of every corner of the active views over fx fy cx cy k1 k2 p1 p2
+ * k3 and 6 pose parameters per view (left-multiplied rotation update), damping lambda diag from 1e-3, / 10 on an accepted step,
+ * x 10 on a rejected one, until max_iter steps were tried or the largest step component falls below 1e-11.
+ *   status [dev] int32 [n_problems]: VBS_OK, VBS_CALIB_FEW_VIEWS (fewer than 3 active views, :92) or VBS_CALIB_DEGENERATE (an
+ *     active view is void; the closed form is singular or gives a non-positive 1 / f^2; a pose puts the board behind the camera;
+ *     no damping up to 1e10 factorises).  A failed problem has NaN outputs and does not touch its neighbours.
+ *   K4 [dev] float64 [n_problems,4] = fx fy cx cy; dist [dev] float64 [n_problems,5] = k1 k2 p1 p2 k3 (cv2's order);
+ *   R [dev] float64 [n_problems,n_views,9], T [dev] float64 [n_problems,n_views,3]: board to camera, NaN for inactive views;
+ *   rms [dev] float64 [n_problems] = sqrt(sum |e|^2 / points), cv2's return value; view_rms [dev] float64 [n_problems,n_views];
+ *   std_intrinsics [dev] float64 [n_problems,9] = sqrt(sigma^2 diag S^-1) at the optimum, sigma^2 = sum e^2 / (2 points -
+ *     parameters), S = the Schur complement of the pose blocks in J^T J (NaN without degrees of freedom);
+ *   iterations [dev] int32 [n_problems]: steps tried (accepted or rejected).
+ * Float64, no atomics, sums ordered by the position in the list of active views: two runs give the same bits, and a masked
+ * problem gives the bits of the same views passed alone.  Checks before the device is touched: VBS_EINVAL (a null pointer other
+ * than view_mask, n_points < 4, n_views, n_problems, w, h or max_iter < 1), VBS_ECAPACITY beyond either cap. */
+#define VBS_CALIB_MAX_VIEWS   64
+#define VBS_CALIB_FEW_VIEWS    1
+#define VBS_CALIB_DEGENERATE   2
+int vbs_calibrate_camera(int device, const double* obj, int n_points, const double* img, int n_views, const uint8_t* view_mask,
+                         int n_problems, int w, int h, int max_iter, double* homography, int32_t* view_void, int32_t* status,
+                         double* K4, double* dist, double* R, double* T, double* rms, double* view_rms, double* std_intrinsics,
+                         int32_t* iterations, void* stream);
+
 /* MarkerTracker._marker_center (marker_detection.py:166-249): band = mask AND NOT erode(mask)
  * (maximum/minimum_filter :171-174) -> 4-connected labels (:176) -> centroids (:181); 5x5 open
  * (:195) -> external contours (:196) -> fitEllipse (:208) -> contour/centre matching (:222-243).

@@ -14,6 +14,7 @@ SERIES_CHUNK, SERIES_REC_COLS, STATS_COLS, WINDOW_COLS = 32, 5, 5, 4
 DIAM_COLS, DIAM_STATS_COLS, DIAM_MAX_EXTENT = 24, 5, 512
 PNP_SAMPLE, PNP_MAX_POINTS, PNP_MAX_HYPOTHESES, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS = 6, 1024, 4096, 1, 2
 CHESS_MAX_CANDIDATES, CHESS_MAX_PATTERN, CHESS_MAX_WIN = 256, 256, 15
+CALIB_MAX_VIEWS, CALIB_FEW_VIEWS, CALIB_DEGENERATE = 64, 1, 2
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -27,7 +28,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_series_chunks", "vbs_series_stats", "vbs_series_stats_f64", "vbs_series_partial", "vbs_series_merge",
            "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device",
            "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers", "vbs_pnp_ransac",
-           "vbs_chess_workspace", "vbs_chess_corners", "vbs_corner_subpix")
+           "vbs_chess_workspace", "vbs_chess_corners", "vbs_corner_subpix", "vbs_calibrate_camera")
 
 
 class Camera(C.Structure):
@@ -128,6 +129,7 @@ def lib():
         "vbs_chess_workspace": (i64, [i32, i32, i32]),
         "vbs_chess_corners": (i32, [i32, vp, i32, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "vbs_corner_subpix": (i32, [i32, vp, i32, i32, i32, i64, i64, vp, i32, i32, i32, i32, i32, i32, f64, vp, vp]),
+        "vbs_calibrate_camera": (i32, [i32, vp, i32, vp, i32, vp, i32, i32, i32, i32] + [vp] * 12),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

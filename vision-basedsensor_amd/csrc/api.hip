@@ -555,6 +555,20 @@ extern "C" int vbs_pnp_ransac(int device, const double* world, int n_points, con
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+extern "C" int vbs_calibrate_camera(int device, const double* obj, int n_points, const double* img, int n_views,
+                                    const uint8_t* view_mask, int n_problems, int w, int h, int max_iter, double* homography,
+                                    int32_t* view_void, int32_t* status, double* K4, double* dist, double* R, double* T, double* rms,
+                                    double* view_rms, double* std_intrinsics, int32_t* iterations, void* stream) {
+    if (!obj || !img || !homography || !view_void || !status || !K4 || !dist || !R || !T || !rms || !view_rms || !std_intrinsics ||
+        !iterations || n_points < 4 || n_views < 1 || n_problems < 1 || w < 1 || h < 1 || max_iter < 1)
+        return VBS_EINVAL;
+    if (n_views > VBS_CALIB_MAX_VIEWS || n_points > VBS_CHESS_MAX_PATTERN) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_calib(obj, n_points, img, n_views, view_mask, n_problems, w, h, max_iter, homography, view_void, status, K4, dist, R, T,
+                 rms, view_rms, std_intrinsics, iterations, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 extern "C" int64_t vbs_chess_workspace(int n, int h, int w) {
     if (n < 0 || h < 1 || w < 1 || h > 16384 || w > 16384) return VBS_EINVAL;
     return (int64_t)chess_workspace_bytes(n, h, w);

@@ -237,6 +237,10 @@ void launch_disp_from_frame(vbs_handle* h, const float* table, int n, int m_ref,
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
                 int32_t* inlier_count, u8* inlier_mask, double* errors, int32_t* winner, hipStream_t s);
+// k_calib.hip (f9): homographies of nv views, then nb calibration problems over subsets of them
+void launch_calib(const double* obj, int n, const double* img, int nv, const u8* view_mask, int nb, int w, int h, int max_iter,
+                  double* H, int32_t* view_void, int32_t* status, double* K4, double* dist, double* R, double* T, double* rms,
+                  double* view_rms, double* std_intrinsics, int32_t* iterations, hipStream_t s);
 // k_chess.hip (f8): response + candidates + ordering + the finder's own refinement; the refinement alone
 size_t chess_workspace_bytes(int n, int h, int w);
 void launch_chess(const u8* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row, int pw, int ph, double* corners,

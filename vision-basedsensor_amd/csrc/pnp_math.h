@@ -18,13 +18,9 @@
 
 struct PnpCam { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
 
-// Rodrigues matrix of w, left-multiplied onto (R, t): R <- E R, t <- E t + dt
-PNP_HD void pnp_apply_step(const double d[6], double R[9], double t[3]) {
+// E = I + a [w]x + b [w]x^2 left-multiplied onto (R, t): R <- E R, t <- E t + dt.  th2 = |w|^2; a, b = the Rodrigues coefficients
+PNP_HD void pnp_apply_rotation(const double d[6], double th2, double a, double b, double R[9], double t[3]) {
     const double wx = d[0], wy = d[1], wz = d[2];
-    const double th2 = wx * wx + wy * wy + wz * wz;
-    const double th = sqrt(th2);
-    double a = 1.0, b = 0.5;
-    if (th > 1e-12) { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
     // E = I + a [w]x + b [w]x^2,   [w]x^2 = w w^T - th2 I
     double E[9];
     E[0] = 1.0 + b * (wx * wx - th2); E[1] = b * (wx * wy) - a * wz;    E[2] = b * (wx * wz) + a * wy;
@@ -41,6 +37,16 @@ PNP_HD void pnp_apply_step(const double d[6], double R[9], double t[3]) {
     for (int i = 0; i < 9; ++i) R[i] = Rn[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) t[i] = tn[i];
+}
+
+// Rodrigues matrix of w, left-multiplied onto (R, t): R <- E R, t <- E t + dt
+PNP_HD void pnp_apply_step(const double d[6], double R[9], double t[3]) {
+    const double wx = d[0], wy = d[1], wz = d[2];
+    const double th2 = wx * wx + wy * wy + wz * wz;
+    const double th = sqrt(th2);
+    double a = 1.0, b = 0.5;
+    if (th > 1e-12) { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
+    pnp_apply_rotation(d, th2, a, b, R, t);
 }
 
 PNP_HD void pnp_to_camera(const double R[9], const double t[3], double X, double Y, double Z, double Pc[3]) {
@@ -162,22 +168,10 @@ PNP_HD bool pnp_pixel_jacobian(const PnpCam& c, const double R[9], const double 
     return true;
 }
 
-// The minimal solver of one hypothesis.  W = world [n][3], (xn, yn) = normalised image points, s = the 6 sample indices
-// (distinct, valid).  Planar homography of the first four (Z ignored) -> pose -> PNP_GN_STEPS Gauss-Newton steps on all six with
-// their true Z, residuals in normalised coordinates.  False = void.  *cond (may be null) = smallest |pivot| of the 8 x 8
-// elimination over the largest |entry| of the system: what the test helper rates the conditioning by.
-PNP_HD bool pnp_minimal(const double* W, const double* xn, const double* yn, const int s[PNP_SAMPLE], double R[9], double t[3],
-                        double* cond) {
-    double A[8][9];
+// A h = A[.][8] for the 8 x 9 augmented system A (destroyed): Gaussian elimination with partial pivoting.  False = void: a pivot
+// below 1e-9 of the largest |entry|.  *cond (may be null) = smallest |pivot| over the largest |entry|.
+PNP_HD bool pnp_eliminate8(double A[8][9], double h[8], double* cond) {
     double amax = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const double X = W[3 * s[p]], Y = W[3 * s[p] + 1], x = xn[s[p]], y = yn[s[p]];
-        A[2 * p][0] = X; A[2 * p][1] = Y; A[2 * p][2] = 1.0; A[2 * p][3] = 0.0; A[2 * p][4] = 0.0; A[2 * p][5] = 0.0;
-        A[2 * p][6] = -(x * X); A[2 * p][7] = -(x * Y); A[2 * p][8] = x;
-        A[2 * p + 1][0] = 0.0; A[2 * p + 1][1] = 0.0; A[2 * p + 1][2] = 0.0; A[2 * p + 1][3] = X; A[2 * p + 1][4] = Y; A[2 * p + 1][5] = 1.0;
-        A[2 * p + 1][6] = -(y * X); A[2 * p + 1][7] = -(y * Y); A[2 * p + 1][8] = y;
-    }
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -212,7 +206,6 @@ PNP_HD bool pnp_minimal(const double* W, const double* xn, const double* yn, con
     }
     if (cond) *cond = pmin / amax;
     if (!(pmin > 1e-9 * amax)) return false;
-    double h[8];
 #pragma unroll
     for (int i = 7; i >= 0; --i) {
         double v = A[i][8];
@@ -220,6 +213,43 @@ PNP_HD bool pnp_minimal(const double* W, const double* xn, const double* yn, con
         for (int j = i + 1; j < 8; ++j) v = v - A[i][j] * h[j];
         h[i] = v / A[i][i];
     }
+    return true;
+}
+
+// M <- the nearest rotation = its polar factor, by Newton's iteration M <- (M + M^-T) / 2; false when M loses its orientation
+PNP_HD bool pnp_polar(double M[9]) {
+    bool ok = true;
+#pragma unroll 1
+    for (int it = 0; it < PNP_POLAR_STEPS; ++it) {
+        double C[9];
+        C[0] = M[4] * M[8] - M[5] * M[7]; C[1] = M[5] * M[6] - M[3] * M[8]; C[2] = M[3] * M[7] - M[4] * M[6];
+        C[3] = M[2] * M[7] - M[1] * M[8]; C[4] = M[0] * M[8] - M[2] * M[6]; C[5] = M[1] * M[6] - M[0] * M[7];
+        C[6] = M[1] * M[5] - M[2] * M[4]; C[7] = M[2] * M[3] - M[0] * M[5]; C[8] = M[0] * M[4] - M[1] * M[3];
+        const double det = (M[0] * C[0] + M[1] * C[1]) + M[2] * C[2];
+        if (!(det > 1e-12)) { ok = false; break; }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) M[i] = 0.5 * (M[i] + C[i] / det);
+    }
+    return ok;
+}
+
+// The minimal solver of one hypothesis.  W = world [n][3], (xn, yn) = normalised image points, s = the 6 sample indices
+// (distinct, valid).  Planar homography of the first four (Z ignored) -> pose -> PNP_GN_STEPS Gauss-Newton steps on all six with
+// their true Z, residuals in normalised coordinates.  False = void.  *cond (may be null) = smallest |pivot| of the 8 x 8
+// elimination over the largest |entry| of the system: what the test helper rates the conditioning by.
+PNP_HD bool pnp_minimal(const double* W, const double* xn, const double* yn, const int s[PNP_SAMPLE], double R[9], double t[3],
+                        double* cond) {
+    double A[8][9];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const double X = W[3 * s[p]], Y = W[3 * s[p] + 1], x = xn[s[p]], y = yn[s[p]];
+        A[2 * p][0] = X; A[2 * p][1] = Y; A[2 * p][2] = 1.0; A[2 * p][3] = 0.0; A[2 * p][4] = 0.0; A[2 * p][5] = 0.0;
+        A[2 * p][6] = -(x * X); A[2 * p][7] = -(x * Y); A[2 * p][8] = x;
+        A[2 * p + 1][0] = 0.0; A[2 * p + 1][1] = 0.0; A[2 * p + 1][2] = 0.0; A[2 * p + 1][3] = X; A[2 * p + 1][4] = Y; A[2 * p + 1][5] = 1.0;
+        A[2 * p + 1][6] = -(y * X); A[2 * p + 1][7] = -(y * Y); A[2 * p + 1][8] = y;
+    }
+    double h[8];
+    if (!pnp_eliminate8(A, h, cond)) return false;
     // H = (h0 h1 h2 ; h3 h4 h5 ; h6 h7 1) ~ (r1 r2 t)
     const double n1 = sqrt((h[0] * h[0] + h[3] * h[3]) + h[6] * h[6]);
     const double n2 = sqrt((h[1] * h[1] + h[4] * h[4]) + h[7] * h[7]);
@@ -233,20 +263,8 @@ PNP_HD bool pnp_minimal(const double* W, const double* xn, const double* yn, con
     M[2] = M[3] * M[7] - M[6] * M[4];
     M[5] = M[6] * M[1] - M[0] * M[7];
     M[8] = M[0] * M[4] - M[3] * M[1];
-    // nearest rotation = the polar factor, by Newton's iteration M <- (M + M^-T) / 2
+    if (!pnp_polar(M)) return false;
     bool ok = true;
-#pragma unroll 1
-    for (int it = 0; it < PNP_POLAR_STEPS; ++it) {
-        double C[9];
-        C[0] = M[4] * M[8] - M[5] * M[7]; C[1] = M[5] * M[6] - M[3] * M[8]; C[2] = M[3] * M[7] - M[4] * M[6];
-        C[3] = M[2] * M[7] - M[1] * M[8]; C[4] = M[0] * M[8] - M[2] * M[6]; C[5] = M[1] * M[6] - M[0] * M[7];
-        C[6] = M[1] * M[5] - M[2] * M[4]; C[7] = M[2] * M[3] - M[0] * M[5]; C[8] = M[0] * M[4] - M[1] * M[3];
-        const double det = (M[0] * C[0] + M[1] * C[1]) + M[2] * C[2];
-        if (!(det > 1e-12)) { ok = false; break; }
-#pragma unroll
-        for (int i = 0; i < 9; ++i) M[i] = 0.5 * (M[i] + C[i] / det);
-    }
-    if (!ok) return false;
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = M[i];
 #pragma unroll 1

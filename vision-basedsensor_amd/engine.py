@@ -608,6 +608,77 @@ def pnp_ransac(world, image_or_table, cam: L.Camera, iterations: int = 1000, rep
     return out
 
 
+def _board_and_corners(obj_points, img_points, dev):
+    """cv2's list-of-arrays layout, stacked arrays or device tensors -> (board [N,2], corners [V,N,2]) float64 on `dev`."""
+    if isinstance(img_points, torch.Tensor):
+        img = img_points.to(device=dev, dtype=torch.float64)
+    else:
+        img = torch.as_tensor(np.stack([np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in img_points]), device=dev)
+    if img.dim() == 4 and img.shape[2] == 1:
+        img = img[:, :, 0]
+    if img.dim() != 3 or img.shape[2] != 2:
+        raise ValueError("img_points must be V arrays of [N,1,2] or [N,2] corners")
+    if isinstance(obj_points, torch.Tensor):
+        obj = obj_points.to(device=dev, dtype=torch.float64)
+    elif isinstance(obj_points, np.ndarray) and obj_points.ndim == 2:
+        obj = torch.as_tensor(obj_points.astype(np.float64), device=dev)
+    else:
+        views = [np.asarray(o, dtype=np.float64).reshape(len(o), -1) for o in obj_points]
+        if len(views) != img.shape[0] or any(o.shape != views[0].shape or not np.array_equal(o, views[0]) for o in views):
+            raise ValueError("obj_points must hold the same board once per view")
+        obj = torch.as_tensor(views[0], device=dev)
+    if obj.dim() == 3:
+        if obj.shape[0] != img.shape[0] or not bool((obj == obj[:1]).all()):
+            raise ValueError("obj_points must hold the same board once per view")
+        obj = obj[0]
+    if obj.dim() != 2 or obj.shape[1] not in (2, 3) or obj.shape[0] != img.shape[1]:
+        raise ValueError(f"obj_points must be [{img.shape[1]},3] (or [.,2]) board points")
+    if obj.shape[1] == 3:
+        if bool((obj[:, 2] != 0).any()):
+            raise ValueError("obj_points must be one planar board with Z = 0")
+        obj = obj[:, :2]
+    return obj.contiguous(), img.contiguous()
+
+
+def calibrate_camera_points(obj_points, img_points, img_size, view_mask=None, max_iter: int = 30, device=None):
+    """`cv2.calibrateCamera(obj_points, img_points, img_size, None, None)` (`intrinsic_calibration.py:97-98`) on the GPU
+    (`vbs_calibrate_camera`) for one planar board, as a batch of problems over subsets of its views.
+    obj_points: cv2's list of [N,3] float32 arrays - which must all be the same board with Z = 0 - or one [N,3] / [N,2] array;
+    img_points: a list of [N,1,2] / [N,2] corners per view, or a stacked array / device tensor [V,N,2]; img_size = (width, height);
+    view_mask: optional [B,V] (or [V]) - problem b uses the views with a non-zero entry; None = one problem over all views.
+    Returns a dict of device tensors: status [B], K4 [B,4], dist [B,5], R [B,V,3,3], T [B,V,3], rms [B], view_rms [B,V],
+    std_intrinsics [B,9], iterations [B], and per view homography [V,3,3], view_void [V]."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    obj, img = _board_and_corners(obj_points, img_points, dev)
+    nv, n = img.shape[0], img.shape[1]
+    if nv > L.CALIB_MAX_VIEWS or n > L.CHESS_MAX_PATTERN:
+        raise L.VbsError(f"vbs_calibrate_camera: {nv} views of {n} points exceed VBS_CALIB_MAX_VIEWS = {L.CALIB_MAX_VIEWS} or "
+                         f"VBS_CHESS_MAX_PATTERN = {L.CHESS_MAX_PATTERN}")
+    m = None
+    if view_mask is not None:
+        m = torch.as_tensor(view_mask, device=dev).reshape(-1, nv).ne(0).to(torch.uint8).contiguous()
+    b = 1 if m is None else m.shape[0]
+    f64, i32 = torch.float64, torch.int32
+    out = {"status": torch.empty((b,), dtype=i32, device=dev), "K4": torch.empty((b, 4), dtype=f64, device=dev),
+           "dist": torch.empty((b, 5), dtype=f64, device=dev), "R": torch.empty((b, nv, 3, 3), dtype=f64, device=dev),
+           "T": torch.empty((b, nv, 3), dtype=f64, device=dev), "rms": torch.empty((b,), dtype=f64, device=dev),
+           "view_rms": torch.empty((b, nv), dtype=f64, device=dev), "std_intrinsics": torch.empty((b, 9), dtype=f64, device=dev),
+           "iterations": torch.empty((b,), dtype=i32, device=dev), "homography": torch.empty((nv, 3, 3), dtype=f64, device=dev),
+           "view_void": torch.empty((nv,), dtype=i32, device=dev)}
+    rc = L.lib().vbs_calibrate_camera(dev.index, _ptr(obj), n, _ptr(img), nv, _ptr(m), b, int(img_size[0]), int(img_size[1]),
+                                      int(max_iter), _ptr(out["homography"]), _ptr(out["view_void"]), _ptr(out["status"]),
+                                      _ptr(out["K4"]), _ptr(out["dist"]), _ptr(out["R"]), _ptr(out["T"]), _ptr(out["rms"]),
+                                      _ptr(out["view_rms"]), _ptr(out["std_intrinsics"]), _ptr(out["iterations"]),
+                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_calibrate_camera: bad argument (at least 4 points, 1 view and 1 problem, positive image size and max_iter)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_calibrate_camera failed ({rc})")
+    return out
+
+
 def normxcorr2_general(template, image, mode="same", device=None):
     """`_normxcorr2` for arbitrary operands: float64 map of the mode's size on the GPU (`vbs_normxcorr2_general`)."""
     if not torch.cuda.is_available():
