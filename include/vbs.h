@@ -563,6 +563,41 @@ int vbs_window_means(vbs_handle* h, const float* table, int n, int m_ref, const 
  * flag = 1 where both rows carry VBS_FLAG_XYZ, else (0, 0).  ref_frame outside [0, n): VBS_EINVAL. */
 int vbs_displacement_from_frame(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, double* out, void* stream);
 
+/* ---- The dynamic polishing process (the reference's Figure 11; it ships no code for it): totals, FIR trend, residual --------
+ * vbs_axis_displacement - the signed analogue of vbs_displacement_from_frame.  For every frame of [frame_begin, frame_end) of a
+ * table holding frames [0, n) (the _range form of the other entries: what a rank calls on the gathered table for its shard) and
+ * every slot: axis [dev] float64 [fe-fb, m_ref, VBS_AXIS_COLS] = (1, dX, dY, dZ) with d = (double)X - (double)X_ref (cols 6-8)
+ * where this row and the slot's row in ref_frame both carry VBS_FLAG_XYZ, else (0, 0, 0, 0).  slot_mask [dev] uint8 [m_ref]
+ * (may be NULL = all): a slot with mask 0 is treated as a slot whose flags are clear.  total [dev] float64 [fe-fb,
+ * VBS_TOTAL_COLS] = complete, sum dX, sum dY, sum dZ, count over the slots with flag 1; complete = 1 when count equals the number
+ * of selected slots valid in ref_frame and that number is >= 1 (a frame where a marker dropped out is not silently a smaller
+ * sum).  THE ORDER OF SUMMATION IS PART OF THE INTERFACE: lane l of 64 adds slots l, l + 64, l + 128, ... in ascending order
+ * (other slots add nothing), the 64 lane sums are folded a[i] + a[i + 32], then + 16, + 8, + 4, + 2, + 1.  No atomics.  axis or
+ * total may be NULL (not both).  ref_frame outside [0, n), a range outside 0 <= fb <= fe <= n: VBS_EINVAL; fb == fe emits nothing.
+ *
+ * vbs_fir_series_f64 - a normalised zero-phase FIR along time with gaps, no handle.  rec [dev] float64 [n, s, cols], time-major:
+ * col 0 the flag (nonzero = valid), cols 1 .. n_values the values, 1 <= n_values < cols <= 8 (axis and total above are valid
+ * inputs as they are: cols 4 resp. 5, n_values 3).  half HOST [n_half] = the centre tap, then the taps at distance 1 .. n_half-1:
+ * the filter is w[k] = half[|k|], k = -h .. h, h = n_half - 1, SYMMETRIC BY CONSTRUCTION, which is what makes it zero-phase.
+ * THE TAPS TRAVEL AS KERNEL ARGUMENTS (1 KB): the call allocates nothing and reads `half` before it returns.  For every frame
+ * f of [frame_begin, frame_end) and every series, in ascending k and skipping (never multiplying by zero) the entries that are
+ * invalid or outside [0, n) - they may hold NaN or anything else:
+ *     num = sum w[k] x[f+k],   den = sum w[k],   sw = the same ascending sum of ALL w[k] (on the host)
+ *     ok = valid[f] && den >= min_coverage * sw
+ * out [dev] float64 [fe-fb, s, 1 + 2 n_values] = flag, filtered[n_values], residual[n_values]: flag = valid[f] + 2 ok (0, 1 or
+ * 3); where ok, filtered = num / den and residual = x[f] - filtered, otherwise both are 0.  Float64 without contraction; an
+ * output depends on its 2h + 1 inputs only - not on the tile (VBS_FIR_TILE frames x 64 series a workgroup, stated for tests of
+ * its edges), on the range or on s.  n_half < 1, 2 n_half - 1 > VBS_FIR_MAX_TAPS, min_coverage outside (0, 1], sw <= 0, a bad
+ * range, bad cols / n_values: VBS_EINVAL. */
+#define VBS_FIR_MAX_TAPS 255   /* full length K = 2*n_half - 1, odd */
+#define VBS_FIR_TILE     64    /* frames a workgroup emits (no result depends on it) */
+#define VBS_AXIS_COLS    4     /* flag, dX, dY, dZ                                   */
+#define VBS_TOTAL_COLS   5     /* complete, sum dX, sum dY, sum dZ, count            */
+int vbs_axis_displacement(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, const uint8_t* slot_mask,
+                          int frame_begin, int frame_end, double* axis, double* total, void* stream);
+int vbs_fir_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half,
+                       double min_coverage, int frame_begin, int frame_end, double* out, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

@@ -991,6 +991,37 @@ extern "C" int vbs_displacement_from_frame(vbs_handle* h, const float* table, in
     return check_launch(h);
 }
 
+// ---- the dynamic polishing process (k_filter.hip) --------------------------------------------------------------------------
+extern "C" int vbs_axis_displacement(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, const uint8_t* slot_mask,
+                                     int frame_begin, int frame_end, double* axis, double* total, void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!table || (!axis && !total) || !series_shape_ok(n, m_ref, 0) || ref_frame < 0 || ref_frame >= n || frame_begin < 0 ||
+        frame_end > n || frame_begin > frame_end) {
+        h->err = "vbs_axis_displacement: bad argument (ref_frame inside [0, n), 0 <= frame_begin <= frame_end <= n)";
+        return VBS_EINVAL;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (frame_end > frame_begin)
+        launch_axis_displacement(h, table, m_ref, ref_frame, slot_mask, frame_begin, frame_end, axis, total, (hipStream_t)stream);
+    return check_launch(h);
+}
+
+extern "C" int vbs_fir_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half,
+                                  int n_half, double min_coverage, int frame_begin, int frame_end, double* out, void* stream) {
+    if (!rec || !half || !out || !series_shape_ok(n, s, 0) || cols < 2 || cols > 8 || n_values < 1 || n_values >= cols ||
+        n_half < 1 || 2 * (int64_t)n_half - 1 > VBS_FIR_MAX_TAPS || !(min_coverage > 0.0 && min_coverage <= 1.0) ||
+        frame_begin < 0 || frame_end > n || frame_begin > frame_end)
+        return VBS_EINVAL;
+    double sw = 0.0;                                     // ascending over k = -h .. h, as the kernel adds den
+    for (int k = -(n_half - 1); k <= n_half - 1; ++k) sw = sw + half[k < 0 ? -k : k];
+    if (!(sw > 0.0)) return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_fir_series(rec, n, s, cols, n_values, half, n_half, min_coverage * sw, frame_begin, frame_end, out,
+                          (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 extern "C" int vbs_assign_ids(vbs_handle* h, const double* det, const int32_t* count, int num_layers, int id_mode,
                               int32_t* ids, double* ref_xy, int cap, int32_t* m_out, void* stream) {
     if (!h) return VBS_EINVAL;

@@ -233,6 +233,11 @@ void launch_series_cumsum64(const double* disp, int n, int m_ref, int frame_begi
 void launch_window_means(vbs_handle* h, const float* table, int m_ref, const int32_t* windows, int nw, int pieces, double* part,
                          double* means, hipStream_t s);
 void launch_disp_from_frame(vbs_handle* h, const float* table, int n, int m_ref, int ref_frame, double* out, hipStream_t s);
+// k_filter.hip (f10): signed displacement from a reference frame with its sum over the slots; gap-aware zero-phase FIR along time
+void launch_axis_displacement(vbs_handle* h, const float* table, int m_ref, int ref_frame, const u8* slot_mask, int frame_begin,
+                              int frame_end, double* axis, double* total, hipStream_t s);
+void launch_fir_series(const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half, double need,
+                       int frame_begin, int frame_end, double* out, hipStream_t st);
 // k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,

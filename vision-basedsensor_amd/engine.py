@@ -499,6 +499,34 @@ class Engine:
                                                              self._stream()), "vbs_displacement_from_frame")
         return out
 
+    def axis_displacement(self, table, ref_frame=0, slots=None, frame_range=None):
+        """The signed displacement of every slot from its position in frame `ref_frame` and its sum over the slots
+        (`vbs_axis_displacement`): `(axis, total)` = float64 [b-a, m, 4] (flag, dX, dY, dZ) and [b-a, 5] (complete, sum dX, sum dY,
+        sum dZ, count).  `slots` (indices) selects markers as `window_displacement` does: the others count as not seen.
+        `frame_range=(a, b)` emits only frames [a, b) of the table."""
+        table = self._table32(table)
+        n, m = table.shape[0], table.shape[1]
+        a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+        if not (0 <= a <= b <= n):
+            raise ValueError(f"frame_range {frame_range} outside the table's {n} frames")
+        if not (0 <= int(ref_frame) < n):
+            raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+        mask = None
+        if slots is not None:
+            idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= m):
+                raise ValueError(f"slots outside the table's {m} slots")
+            mask = torch.zeros((m,), dtype=torch.uint8, device=self.device)
+            mask[torch.as_tensor(idx, device=self.device)] = 1
+        axis = torch.empty((b - a, m, L.AXIS_COLS), dtype=torch.float64, device=self.device)
+        total = torch.empty((b - a, L.TOTAL_COLS), dtype=torch.float64, device=self.device)
+        if a == b:
+            return axis, total
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_axis_displacement(self._h, _ptr(table), n, m, int(ref_frame), _ptr(mask), a, b, _ptr(axis),
+                                                       _ptr(total), self._stream()), "vbs_axis_displacement")
+        return axis, total
+
     # ---- a14 / f4 ------------------------------------------------------------------------------
     def assign_ids(self, det, counts, num_layers=5, id_mode="as_written"):
         """Frame-0 identities on the device: (ids int32 [M,2], ref_xy float64 [M,2]) as device tensors, in the
@@ -762,3 +790,39 @@ def series_stats_f64(disp64, frame_begin=0, cumulative=False, device=None):
     if rc != L.VBS_OK:
         raise L.VbsError(f"vbs_series_stats_f64 failed ({rc})")
     return (stats, cum) if cumulative else stats
+
+
+def fir_series_f64(rec, taps, n_values=None, min_coverage=0.5, frame_range=None, device=None):
+    """A normalised zero-phase FIR along time with gaps (`vbs_fir_series_f64`).  rec float64 [n, s, cols] (host or device): col 0
+    the flag (nonzero = valid), cols 1 .. n_values the values (default cols - 1).  `taps`: the FULL odd-length array, refused
+    unless |w[k] - w[K-1-k]| <= 1e-12 max|w|; the means of its pairs are what is used (`filters.half_taps`), so the filter is
+    exactly symmetric.  Returns float64 [b-a, s, 1 + 2 n_values] = flag (0, 1 = valid, 3 = valid and filtered), filtered,
+    residual for the frames [a, b) of `frame_range` (default all); an output does not depend on the range it was asked in."""
+    from .filters import half_taps
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    half = np.ascontiguousarray(half_taps(taps), dtype=np.float64)
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    nv = cols - 1 if n_values is None else int(n_values)
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    if nv < 1:
+        raise ValueError("n_values must be >= 1")
+    out = torch.empty((b - a, s, 1 + 2 * nv), dtype=torch.float64, device=dev)
+    if a == b:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_fir_series_f64(dev.index, _ptr(r), n, s, cols, nv, half.ctypes.data_as(C.c_void_p), half.size,
+                                        float(min_coverage), a, b, _ptr(out),
+                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError(f"vbs_fir_series_f64: bad argument (at most {L.FIR_MAX_TAPS} taps with a positive sum, min_coverage in "
+                         f"(0, 1], 1 <= n_values < cols <= 8)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_fir_series_f64 failed ({rc})")
+    return out

@@ -185,6 +185,53 @@ def window_displacement(eng: Engine, table: torch.Tensor, start=(1, 30), end=(12
     return {"slots": idx, "start_xyz": s_xyz, "end_xyz": e_xyz, "d": torch.cat([d, mag[:, None]], dim=1), "mean": mag.mean()}
 
 
+# ---- the dynamic polishing process (k_filter.hip): the reference's Figure 11 from a tracked table ------------------------------
+def polishing_analysis(eng: Engine, table: torch.Tensor, taps, ref_frame=0, slots=None, min_coverage=0.5):
+    """Figure 11 of the reference (it ships no code for it) from a table [N, M, 10]: (a) the total marker
+    displacement per frame and its trend, (b) per marker the amplitude left when the marker's own trend is removed.  `taps`: a
+    full odd-length symmetric FIR (`filters.lowpass_taps`).  Returns a dict of device tensors (float64):
+      `axis` [N, M, 4] flag, dX, dY, dZ against frame `ref_frame`;  `total` [N, 5] complete, sum dX, dY, dZ, count;
+      `total_filtered` [N, 7] flag, trend, residual: the FIR of the TOTAL series over its complete frames (not the sum of the
+      per-marker trends: a frame with a dropout is a gap of the total, whichever marker it was);
+      `marker_filtered` [N, M, 7] the same per marker over the frames it was seen in;
+      `amplitude` [M, 3, 3]: per marker and axis the count, std (ddof = 1) and max |.| of its residual (NaN as `series_stats`)."""
+    from .engine import fir_series_f64, series_stats_f64
+    axis, total = eng.axis_displacement(table, ref_frame, slots)
+    dev = eng.device.index
+    total_f = fir_series_f64(total[:, None, :], taps, 3, min_coverage, device=dev)[:, 0]
+    marker_f = fir_series_f64(axis, taps, 3, min_coverage, device=dev)
+    n, m = marker_f.shape[0], marker_f.shape[1]
+    amplitude = torch.empty((m, 3, 3), dtype=torch.float64, device=eng.device)
+    packed = torch.zeros((n, m, L.DISP_COLS), dtype=torch.float64, device=eng.device)     # the layout series_stats_f64 reads
+    packed[..., 0] = (marker_f[..., 0] == 3.0).to(torch.float64)
+    for a in range(3):
+        packed[..., 4] = marker_f[..., 4 + a]
+        st = series_stats_f64(packed, device=dev)
+        packed[..., 4] = marker_f[..., 4 + a].abs()
+        amplitude[:, a, 0], amplitude[:, a, 1] = st[:, 0], st[:, 2]
+        amplitude[:, a, 2] = series_stats_f64(packed, device=dev)[:, 3]
+    return {"axis": axis, "total": total, "total_filtered": total_f, "marker_filtered": marker_f, "amplitude": amplitude}
+
+
+def to_total_frame(total, total_filtered, frame_offset=0, path=None):
+    """The sheet behind Figure 11 (a): one row `frameno, count, complete, dX, dY, dZ, dX_f, dY_f, dZ_f` per frame from
+    `polishing_analysis`'s `total` [N, 5] and `total_filtered` [N, 7]; the filtered columns are NaN (empty cells) where the
+    frame has no trend (flag != 3).  `path`: also written as .xlsx (`xlsx_io.dataframe_to_xlsx`)."""
+    import pandas as pd
+    t = total.detach().cpu().numpy() if isinstance(total, torch.Tensor) else np.asarray(total)
+    f = total_filtered.detach().cpu().numpy() if isinstance(total_filtered, torch.Tensor) else np.asarray(total_filtered)
+    if t.ndim != 2 or t.shape[1] != L.TOTAL_COLS or f.shape != (t.shape[0], 7):
+        raise ValueError(f"total must be [N, {L.TOTAL_COLS}] and total_filtered [N, 7]")
+    trend = np.where((f[:, 0] == 3.0)[:, None], f[:, 1:4], np.nan)
+    df = pd.DataFrame({"frameno": np.arange(t.shape[0], dtype=np.int64) + int(frame_offset), "count": t[:, 4].astype(np.int64),
+                       "complete": t[:, 0].astype(np.int64), "dX": t[:, 1].astype(np.float64), "dY": t[:, 2].astype(np.float64),
+                       "dZ": t[:, 3].astype(np.float64), "dX_f": trend[:, 0], "dY_f": trend[:, 1], "dZ_f": trend[:, 2]})
+    if path is not None:
+        from .xlsx_io import dataframe_to_xlsx
+        dataframe_to_xlsx(df, path)
+    return df
+
+
 def to_marker_frame(table, ids, frame_offset=0, path=None):
     """The sheet the reference's L4 scripts read (`LocalAnalysis.py:47,58`, `MarkerDisplacement.py:72,80`): one row
     `frameno, marker_id, Xw, Yw, Zw` per table entry with a 3-D point, frame-major; `marker_id` = `ids.marker_ids`.
