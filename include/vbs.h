@@ -472,7 +472,9 @@ int vbs_solve3d(vbs_handle* h, float* table, int n, int m_ref, const vbs_camera*
                 double min_marker_size_px, void* stream);
 
 /* Fused frames -> table: everything above in one call, intermediates kept on the device in
- * float64 / bit-packed form (no uint8 masks are written).  counts may be NULL. */
+ * float64 / bit-packed form (no uint8 masks are written).  counts may be NULL.  The 3-D solve reads
+ * Cx, Cy, major_axis as the float32 values of the row it writes: the table equals vbs_track followed
+ * by vbs_solve3d bit for bit. */
 int vbs_track_to_3d(vbs_handle* h, const uint8_t* frames, int n, int channels, int64_t stride_n,
                     int64_t stride_row, const double* ref_xy, int m_ref, double min_dist,
                     const vbs_camera* cam, double min_marker_size_px, float* table,

@@ -29,6 +29,7 @@ from oracle import stages as O                                # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "helpers"))
 from markers import TOL_AX, angle_close, compare_markers      # noqa: E402,F401
+import backend_oracle as BO                                   # noqa: E402
 
 TOL_XY, TOL_XYZ = 2.5e-4, 2e-5
 
@@ -928,22 +929,7 @@ def test_displacement_range_and_gaps():
     xyz[200, 7] += 80.0                            # > 50 mm jump
     tab[..., 6:9] = xyz
     warm, minsz, lim = 10, 5.0, 50.0
-    want = np.zeros((n, m, 5), dtype=np.float64)
-    seen = (tab[..., 0].astype(int) & 1 > 0) & (tab[..., 3] >= minsz)
-    fmin = int(np.nonzero(seen.any(1))[0][0])
-    for r in range(m):
-        last = None
-        for f in range(fmin + warm, n):
-            if not seen[f, r]:
-                continue
-            good = int(tab[f, r, 0]) & 2
-            cur = tab[f, r, 6:9].astype(np.float64)
-            if last is not None and last[0] and good:
-                d = cur - last[1]
-                mm = np.sqrt((d * d).sum())
-                if not mm > lim:
-                    want[f, r] = [1, d[0], d[1], d[2], mm]
-            last = (good, cur)
+    want = BO.displacement(tab, warm, minsz, lim)           # the sequential loop (tests/helpers/backend_oracle.py)
     eng = engine(480, 640)
     tt = torch.from_numpy(tab).cuda()
     full = eng.displacement(tt, warm, minsz, lim).cpu().numpy()

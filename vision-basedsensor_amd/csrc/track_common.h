@@ -150,10 +150,12 @@ __device__ __forceinline__ void track_frame(int n, const double* __restrict__ de
             int flags = VBS_FLAG_TRACKED;
             o[1] = (float)mx[bi]; o[2] = (float)my[bi]; o[3] = (float)major; o[4] = (float)minor;
             o[5] = (float)ang; o[9] = (float)bi;
-            if (do3d && major >= min_size) {
+            // the solve reads the float32 values the row holds, not the float64 detection: X, Y, Z are then a function of the
+            // table's own columns 1-3, and vbs_track + vbs_solve3d (k_solve3d has nothing but the row) give the same bits
+            if (do3d && (double)o[3] >= min_size) {
                 double u, v, X[3];
-                undistort_point(cam, mx[bi], my[bi], &u, &v);
-                if (solve_marker(cam, u, v, major, X)) {
+                undistort_point(cam, (double)o[1], (double)o[2], &u, &v);
+                if (solve_marker(cam, u, v, (double)o[3], X)) {
                     flags |= VBS_FLAG_XYZ;
                     o[6] = (float)X[0]; o[7] = (float)X[1]; o[8] = (float)X[2];
                 }
