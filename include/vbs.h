@@ -600,6 +600,48 @@ int vbs_axis_displacement(vbs_handle* h, const float* table, int n, int m_ref, i
 int vbs_fir_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half,
                        double min_coverage, int frame_begin, int frame_end, double* out, void* stream);
 
+/* ---- The probe-indentation validation (the reference's Figure 6(b); it ships no code for it): steps, dwells, step error ---------
+ * Three entries without a handle on the record layout vbs_fir_series_f64 takes: rec [dev] float64 [n, s, cols], time-major, col 0
+ * the flag (nonzero = valid), cols 1 .. n_values the values, 1 <= n_values < cols <= 8.  Float64 without contraction, no atomics;
+ * invalid entries are selected out and never multiplied (they may hold NaN).  No result depends on the launch shape, on a tile
+ * boundary or on s.  THE DEFINITIONS AND THE ORDER OF EVERY SUM ARE PART OF THE INTERFACE.
+ *
+ * vbs_step_response_f64 - a step detector: the difference of two one-sided means.  1 <= min_count <= w <= VBS_STEP_MAX_WINDOW.
+ * For frame f the left window is the valid frames g of [f-w, f) within [0, n), the right window the valid frames g of [f, f+w)
+ * within [0, n); their populations are cl and cr, and ok = cl >= min_count && cr >= min_count.  Per value v each sum starts at
+ * 0.0 and adds in ascending g, one add per valid frame: EVERY OUTPUT ADDS ITS OWN WINDOWS (no running sum: it would change the
+ * bits and drift).  r_v = SR_v / cr - SL_v / cl;  score = sum of r_v * r_v in ascending v from 0.0.  The score stays squared: no
+ * square root enters a decision.  out [dev] float64 [n, s, 2 + n_values] = (ok, score, r_1 .. r_nv), all zero where !ok.
+ *
+ * vbs_find_steps_f64 - the peaks of that response.  Only columns 0 (ok) and 1 (score) of resp [dev] float64 [n, s, resp_cols]
+ * are read, 2 <= resp_cols <= 9; thr2 is the SQUARED threshold, a double computed by the caller (NaN or negative: VBS_EINVAL).
+ * Frame f is a step of series i when ok[f], score[f] >= thr2, and for every g of [f-w, f+w] within [0, n), g != f, with ok[g]:
+ * score[g] < score[f] when g < f and score[g] <= score[f] when g > f - so the earliest of equal maxima wins.  A NaN score is
+ * never a step and never suppresses one.  steps [dev] int32 [s, 1 + max_steps], 1 <= max_steps <= VBS_STEP_MAX_STEPS: column 0
+ * the number of steps found - it MAY EXCEED max_steps, which is how the caller sees an overflow: a per-series result, not an
+ * error of the call - then the first min(count, max_steps) frames in ascending order, then -1.  The order is ascending by
+ * construction (a workgroup walks the frames of its 64 series in order); no atomics decide it.
+ *
+ * vbs_dwell_stats_f64 - the statistics between the steps.  steps [dev] int32 [steps_rows, 1 + max_steps] as above; steps_rows
+ * is s (each series has its own steps) or 1 (one list shared by all series); guard >= 0.  With k = min(count, max_steps)
+ * (a negative count reads as 0) and the change frames c_0 < .. < c_{k-1}, dwell j of [0, k] covers [begin, end):
+ * begin = j == 0 ? 0 : c_{j-1} + guard, end = j == k ? n : c_j - guard, both clipped to [0, n], then end = max(end, begin).
+ * out [dev] float64 [s, max_steps + 1, 3 + 2 n_values] = (begin, end, count, mean_v .., M2_v ..).  One wave per (series, dwell):
+ * lane l of 64 adds the valid frames begin + l, begin + l + 64, .. in ascending order from 0.0, the 64 lane sums are folded
+ * a[i] + a[i + 32], then + 16, + 8, + 4, + 2, + 1 (the rule of vbs_axis_displacement's totals); mean = S / count; a second pass
+ * in the same order gives M2 = sum of (x - mean)^2.  count == 0: mean is NaN and M2 is 0.  Rows j > k are (-1, -1, 0, NaN ..).
+ * std = sqrt(M2 / (count - 1)) is the caller's (NaN below two frames).
+ * All three: a null pointer, n < 1, s < 1, bad cols / n_values or a limit above broken: VBS_EINVAL, decided before the device
+ * is touched. */
+#define VBS_STEP_MAX_WINDOW 64
+#define VBS_STEP_MAX_STEPS  64
+int vbs_step_response_f64(int device, const double* rec, int n, int s, int cols, int n_values, int window, int min_count,
+                          double* out, void* stream);
+int vbs_find_steps_f64(int device, const double* resp, int n, int s, int resp_cols, int window, double thr2, int max_steps,
+                       int32_t* steps, void* stream);
+int vbs_dwell_stats_f64(int device, const double* rec, int n, int s, int cols, int n_values, const int32_t* steps, int steps_rows,
+                        int max_steps, int guard, double* out, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

@@ -1022,6 +1022,41 @@ extern "C" int vbs_fir_series_f64(int device, const double* rec, int n, int s, i
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- the probe-indentation validation (k_steps.hip) ---------------------------------------------------------------------------
+static bool record_shape_ok(int n, int s, int cols, int n_values) {
+    return series_shape_ok(n, s, 0) && cols >= 2 && cols <= 8 && n_values >= 1 && n_values < cols;
+}
+
+extern "C" int vbs_step_response_f64(int device, const double* rec, int n, int s, int cols, int n_values, int window,
+                                     int min_count, double* out, void* stream) {
+    if (!rec || !out || !record_shape_ok(n, s, cols, n_values) || window > VBS_STEP_MAX_WINDOW || min_count < 1 ||
+        min_count > window)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_step_response(rec, n, s, cols, n_values, window, min_count, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_find_steps_f64(int device, const double* resp, int n, int s, int resp_cols, int window, double thr2,
+                                  int max_steps, int32_t* steps, void* stream) {
+    if (!resp || !steps || !series_shape_ok(n, s, 0) || resp_cols < 2 || resp_cols > 9 || window < 1 ||
+        window > VBS_STEP_MAX_WINDOW || !(thr2 >= 0.0) || max_steps < 1 || max_steps > VBS_STEP_MAX_STEPS)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_find_steps(resp, n, s, resp_cols, window, thr2, max_steps, steps, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_dwell_stats_f64(int device, const double* rec, int n, int s, int cols, int n_values, const int32_t* steps,
+                                   int steps_rows, int max_steps, int guard, double* out, void* stream) {
+    if (!rec || !steps || !out || !record_shape_ok(n, s, cols, n_values) || (steps_rows != s && steps_rows != 1) ||
+        max_steps < 1 || max_steps > VBS_STEP_MAX_STEPS || guard < 0)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_dwell_stats(rec, n, s, cols, n_values, steps, steps_rows, max_steps, guard, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 extern "C" int vbs_assign_ids(vbs_handle* h, const double* det, const int32_t* count, int num_layers, int id_mode,
                               int32_t* ids, double* ref_xy, int cap, int32_t* m_out, void* stream) {
     if (!h) return VBS_EINVAL;

@@ -238,6 +238,13 @@ void launch_axis_displacement(vbs_handle* h, const float* table, int m_ref, int 
                               int frame_end, double* axis, double* total, hipStream_t s);
 void launch_fir_series(const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half, double need,
                        int frame_begin, int frame_end, double* out, hipStream_t st);
+// k_steps.hip (f11): step response, peak search, dwell statistics
+void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
+                          hipStream_t st);
+void launch_find_steps(const double* resp, int n, int s, int resp_cols, int w, double thr2, int max_steps, int32_t* steps,
+                       hipStream_t st);
+void launch_dwell_stats(const double* rec, int n, int s, int cols, int n_values, const int32_t* steps, int steps_rows,
+                        int max_steps, int guard, double* out, hipStream_t st);
 // k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,

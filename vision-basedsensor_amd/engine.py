@@ -826,3 +826,86 @@ def fir_series_f64(rec, taps, n_values=None, min_coverage=0.5, frame_range=None,
     if rc != L.VBS_OK:
         raise L.VbsError(f"vbs_fir_series_f64 failed ({rc})")
     return out
+
+
+# ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
+def _steps_call(name, what, fn):
+    rc = fn()
+    if rc == L.VBS_EINVAL:
+        raise ValueError(f"{name}: bad argument ({what})")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"{name} failed ({rc})")
+
+
+def _record(rec, n_values, device):
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    nv = r.shape[2] - 1 if n_values is None else int(n_values)
+    if nv < 1:
+        raise ValueError("n_values must be >= 1")
+    return dev, r, nv
+
+
+def step_response_f64(rec, window, n_values=None, min_count=None, device=None):
+    """A step detector along time with gaps (`vbs_step_response_f64`): per frame the mean of the valid frames of [f, f+window)
+    minus that of [f-window, f).  rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values
+    the values (default cols - 1).  `min_count` (default (window + 1) // 2): the valid frames each side needs.  Returns float64
+    [n, s, 2 + n_values] = ok, score (the SQUARED norm of the difference), the difference per value; zero where not ok."""
+    dev, r, nv = _record(rec, n_values, device)
+    n, s, cols = r.shape
+    w = int(window)
+    mc = (w + 1) // 2 if min_count is None else int(min_count)
+    out = torch.empty((n, s, 2 + nv), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _steps_call("vbs_step_response_f64", f"1 <= min_count <= window <= {L.STEP_MAX_WINDOW}, 1 <= n_values < cols <= 8",
+                    lambda: L.lib().vbs_step_response_f64(dev.index, _ptr(r), n, s, cols, nv, w, mc, _ptr(out),
+                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
+
+
+def find_steps_f64(resp, window, threshold, max_steps=L.STEP_MAX_STEPS, device=None):
+    """The peaks of a step response (`vbs_find_steps_f64`): frame f is a step where it is ok, its score reaches `threshold`
+    squared and no ok frame within `window` on either side has a larger score (of equal ones the earliest wins).  resp float64
+    [n, s, >= 2] as `step_response_f64` returns it.  Returns int32 [s, 1 + max_steps]: the number of steps found (more than
+    `max_steps` = an overflow of that series), the first `max_steps` of them in ascending order, then -1."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(resp, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1:
+        raise ValueError("resp must be [n >= 1, s >= 1, cols >= 2]")
+    n, s, cols = r.shape
+    ms = int(max_steps)
+    steps = torch.empty((s, 1 + max(ms, 0)), dtype=torch.int32, device=dev)
+    thr = float(threshold)
+    with torch.cuda.device(dev):
+        _steps_call("vbs_find_steps_f64", f"1 <= window <= {L.STEP_MAX_WINDOW}, threshold >= 0, 1 <= max_steps <= "
+                    f"{L.STEP_MAX_STEPS}, 2 <= cols <= 9",
+                    lambda: L.lib().vbs_find_steps_f64(dev.index, _ptr(r), n, s, cols, int(window), thr * thr, ms, _ptr(steps),
+                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return steps
+
+
+def dwell_stats_f64(rec, steps, guard, n_values=None, device=None):
+    """The statistics of the dwells between steps (`vbs_dwell_stats_f64`).  rec float64 [n, s, cols] as `step_response_f64`
+    takes it; steps int32 [s or 1, 1 + max_steps] as `find_steps_f64` returns it (one row: the list is shared by all series);
+    `guard`: frames left out on either side of a step.  Returns float64 [s, max_steps + 1, 3 + 2 n_values] = begin, end, count,
+    mean per value, M2 per value (sum of squared deviations; std = sqrt(M2 / (count - 1))); rows past the last dwell are
+    (-1, -1, 0, NaN ...)."""
+    dev, r, nv = _record(rec, n_values, device)
+    n, s, cols = r.shape
+    st = torch.as_tensor(steps, dtype=torch.int32, device=dev).contiguous()
+    if st.dim() != 2 or st.shape[1] < 2:
+        raise ValueError("steps must be [s or 1, 1 + max_steps]")
+    ms = st.shape[1] - 1
+    out = torch.empty((s, ms + 1, 3 + 2 * nv), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _steps_call("vbs_dwell_stats_f64", f"steps rows = s or 1, 1 <= max_steps <= {L.STEP_MAX_STEPS}, guard >= 0, "
+                    "1 <= n_values < cols <= 8",
+                    lambda: L.lib().vbs_dwell_stats_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(st), st.shape[0], ms, int(guard),
+                                                        _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out

@@ -232,6 +232,83 @@ def to_total_frame(total, total_filtered, frame_offset=0, path=None):
     return df
 
 
+# ---- the probe-indentation validation (k_steps.hip): the reference's Figure 6(b) from a tracked table -------------------------
+@dataclass
+class IndentationResult:
+    """What `indentation_analysis` returns (host arrays; k = the number of steps kept, so k + 1 dwells)."""
+    step_mm: float
+    component: str
+    step_frames: np.ndarray         # int64 [k]
+    begin: np.ndarray               # int64 [k + 1]: dwell j is the frames [begin, end) ...
+    end: np.ndarray                 # int64 [k + 1]
+    count: np.ndarray               # int64 [k + 1]: ... of which this many are complete
+    cumulative: np.ndarray          # float64 [k + 1]: the dwell mean (for "xyz" the norm of the dwell-mean vector)
+    std: np.ndarray                 # float64 [k + 1], ddof = 1; NaN below two frames
+    delta: np.ndarray               # float64 [k]: cumulative[j + 1] - cumulative[j]
+    abs_error: np.ndarray           # float64 [k]: |delta - step_mm|
+    marker_means: np.ndarray        # float64 [m, k + 1, 3]: per marker the dwell means of dX, dY, dZ (NaN where never seen)
+    overflow: bool                  # more steps were found than `VBS_STEP_MAX_STEPS`: the last dwell runs over the rest
+
+
+_COMPONENT_COLS = {"x": (1,), "y": (2,), "z": (3,), "xyz": (1, 2, 3)}
+
+
+def indentation_analysis(eng: Engine, table: torch.Tensor, step_mm=0.7, window=8, threshold=None, guard=None, ref_frame=0,
+                         slots=None, component="z"):
+    """Figure 6(b) of the reference (it ships no code for it) from a table [N, M, 10] of a tool pressed in steps
+    of `step_mm`: the displacement of the selected slots against `ref_frame`, averaged over the slots in every COMPLETE frame
+    (`Engine.axis_displacement`; a frame where a marker dropped out is a gap), the steps of that one series (`step_response_f64`,
+    `find_steps_f64` on `component`: "x", "y", "z" or "xyz"; `threshold` in mm, default step_mm / 2), the statistics of the dwells
+    between them (`dwell_stats_f64`, `guard` frames left out on either side of a step, default `window`) and, with the same step
+    list, the dwell means of every marker.  The displacement is signed: a tool that lowers the component gives negative steps,
+    which "xyz" (a norm) does not see."""
+    from .engine import dwell_stats_f64, find_steps_f64, step_response_f64
+    if component not in _COMPONENT_COLS:
+        raise ValueError(f"component must be one of {sorted(_COMPONENT_COLS)}")
+    threshold = step_mm / 2 if threshold is None else threshold
+    guard = window if guard is None else guard
+    axis, total = eng.axis_displacement(table, ref_frame, slots)
+    dev = eng.device.index
+    cols = list(_COMPONENT_COLS[component])
+    series = torch.cat([total[:, 0:1], total[:, cols] / total[:, 4:5]], dim=1)[:, None, :].contiguous()   # [N, 1, 1 + nv]
+    resp = step_response_f64(series, window, device=dev)
+    steps = find_steps_f64(resp, window, threshold, device=dev)
+    own = dwell_stats_f64(series, steps, guard, device=dev)[0].cpu().numpy()
+    per_marker = dwell_stats_f64(axis, steps, guard, 3, device=dev).cpu().numpy()
+    st = steps[0].cpu().numpy()
+    found = int(st[0])
+    k = min(found, L.STEP_MAX_STEPS)
+    nv = len(cols)
+    own = own[:k + 1]
+    count = own[:, 2]
+    with np.errstate(all="ignore"):
+        cumulative = own[:, 3] if nv == 1 else np.sqrt((own[:, 3:3 + nv] ** 2).sum(axis=1))
+        std = np.where(count >= 2, np.sqrt(own[:, 3 + nv:].sum(axis=1) / (count - 1)), np.nan)
+    delta = np.diff(cumulative)
+    return IndentationResult(step_mm=float(step_mm), component=component, step_frames=st[1:1 + k].astype(np.int64),
+                             begin=own[:, 0].astype(np.int64), end=own[:, 1].astype(np.int64), count=count.astype(np.int64),
+                             cumulative=cumulative, std=std, delta=delta, abs_error=np.abs(delta - float(step_mm)),
+                             marker_means=per_marker[:, :k + 1, 3:6], overflow=found > L.STEP_MAX_STEPS)
+
+
+def to_step_frame(result: IndentationResult, path=None):
+    """The sheet behind Figure 6(b): one row `step, frame_first, frame_last, count, cumulative_mm, std_mm, step_mm,
+    abs_error_mm` per dwell of an `IndentationResult` (frame_last inclusive; `step_mm` here is the MEASURED step from the dwell
+    before); row 0 has no step before it: NaN (empty cells) there.  `path`: also written as .xlsx."""
+    import pandas as pd
+    k1 = len(result.cumulative)
+    nan = np.full(1, np.nan)
+    df = pd.DataFrame({"step": np.arange(k1, dtype=np.int64), "frame_first": np.asarray(result.begin, dtype=np.int64),
+                       "frame_last": np.asarray(result.end, dtype=np.int64) - 1, "count": np.asarray(result.count, dtype=np.int64),
+                       "cumulative_mm": np.asarray(result.cumulative, dtype=np.float64),
+                       "std_mm": np.asarray(result.std, dtype=np.float64),
+                       "step_mm": np.concatenate([nan, result.delta]), "abs_error_mm": np.concatenate([nan, result.abs_error])})
+    if path is not None:
+        from .xlsx_io import dataframe_to_xlsx
+        dataframe_to_xlsx(df, path)
+    return df
+
+
 def to_marker_frame(table, ids, frame_offset=0, path=None):
     """The sheet the reference's L4 scripts read (`LocalAnalysis.py:47,58`, `MarkerDisplacement.py:72,80`): one row
     `frameno, marker_id, Xw, Yw, Zw` per table entry with a 3-D point, frame-major; `marker_id` = `ids.marker_ids`.
