@@ -69,7 +69,27 @@ typedef struct vbs_camera {
  * batches are looped).  height <= 480 selects the reference's small-image parameter set
  * (marker_detection.py:117-126,170).  Throughput: the labelling kernel runs three frames per compute unit at a time, so
  * passes that are a multiple of 768 frames suit an MI355X best (bench.py: 1536; 290-295 k frames/s against 280 k at 512 and
- * 292 k at 1368 or 1640); results do not depend on the pass size. */
+ * 292 k at 1368 or 1640); results do not depend on the pass size.
+ *
+ * Frame-size envelope: height >= 64 (no upper bound), 128 <= width <= 4096, 1 <= max_markers <= 1024, max_batch >= 1; anything
+ * else is VBS_EINVAL and no handle.  Inside it the frame size alone decides which kernels run; results are the same on every
+ * route (tests/test_gpu_geometry_edges.py holds each limit to the oracle).  WW = ceil(width / 64) words per row, G = 64 / WW:
+ *   branch      height <= 480: blur taps 21 / 35, NCC template 33; else 39 / 101 and 80 (api.hip).
+ *   k_blur16    from 176 (small branch) / 240 columns, width a multiple of 4, frames, rows and the base pointer 4-byte
+ *               aligned; else k_blur_mfma (k_blur16.hip: blur16_takes).  Below 128 rows its column grid has one segment.
+ *   k_gray      one flat pass when the frame is dense, 16-byte aligned, width a multiple of 64 and height * width one of 16;
+ *               else row by row with a scalar tail (k_gray.hip: launch_gray).
+ *   k_stage     height <= 2048 and tiles of R = ceil(height / ((threads / 64) * G)) <= 128 rows, for its 256- and its
+ *               768-thread instance separately; where 256 refuses, 768 is tried (k_stage.hip: stage_geom).  With
+ *               2049 <= width <= 4096 (G = 1) that is height <= 512 / <= 1536.
+ *   k_stage_lat height <= 2048 and R = ceil(height / (4 C G)) <= 128 with C = clamp(ceil(ceil(height / (6 G)) / 4), 1, 16)
+ *               workgroups (k_stage_lat.hip: lat_geom).  R reaches at most 32 below 2049 rows: only the height rule binds.
+ *   k_ccl       height <= 2048 and height * ceil(WW / min(WW, 5)) < 65535 (k_ccl.hip: ccl_layout).
+ *   These are the geometry rules only.  k_stage, k_stage_lat and k_ccl also refuse when the LDS their tables need (sized by
+ *   the frame and max_markers) exceeds what a workgroup may have: 160 KB, a third of it for k_stage's 256-thread instance;
+ *   k_ccl needs room for at least 1024 nodes.
+ *   A route whose launcher refuses falls through: few frames (k_stage_lat) -> fused (k_stage) -> round 2 (k_morph, k_ccl)
+ *   -> k_morph and k_label over every frame (labelling.hip).  Beyond 2048 rows every frame takes k_label. */
 int vbs_create(int device, int height, int width, int max_markers, int max_batch, vbs_handle** out);
 int vbs_destroy(vbs_handle* h);
 const char* vbs_last_error(const vbs_handle* h);

@@ -1697,6 +1697,14 @@ def test_engine_argument_errors():
     from vbs_amd.engine import Engine
     with pytest.raises(ValueError):
         Engine(32, 32)
+    # just outside the envelope (height >= 64, 128 <= width <= 4096).  A large-branch frame no wider than its blur radius
+    # (481 x 54) is refused by the width limit already: inside the envelope vbs_create's own blur-radius check (taps / 2 + 4
+    # <= 54) cannot be reached
+    for h, w in ((63, 128), (64, 127), (64, 4097), (481, 54)):
+        e = Engine.__new__(Engine)
+        with pytest.raises(ValueError):
+            e.__init__(h, w)
+        assert not e._h, (h, w)                         # no handle left behind
     eng = engine(480, 640)
     with pytest.raises(ValueError):
         eng.find_markers(torch.zeros((1, 100, 100), dtype=torch.uint8, device="cuda"))
