@@ -303,6 +303,13 @@ int vbs_frame_stats(vbs_handle* h, uint32_t* out, int n);
  * Entries past a frame's component counts are unspecified. */
 int vbs_stage_tables(vbs_handle* h, int n, uint32_t* ncomp, uint64_t* band_sums, uint32_t* area_first, int64_t* area_sums,
                      uint16_t* probe, uint32_t* slow);
+/* Diagnostic / parity entry: host copy of the ellipse table that the last step of _marker_center (k_finalize, or
+ * k_finalize_track) left for the first n frames of the LAST internal pass (synchronises): out [n][max_markers][8], one row per
+ * opened component in vbs_stage_tables' order = {0, 1: ellipse centre x, y; 2, 3: axes w <= h; 4: angle in degrees (all five
+ * float32 values, as cv2.fitEllipse returns them); 5: contour vertices; 6: 1 = fitted, 0 = fewer than 5 vertices or a singular
+ * system (columns 0 - 4 are then unspecified); 7: spare}.  Rows past a frame's opened-component count, and the rows of a frame
+ * whose status is not VBS_OK, are unspecified. */
+int vbs_ellipse_table(vbs_handle* h, int n, double* out);
 /* Running totals over EVERY internal pass of the detection stage since the last reset (vbs_frame_stats only sees the
  * last pass): out = {NCC pixels inside the ambiguity band of the 0.1 threshold (`:133`; 0 = every decision equals the
  * float64 one), NCC pixels re-evaluated in float64, frames}.  Synchronises. */
@@ -398,7 +405,10 @@ int vbs_calibrate_camera(int device, const double* obj, int n_points, const doub
  * det [dev] float64 [n,max_markers,VBS_DET_COLS], rows in the reference's output order (centroids are
  * integer sums / count in float64, bit-identical to ndimage.center_of_mass; axes and angle are the
  * float32 values cv2.fitEllipse would return, widened);
- * counts [dev] int32 [n] = number of rows, or a negative status for that frame. */
+ * counts [dev] int32 [n] = number of rows, or a negative status for that frame: VBS_ECAPACITY beyond the labelling's
+ * limits (30720 runs, max_markers or 512 components), and for a contour so long that its int64 vertex moments could leave
+ * 64 bits (vertex count + sum x^2 (w - 1)^2 + sum y^2 (h - 1)^2 >= 9e18 about its first pixel: only frames of several
+ * thousand rows hold one). */
 int vbs_marker_center(vbs_handle* h, const uint8_t* mask, const uint8_t* area_mask, int n,
                       double* det, int32_t* counts, void* stream);
 

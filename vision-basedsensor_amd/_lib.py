@@ -25,7 +25,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_profile", "vbs_profile_read", "vbs_frame_stats", "vbs_undistort_points", "vbs_calculate_3d", "vbs_marker_center",
            "vbs_track", "vbs_solve3d", "vbs_track_to_3d", "vbs_displacement", "vbs_displacement_range", "vbs_displacement_f64",
            "vbs_plane_fit", "vbs_assign_ids", "vbs_set_option", "vbs_bgr2gray", "vbs_ncc_counters", "vbs_normxcorr2_general",
-           "vbs_stage_tables", "vbs_deviation_plane", "vbs_format_csv", "vbs_mjpeg_probe", "vbs_mjpeg_entropy_batch",
+           "vbs_stage_tables", "vbs_ellipse_table", "vbs_deviation_plane", "vbs_format_csv", "vbs_mjpeg_probe", "vbs_mjpeg_entropy_batch",
            "vbs_mjpeg_reconstruct", "vbs_jpeg_encode_workspace", "vbs_jpeg_encode", "vbs_draw_tracking",
            "vbs_series_chunks", "vbs_series_stats", "vbs_series_stats_f64", "vbs_series_partial", "vbs_series_merge",
            "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device",
@@ -49,7 +49,8 @@ def status_text(status: int, max_markers: int = 0) -> str:
     """What a negative per-frame status in `counts[]` means (include/vbs.h)."""
     if status == VBS_ECAPACITY:
         return ("the frame exceeds the device workspace (more than 30720 runs in a mask, more than "
-                f"{max_markers or 'max_markers'} band components, or more than about 512 contours)")
+                f"{max_markers or 'max_markers'} band components, more than about 512 contours, or a contour thousands of rows "
+                "long whose vertex moments would leave 64 bits)")
     if status == VBS_EINTERNAL:
         return ("a kernel's internal hand-shake timed out: the frame's result is not to be trusted (bounded wait expired; "
                 "see VBS_EINTERNAL in include/vbs.h)")
@@ -109,6 +110,7 @@ def lib():
         "vbs_ncc_counters": (i32, [vp, vp, i32]),
         "vbs_normxcorr2_general": (i32, [i32, vp, i32, i32, vp, i32, i32, i32, vp, vp]),
         "vbs_stage_tables": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+        "vbs_ellipse_table": (i32, [vp, i32, vp]),
         "vbs_deviation_plane": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
         "vbs_format_csv": (i64, [vp, vp, vp, vp, i32, i64, vp, i64, i32]),
         "vbs_mjpeg_probe": (i32, [vp, i64, vp]),

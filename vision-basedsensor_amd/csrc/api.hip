@@ -508,6 +508,14 @@ extern "C" int vbs_stage_tables(vbs_handle* h, int n, uint32_t* ncomp, uint64_t*
     return VBS_OK;
 }
 
+extern "C" int vbs_ellipse_table(vbs_handle* h, int n, double* out) {
+    if (!h || !out || n < 0 || n > h->maxb) return VBS_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipMemcpy(out, h->last_ws->ell, (size_t)n * h->maxm * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    return VBS_OK;
+}
+
 extern "C" int vbs_ncc_counters(vbs_handle* h, uint64_t out[3], int reset) {
     if (!h || !out) return VBS_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));

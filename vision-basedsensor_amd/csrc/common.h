@@ -68,7 +68,8 @@ struct Workspace {
     u32* band_first;   // [maxb][maxm]
     u64* band_sums;    // [maxb][maxm][4]   count, sum x, sum y, spare
     u32* area_first;   // [maxb][maxm]
-    i64* area_sums;    // [maxb][maxm][VBS_AREA_SUMS]  vertex moments about the component's first pixel
+    i64* area_sums;    // [maxb][maxm][VBS_AREA_SUMS]  vertex moments about the component's first pixel.  The capacity limits alone
+                       // do not keep them below 2^63: k_finalize reports VBS_ECAPACITY where a sum could leave 64 bits
     double* ell;       // [maxb][maxm][8]   cx, cy, w, h, angle, nvert, ok, spare
     double* det64;     // [maxb][maxm][6]
     int32_t* cnt;      // [maxb]

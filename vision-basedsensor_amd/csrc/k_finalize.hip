@@ -66,6 +66,17 @@ __device__ __forceinline__ void shift_moments(const double (&in)[5][5], double s
         }
 }
 
+// Did the int64 vertex moments S of a contour stay inside 64 bits?  With x, y the integer offsets from the first pixel
+// (|x| <= W - 1, 0 <= y <= H - 1) every |x^a y^b|, a + b <= 4, is at most 1 + x^4 + y^4, so every |S[k]| is at most
+// n + sum x^4 + sum y^4 <= n + S[3] (W - 1)^2 + S[5] (H - 1)^2.  n, S[3] = sum x^2 and S[5] = sum y^2 themselves cannot
+// overflow inside the run capacity ("Range of the vertex moments": below 2^20, 2^44 and 2^50), so the test is sound; it refuses
+// from about 5/3 of the true fourth moment, i.e. a contour 10 % shorter than the first that overflows.  (The sums are
+// accumulated modulo 2^64, so only the final value has to fit.)
+__device__ __forceinline__ bool moments_in_range(const i64* S, int H, int W) {
+    const double wx = (double)(W - 1) * (double)(W - 1), wy = (double)(H - 1) * (double)(H - 1);
+    return (double)S[0] + (double)S[3] * wx + (double)S[5] * wy < 9.0e18;           // 2^63 = 9.22e18
+}
+
 // out: cx, cy, w, h, angle (float32-rounded, w <= h), nvert, ok
 __device__ void fit_ellipse_moments(const i64* S, int ax, int ay, double* out) {
     const double PI = 3.14159265358979323846;
@@ -173,7 +184,7 @@ __device__ __forceinline__ void finalize_frame(int n, const u32* __restrict__ nc
                                                const u32* __restrict__ area_first,
                                                const i64* __restrict__ area_sums,
                                                const unsigned short* __restrict__ probe_all,
-                                               const u32* __restrict__ fstat, double* __restrict__ ell_all,
+                                               u32* __restrict__ fstat, double* __restrict__ ell_all,
                                                double* __restrict__ det64, int32_t* __restrict__ cnt64,
                                                double* __restrict__ det32, int32_t* __restrict__ cnt32,
                                                int H, int W, int WW, int maxm, int stop, int force_seq) {
@@ -201,11 +212,21 @@ __device__ __forceinline__ void finalize_frame(int n, const u32* __restrict__ nc
     }
     double* ell = ell_all + (int64_t)n * maxm * 8;
     const u32* af = area_first + (int64_t)n * maxm;
+    int wide = 0;
     for (int i = tid; i < na; i += blockDim.x) {
         u32 fp = af[i];
-        fit_ellipse_moments(area_sums + ((int64_t)n * maxm + i) * VBS_AREA_SUMS, fp % W, fp / W, ell + i * 8);
+        const i64* S = area_sums + ((int64_t)n * maxm + i) * VBS_AREA_SUMS;
+        wide |= !moments_in_range(S, H, W);
+        fit_ellipse_moments(S, fp % W, fp / W, ell + i * 8);
     }
-    __syncthreads();
+    if (__syncthreads_or(wide)) {                       // a contour too long for 64-bit moments: the frame is over capacity
+        if (tid == 0) {
+            cnt64[n] = VBS_ECAPACITY;
+            if (cnt32) cnt32[n] = VBS_ECAPACITY;
+            atomicMin((int*)&fstat[n * 8 + 2], VBS_ECAPACITY);
+        }
+        return;
+    }
     if (stop == 1) return;
     const unsigned short* probe = probe_all + (int64_t)n * maxm * 4;
     double* d64 = det64 + (int64_t)n * maxm * 6;
@@ -345,7 +366,7 @@ __device__ __forceinline__ void finalize_frame(int n, const u32* __restrict__ nc
 __global__ __launch_bounds__(256) void k_finalize(const u32* __restrict__ ncomp_all, const u64* __restrict__ band_sums,
                                                   const u32* __restrict__ area_first, const i64* __restrict__ area_sums,
                                                   const unsigned short* __restrict__ probe_all,
-                                                  const u32* __restrict__ fstat, double* __restrict__ ell_all,
+                                                  u32* __restrict__ fstat, double* __restrict__ ell_all,
                                                   double* __restrict__ det64, int32_t* __restrict__ cnt64,
                                                   double* __restrict__ det32, int32_t* __restrict__ cnt32,
                                                   int H, int W, int WW, int maxm, int stop, int force_seq) {
@@ -366,7 +387,7 @@ void launch_finalize(vbs_handle* h, Workspace& w, int nb, double* det, int32_t* 
 __global__ __launch_bounds__(256) void k_finalize_track(const u32* __restrict__ ncomp_all, const u64* __restrict__ band_sums,
                                                         const u32* __restrict__ area_first, const i64* __restrict__ area_sums,
                                                         const unsigned short* __restrict__ probe_all,
-                                                        const u32* __restrict__ fstat, double* __restrict__ ell_all,
+                                                        u32* __restrict__ fstat, double* __restrict__ ell_all,
                                                         double* __restrict__ det64, int32_t* __restrict__ cnt64,
                                                         double* __restrict__ det32, int32_t* __restrict__ cnt32,
                                                         int H, int W, int WW, int maxm, int force_seq,

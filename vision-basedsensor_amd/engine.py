@@ -187,6 +187,13 @@ class Engine:
                     "vbs_stage_tables")
         return t
 
+    def ellipse_table(self, n):
+        """Host copy of the ellipse table of the first n frames of the last internal pass (`vbs_ellipse_table`, diagnostic):
+        float64 [n,M,8] = cx, cy, w, h, angle, contour vertices, fitted (0 | 1), spare; rows in `stage_tables` order."""
+        out = np.zeros((n, self.max_markers, 8), dtype=np.float64)
+        self._check(self.lib.vbs_ellipse_table(self._h, n, out.ctypes.data_as(C.c_void_p)), "vbs_ellipse_table")
+        return out
+
     def ncc_counters(self, reset=False):
         """{ambiguous, exact, frames} over every detection pass since the last reset (`vbs_ncc_counters`)."""
         out = np.zeros(3, dtype=np.uint64)
