@@ -681,7 +681,14 @@ int vbs_dwell_stats_f64(int device, const double* rec, int n, int s, int cols, i
  *   id_mode       0 = "as_written" (the published `(layer,-1)` key collision: 1 + num_layers IDs), 1 = "full"
  *   ids [dev]     int32 [cap][2] (layer, index) in the reference dict's order; ref_xy [dev] float64 [cap][2] (Ox, Oy):
  *                 the table vbs_track / vbs_track_to_3d take as `ref_xy`
- *   m_out [dev]   int32[1] number of IDs; -1 = no markers ("No markers detected in first frame!"), -2 = cap too small */
+ *   m_out [dev]   int32[1] number of IDs; -1 = no markers ("No markers detected in first frame!"), -2 = cap too small,
+ *                 -3 = *count > VBS_IDS_MAX_MARKERS (the kernel keeps every marker in LDS; nothing is truncated)
+ * Limits: 1 <= num_layers <= VBS_IDS_MAX_LAYERS, else VBS_EINVAL, decided on the host before any launch (like a null
+ * pointer, cap < 1 or another id_mode).  *count lives on the device, so its limit is the kernel's: with m_out < 0 neither
+ * `ids` nor `ref_xy` is written.  Only rows < *count and columns 0, 1 (cx, cy) of `det` are read.  With fewer than
+ * num_layers + 1 markers every marker but the centre is its own layer (k = max(1, min(num_layers, *count - 1))). */
+#define VBS_IDS_MAX_MARKERS 1024
+#define VBS_IDS_MAX_LAYERS  16
 int vbs_assign_ids(vbs_handle* h, const double* det, const int32_t* count, int num_layers, int id_mode,
                    int32_t* ids, double* ref_xy, int cap, int32_t* m_out, void* stream);
 

@@ -17,6 +17,7 @@ DIAM_COLS, DIAM_STATS_COLS, DIAM_MAX_EXTENT = 24, 5, 512
 PNP_SAMPLE, PNP_MAX_POINTS, PNP_MAX_HYPOTHESES, PNP_FEW_POINTS, PNP_NO_HYPOTHESIS = 6, 1024, 4096, 1, 2
 CHESS_MAX_CANDIDATES, CHESS_MAX_PATTERN, CHESS_MAX_WIN = 256, 256, 15
 CALIB_MAX_VIEWS, CALIB_FEW_VIEWS, CALIB_DEGENERATE = 64, 1, 2
+IDS_MAX_MARKERS, IDS_MAX_LAYERS = 1024, 16
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)

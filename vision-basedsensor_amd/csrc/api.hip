@@ -1072,6 +1072,10 @@ extern "C" int vbs_assign_ids(vbs_handle* h, const double* det, const int32_t* c
         h->err = "vbs_assign_ids: bad argument";
         return VBS_EINVAL;
     }
+    if (num_layers > VBS_IDS_MAX_LAYERS) {
+        h->err = "vbs_assign_ids: num_layers above VBS_IDS_MAX_LAYERS";
+        return VBS_EINVAL;
+    }
     HIPCHK(h, hipSetDevice(h->device));
     launch_assign_ids(h, det, count, num_layers, id_mode, ids, ref_xy, cap, m_out, (hipStream_t)stream);
     return check_launch(h);

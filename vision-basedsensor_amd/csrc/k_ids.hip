@@ -6,8 +6,8 @@
 // first minimum wins), so layers and orders are those of the host path.
 #include "common.h"
 
-#define IDS_MAXN 1024
-#define IDS_MAXK 16
+#define IDS_MAXN VBS_IDS_MAX_MARKERS
+#define IDS_MAXK VBS_IDS_MAX_LAYERS
 
 __device__ __forceinline__ double dsq(double a) { return __dmul_rn(a, a); }
 
@@ -23,7 +23,8 @@ __global__ __launch_bounds__(256) void k_assign_ids(const double* __restrict__ d
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int cnt_in = *count_p;
     if (cnt_in < 0) { if (tid == 0) *m_out = 1000 * cnt_in; return; }      // frame 0 carries a device status
-    const int n = min(cnt_in, IDS_MAXN);
+    if (cnt_in > IDS_MAXN) { if (tid == 0) *m_out = -3; return; }         // refused, never truncated
+    const int n = cnt_in;
     if (n == 0) { if (tid == 0) *m_out = -1; return; }      // "No markers detected in first frame!"
     for (int i = tid; i < n; i += nthr) { px[i] = det[i * 6 + 0]; py[i] = det[i * 6 + 1]; }
     __syncthreads();
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void k_assign_ids(const double* __restrict__ d
     __syncthreads();
     for (int i = tid; i < nr; i += nthr) rad[i] = srt[i];
     __syncthreads();
-    const int k = max(1, min(min(num_layers, IDS_MAXK), nr));
+    const int k = max(1, min(min(num_layers, IDS_MAXK), nr));      // (vbs_assign_ids refuses num_layers > IDS_MAXK)
     if (nr > 0) {
         // ---- kmeans_1d(radius, k): stable argsort, prefix sums, exact DP over contiguous partitions ----
         for (int i = tid; i < nr; i += nthr) {

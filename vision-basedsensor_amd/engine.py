@@ -540,6 +540,9 @@ class Engine:
         reference dict's order.  `det` / `counts` are frame 0's rows of `marker_center` / `track_to_3d(want_det=True)`."""
         if id_mode not in ("as_written", "full"):
             raise ValueError(f"id_mode must be 'as_written' or 'full', got {id_mode!r}")
+        if int(num_layers) > L.IDS_MAX_LAYERS:
+            raise ValueError(f"vbs_assign_ids: num_layers {int(num_layers)} above the kernel's {L.IDS_MAX_LAYERS} "
+                             "(VBS_IDS_MAX_LAYERS); ids.assign_ids on the host has no such limit")
         det0 = (det[0] if det.dim() == 3 else det).contiguous()
         cnt0 = counts.reshape(-1)[:1].contiguous()
         cap = det0.shape[0] + 1
@@ -555,6 +558,9 @@ class Engine:
             raise ValueError("No markers detected in first frame!")
         if mm <= -1000:
             raise L.VbsError(f"device status {mm // 1000} in frame 0")
+        if mm == -3:
+            raise L.VbsError(f"vbs_assign_ids: more than {L.IDS_MAX_MARKERS} markers in frame 0 (VBS_IDS_MAX_MARKERS); "
+                             "nothing was assigned")
         if mm < 0:
             raise L.VbsError(f"vbs_assign_ids: device status {mm}")
         return ids[:mm], xy[:mm]

@@ -477,10 +477,11 @@ class MarkerTracker:
             # bit for bit the device's arrays are the ones the tracking calls use, else the host's (the reference's own
             # order: the two may only differ in the order of markers at mathematically equal angles).  `first_frame_markers`
             # - the reference's attribute, marker dicts and all - is the host table either way.  The kernel covers
-            # num_layers <= 16 (k_ids.hip): a configuration beyond that runs on the host alone, as it always did.
+            # num_layers <= VBS_IDS_MAX_LAYERS (16): a configuration beyond that runs on the host alone, as it always did.
             self._ref_arrays = None
+            from ._lib import IDS_MAX_LAYERS
             if (self.config.get("kmeans", "optimal") == "optimal" and self.config.get("ids_on_device", True)
-                    and int(self.config.get("num_layers", 5)) <= 16):
+                    and int(self.config.get("num_layers", 5)) <= IDS_MAX_LAYERS):
                 ids_h, xy_h = _ids.reference_arrays(self.first_frame_markers)
                 ids_d, xy_d = eng.assign_ids(det, counts, self.config.get("num_layers", 5),
                                              self.config.get("id_mode", "as_written"))

@@ -41,11 +41,11 @@ def reference_from_frame0(eng: Engine, frame0: torch.Tensor, num_layers=5, id_mo
         np.arctan2's last bit decides on the host, the device's atan2 on the GPU) -> the host table, the reference's own
         order (`"host"`, `slots_in_another_order` says how many slots);
       * anything else raises.
-    The device kernel covers `num_layers <= 16` (k_ids.hip: IDS_MAXK) and `kmeans == "optimal"`; other configurations run
+    The device kernel covers `num_layers <= L.IDS_MAX_LAYERS` (16, VBS_IDS_MAX_LAYERS) and `kmeans == "optimal"`; other configurations run
     on the host alone (`"host"`, `on_device: False`) as they always did."""
     _, det, counts = eng.track_to_3d(frame0[:1], None, want_det=True)
     dev = None
-    if ids_on_device and kmeans == "optimal" and int(num_layers) <= 16:
+    if ids_on_device and kmeans == "optimal" and int(num_layers) <= L.IDS_MAX_LAYERS:
         ids_d, xy_d = eng.assign_ids(det, counts, num_layers, id_mode)      # raises the reference's ValueError on no markers
         dev = (ids_d.cpu().numpy().astype("int64"), xy_d.cpu().numpy())
     n0 = int(counts[0].item())
