@@ -672,6 +672,46 @@ int vbs_find_steps_f64(int device, const double* resp, int n, int s, int resp_co
 int vbs_dwell_stats_f64(int device, const double* rec, int n, int s, int cols, int n_values, const int32_t* steps, int steps_rows,
                         int max_steps, int guard, double* out, void* stream);
 
+/* ---- Pose misalignment along a recording (ForceDistribution.py's deviation field and plane, for every frame): plane, tilt, trend ----
+ * vbs_pose_series - what vbs_deviation_plane gives for four table rows, for every frame of [frame_begin, frame_end) of a table
+ * holding frames [0, n), in float64, against a reference state that is given once.
+ *   table [dev] float32 [n, m_ref, VBS_TABLE_COLS];  ref_disp [dev] float64 [m_ref, 4] = (flag, dX, dY, dZ): the displacement field
+ *   of the reference state (one frame of vbs_axis_displacement's `axis` is a valid input as it is);  ref_xyz [dev] float64
+ *   [m_ref, 3] reference positions;  slot_mask [dev] uint8 [m_ref] as vbs_axis_displacement's (may be NULL = all).
+ * A slot r is COMMON in frame f when it is selected, ref_disp[r][0] != 0, and its rows in start_frame and in f both carry
+ * VBS_FLAG_XYZ.  Where common, per axis (cols 6-8)  d = ((double)X_f - (double)X_start) - ref_disp[r],  the end point is
+ * P = (ref_x + scale dX, ref_y + scale dY, (shell_mode ? ref_z : 0.0) + scale dZ)  and  |d| = sqrt(dX dX + dY dY + dZ dZ), added
+ * left to right.  Nothing else of a slot is ever read into a sum: the XYZ of rows without the flag and ref_disp rows with flag 0
+ * may hold NaN.
+ *   deviation [dev] float64 [fe-fb, m_ref, 4] = (1, dX, dY, dZ) where common, else (0, 0, 0, 0)
+ *   field [dev] float64 [fe-fb, VBS_POSEFIELD_COLS] = complete, count, the means of scale d and of |d| over the common slots
+ *       (zeros at count 0); complete = 1 when count equals the number of selected slots valid in ref_disp and in start_frame and
+ *       that number is >= 1.  `field` is always over ALL common slots
+ *   pose [dev] float64 [fe-fb, VBS_POSE_COLS] = flag, a, b, c, tilt_deg, azimuth_deg, rms, n_used
+ * Any of the three may be NULL (not all).  EVERY SUM FOLLOWS THE RULE OF vbs_axis_displacement, WHICH IS PART OF THE INTERFACE:
+ * lane l of 64 adds slots l, l + 64, ... in ascending order (other slots add nothing - selected, never multiplied by zero), the
+ * 64 lane sums are folded a[i] + a[i + 32], then + 16, 8, 4, 2, 1.  No atomics, float64 without contraction: no result depends
+ * on the launch shape, on the range or on VBS_POSE_GROUP (the frames a workgroup takes: stated for tests of its edges).
+ * The plane, with the formulas of vbs_deviation_plane: the means (mx, my, mz) of P; the centred sums xx, xy, yy, xz, yz, recomputed
+ * from the table (never from a rounded output); det = xx yy - xy xy; a plane exists iff count >= 3 and |det| > 1e-300;
+ * a = (xz yy - yz xy) / det, b = (yz xx - xz xy) / det, c = mz - a mx - b my.  The residual of a slot on the centred coordinates is
+ * r = z - (a x + b y), SSR = the sum of r r by the same rule, rms = sqrt(SSR / n_used), tilt_deg = atan(sqrt(a a + b b)) and
+ * azimuth_deg = atan2(b, a), both times 57.29577951308232 (the azimuth is the steep direction: where the plane rises).
+ * One round of outlier rejection, only when reject_k > 0, a plane exists and SSR > 0: the common slots with
+ * r r <= (reject_k reject_k) (SSR / count) are kept (squared: no square root decides).  If fewer are kept than are common and the
+ * kept set still gives a plane (kept >= 3, |det| > 1e-300 of its own centred sums), means, sums, plane and SSR are those of the
+ * kept set, n_used = kept and flag = 2; otherwise the first plane stands with n_used = count and flag = 1.  flag = 0: no plane;
+ * a .. rms are 0 and n_used = count.  A nonzero flag is what vbs_fir_series_f64 reads as valid: `pose` seen as [F, 1, 8] with
+ * n_values = 3 is a FIR input (a, b, c; angles are never filtered).
+ * start_frame outside [0, n), a range outside 0 <= fb <= fe <= n, reject_k negative or not finite, scale not finite, m_ref < 1,
+ * a shell_mode other than 0 / 1: VBS_EINVAL; fb == fe emits nothing.  The call allocates nothing. */
+#define VBS_POSE_COLS      8   /* flag, a, b, c, tilt_deg, azimuth_deg, rms, n_used                     */
+#define VBS_POSEFIELD_COLS 6   /* complete, count, mean k dX, mean k dY, mean k dZ, mean |d|            */
+#define VBS_POSE_GROUP     8   /* frames a workgroup takes, one wave each (no result depends on it)     */
+int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
+                    const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k, int frame_begin,
+                    int frame_end, double* deviation, double* field, double* pose, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

@@ -1030,6 +1030,25 @@ extern "C" int vbs_fir_series_f64(int device, const double* rec, int n, int s, i
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- pose misalignment along a recording (k_pose.hip) ---------------------------------------------------------------------------
+extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
+                               const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k,
+                               int frame_begin, int frame_end, double* deviation, double* field, double* pose, void* stream) {
+    if (!h) return VBS_EINVAL;
+    if (!table || !ref_disp || !ref_xyz || (!deviation && !field && !pose) || !series_shape_ok(n, m_ref, 0) || start_frame < 0 ||
+        start_frame >= n || frame_begin < 0 || frame_end > n || frame_begin > frame_end || (shell_mode != 0 && shell_mode != 1) ||
+        !std::isfinite(scale) || !std::isfinite(reject_k) || reject_k < 0.0) {
+        h->err = "vbs_pose_series: bad argument (start_frame inside [0, n), 0 <= frame_begin <= frame_end <= n, reject_k >= 0, "
+                 "scale and reject_k finite, shell_mode 0 or 1, at least one output)";
+        return VBS_EINVAL;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (frame_end > frame_begin)
+        launch_pose_series(h, table, m_ref, start_frame, ref_disp, ref_xyz, slot_mask, shell_mode, scale, reject_k, frame_begin,
+                           frame_end, deviation, field, pose, (hipStream_t)stream);
+    return check_launch(h);
+}
+
 // ---- the probe-indentation validation (k_steps.hip) ---------------------------------------------------------------------------
 static bool record_shape_ok(int n, int s, int cols, int n_values) {
     return series_shape_ok(n, s, 0) && cols >= 2 && cols <= 8 && n_values >= 1 && n_values < cols;

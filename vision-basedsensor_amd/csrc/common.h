@@ -239,6 +239,10 @@ void launch_axis_displacement(vbs_handle* h, const float* table, int m_ref, int 
                               int frame_end, double* axis, double* total, hipStream_t s);
 void launch_fir_series(const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half, double need,
                        int frame_begin, int frame_end, double* out, hipStream_t st);
+// k_pose.hip (f12): deviation field, plane, tilt, steep direction and residual of every frame against a reference state
+void launch_pose_series(vbs_handle* h, const float* table, int m_ref, int start_frame, const double* ref_disp, const double* ref_xyz,
+                        const u8* slot_mask, int shell, double scale, double reject_k, int frame_begin, int frame_end,
+                        double* deviation, double* field, double* pose, hipStream_t s);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

@@ -534,6 +534,38 @@ class Engine:
                                                        _ptr(total), self._stream()), "vbs_axis_displacement")
         return axis, total
 
+    def pose_series(self, table, ref_disp, ref_xyz, start_frame=0, mode="plane", scale=1.0, slots=None, reject_k=0.0,
+                    frame_range=None):
+        """Pose misalignment for every frame of a recording (`vbs_pose_series`): the deviation of the displacement field against
+        frame `start_frame` from the reference state's field `ref_disp` [m, 4] (flag, dX, dY, dZ: one frame of
+        `axis_displacement`'s `axis`), the plane through reference position + scale * deviation (`ref_xyz` [m, 3]; `mode` as
+        `deviation_plane`), its tilt, steep direction and residual.  Returns float64 device tensors `(deviation, field, pose)` =
+        [b-a, m, 4] (common, dX, dY, dZ), [b-a, 6] (complete, count, mean scaled dX, dY, dZ, mean |d|) and [b-a, 8] (flag, a, b,
+        c, tilt_deg, azimuth_deg, rms, n_used; flag 0 = no plane, 1 = the plane of all common slots, 2 = refitted after one round
+        of rejection at `reject_k` times the rms residual; `reject_k = 0`: no rejection).  `slots` selects markers as `axis_displacement` does; `frame_range=(a, b)` emits only
+        frames [a, b) of the table."""
+        table = self._table32(table)
+        n, m = table.shape[0], table.shape[1]
+        a, b, shell = _pose_args(n, m, start_frame, mode, scale, slots, reject_k, frame_range)
+        rd = torch.as_tensor(ref_disp, dtype=torch.float64, device=self.device).contiguous()
+        rx = torch.as_tensor(ref_xyz, dtype=torch.float64, device=self.device).contiguous()
+        if tuple(rd.shape) != (m, L.AXIS_COLS) or tuple(rx.shape) != (m, 3):
+            raise ValueError(f"ref_disp must be [{m}, {L.AXIS_COLS}] and ref_xyz [{m}, 3]: one row per table slot")
+        mask = None
+        if slots is not None:
+            mask = torch.zeros((m,), dtype=torch.uint8, device=self.device)
+            mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=self.device)] = 1
+        deviation = torch.empty((b - a, m, 4), dtype=torch.float64, device=self.device)
+        field = torch.empty((b - a, L.POSEFIELD_COLS), dtype=torch.float64, device=self.device)
+        pose = torch.empty((b - a, L.POSE_COLS), dtype=torch.float64, device=self.device)
+        if a == b:
+            return deviation, field, pose
+        with torch.cuda.device(self.device):
+            self._check(self.lib.vbs_pose_series(self._h, _ptr(table), n, m, int(start_frame), _ptr(rd), _ptr(rx), _ptr(mask), shell,
+                                                 float(scale), float(reject_k), a, b, _ptr(deviation), _ptr(field), _ptr(pose),
+                                                 self._stream()), "vbs_pose_series")
+        return deviation, field, pose
+
     # ---- a14 / f4 ------------------------------------------------------------------------------
     def assign_ids(self, det, counts, num_layers=5, id_mode="as_written"):
         """Frame-0 identities on the device: (ids int32 [M,2], ref_xy float64 [M,2]) as device tensors, in the
@@ -803,6 +835,26 @@ def series_stats_f64(disp64, frame_begin=0, cumulative=False, device=None):
     if rc != L.VBS_OK:
         raise L.VbsError(f"vbs_series_stats_f64 failed ({rc})")
     return (stats, cum) if cumulative else stats
+
+
+def _pose_args(n, m, start_frame, mode, scale, slots, reject_k, frame_range):
+    """`Engine.pose_series`'s argument checks (no device needed): -> (a, b, shell_mode) or ValueError."""
+    if mode not in ("plane", "shell"):
+        raise ValueError("mode must be 'plane' or 'shell'")
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the table's {n} frames")
+    if not (0 <= int(start_frame) < n):
+        raise ValueError(f"start_frame {start_frame} outside the table's {n} frames")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"scale {scale} is not finite")
+    if not (np.isfinite(float(reject_k)) and float(reject_k) >= 0.0):
+        raise ValueError(f"reject_k {reject_k} must be finite and >= 0 (0 = no rejection)")
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= m):
+            raise ValueError(f"slots outside the table's {m} slots")
+    return a, b, 1 if mode == "shell" else 0
 
 
 def fir_series_f64(rec, taps, n_values=None, min_coverage=0.5, frame_range=None, device=None):

@@ -232,6 +232,76 @@ def to_total_frame(total, total_filtered, frame_offset=0, path=None):
     return df
 
 
+# ---- pose misalignment along a recording (k_pose.hip): `deviation_pose` for every frame, with its trend ----------------------------
+_DEG = 57.29577951308232
+
+
+def misalignment_analysis(eng: Engine, table: torch.Tensor, table_ref: torch.Tensor, ref_xyz, taps=None, start=0, ref_start=0,
+                          ref_end=-1, mode="plane", scale=1.0, slots=None, reject_k=0.0, min_coverage=0.5):
+    """`deviation_pose` for every frame of a recording: `table_ref` [Nr, M, 10] is the reference state's session
+    (the vertical loading), whose displacement between its frames `ref_start` and `ref_end` is the field every frame of `table`
+    [N, M, 10] is compared with - frame f of `table` against its frame `start`.  Both tables use the same slot order.  Returns a
+    dict of device tensors (float64): `ref_disp` [M, 4], `deviation` [N, M, 4], `field` [N, 6], `pose` [N, 8]
+    (`Engine.pose_series`) and, with `taps` (a full odd-length symmetric FIR, `filters.lowpass_taps`): `pose_filtered` [N, 7] =
+    flag, trend and residual of the plane's a, b, c over the frames that have a plane (`fir_series_f64`), and `trend` [N, 3] =
+    flag (1 where the frame has a trend), tilt_deg and azimuth_deg OF THE FILTERED a and b - angles themselves are never
+    filtered (an azimuth wraps, a tilt is not linear in the plane)."""
+    from .engine import fir_series_f64
+    n_ref = int(table_ref.shape[0])
+    end = int(ref_end) + n_ref if int(ref_end) < 0 else int(ref_end)
+    if not (0 <= end < n_ref):
+        raise ValueError(f"ref_end {ref_end} outside the reference table's {n_ref} frames")
+    ref_disp = eng.axis_displacement(table_ref, ref_start, slots, frame_range=(end, end + 1))[0][0]
+    deviation, field, pose = eng.pose_series(table, ref_disp, ref_xyz, start, mode, scale, slots, reject_k)
+    out = {"ref_disp": ref_disp, "deviation": deviation, "field": field, "pose": pose}
+    if taps is not None:
+        pf = fir_series_f64(pose[:, None, :], taps, 3, min_coverage, device=eng.device.index)[:, 0]
+        ok = pf[:, 0] == 3.0
+        a, b = pf[:, 1], pf[:, 2]
+        zero = torch.zeros_like(a)
+        out["pose_filtered"] = pf
+        out["trend"] = torch.stack([ok.to(torch.float64), torch.where(ok, torch.atan(torch.sqrt(a * a + b * b)) * _DEG, zero),
+                                    torch.where(ok, torch.atan2(b, a) * _DEG, zero)], dim=1)
+    return out
+
+
+POSE_FRAME_COLUMNS = ("frameno", "count", "complete", "n_used", "flag", "a", "b", "c", "tilt_deg", "azimuth_deg", "rms", "mean_dX",
+                      "mean_dY", "mean_dZ", "mean_mag")
+POSE_TREND_COLUMNS = ("a_f", "b_f", "c_f", "tilt_f", "azimuth_f")
+
+
+def to_pose_frame(field, pose, pose_filtered=None, frame_offset=0, path=None):
+    """The sheet of `misalignment_analysis`: one row per frame with `POSE_FRAME_COLUMNS` from `field` [N, 6] and `pose` [N, 8],
+    and with `pose_filtered` [N, 7] also `POSE_TREND_COLUMNS` (the angles computed from the filtered a and b).  a .. rms are NaN
+    (empty cells) where the frame has no plane (flag 0), the trend columns where it has no trend (flag != 3).  `path`: also
+    written as .xlsx (`xlsx_io.dataframe_to_xlsx`)."""
+    import pandas as pd
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    fl, po = host(field), host(pose)
+    if fl.ndim != 2 or fl.shape[1] != L.POSEFIELD_COLS or po.shape != (fl.shape[0], L.POSE_COLS):
+        raise ValueError(f"field must be [N, {L.POSEFIELD_COLS}] and pose [N, {L.POSE_COLS}]")
+    plane = np.where((po[:, 0] != 0)[:, None], po[:, 1:7], np.nan)
+    cols = {"frameno": np.arange(fl.shape[0], dtype=np.int64) + int(frame_offset), "count": fl[:, 1].astype(np.int64),
+            "complete": fl[:, 0].astype(np.int64), "n_used": po[:, 7].astype(np.int64), "flag": po[:, 0].astype(np.int64)}
+    for k, name in enumerate(("a", "b", "c", "tilt_deg", "azimuth_deg", "rms")):
+        cols[name] = plane[:, k]
+    for k, name in enumerate(("mean_dX", "mean_dY", "mean_dZ", "mean_mag")):
+        cols[name] = fl[:, 2 + k].astype(np.float64)
+    if pose_filtered is not None:
+        pf = host(pose_filtered)
+        if pf.shape != (fl.shape[0], 7):
+            raise ValueError("pose_filtered must be [N, 7]")
+        t = np.where((pf[:, 0] == 3.0)[:, None], pf[:, 1:4], np.nan)
+        cols["a_f"], cols["b_f"], cols["c_f"] = t[:, 0], t[:, 1], t[:, 2]
+        cols["tilt_f"] = np.arctan(np.sqrt(t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1])) * _DEG
+        cols["azimuth_f"] = np.arctan2(t[:, 1], t[:, 0]) * _DEG
+    df = pd.DataFrame(cols)
+    if path is not None:
+        from .xlsx_io import dataframe_to_xlsx
+        dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- the probe-indentation validation (k_steps.hip): the reference's Figure 6(b) from a tracked table -------------------------
 @dataclass
 class IndentationResult:
