@@ -712,6 +712,59 @@ int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int sta
                     const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k, int frame_begin,
                     int frame_end, double* deviation, double* field, double* pose, void* stream);
 
+/* ---- Contact maps along a recording (the reference's Figure 4(c) stops at arrows on the markers; it ships no code for this) ----
+ * The spatial counterpart of vbs_fir_series_f64: a gap-aware, normalised kernel smoother in space, for every frame of a recording
+ * in one launch, and the contact patch of every resulting map.  Two entries without a handle.  The operator, the coverage rule
+ * and the patch definition are this project's.
+ *
+ * vbs_field_map_f64 - rec [dev] float64 [n, s, cols], time-major, the record layout vbs_fir_series_f64 takes: col 0 the flag
+ * (nonzero = valid), cols 1 .. n_values the values, 1 <= n_values <= 3, n_values < cols <= 8 (one range of
+ * vbs_axis_displacement's `axis` and vbs_pose_series's `deviation` are valid inputs as they are).  W [dev] float64 [P, s],
+ * row-major: the non-negative weight of slot m at grid point p, computed by the caller (as the FIR's taps are: no exp of the
+ * device enters a result).  wsum [dev] float64 [P]: the caller's full row sums.  For frame f of [frame_begin, frame_end) and grid
+ * point p, over the VALID slots only:
+ *     den = sum W[p,m],   num_v = sum W[p,m] x_v[f,m],   ok = den > 0 && den >= min_coverage * wsum[p]
+ * map [dev] float64 [fe-fb, P, 1 + n_values] = (ok, num_v / den ..), all zeros where !ok.  Invalid entries are selected out when
+ * they are staged, never multiplied by zero: they may hold NaN or 1e300, and so may every column beyond n_values.
+ * The kernel is a float64 matrix product on v_mfma_f64_16x16x4_f64: a tile is 16 grid points x 16 columns = VBS_FIELD_FRAMES
+ * frames x (x1, x2, x3, flag as 1.0 / 0.0); padding is selected zeros, never a read past s or P.  No atomics.
+ * THE ORDER OF SUMMATION IS NOT PART OF THIS INTERFACE (unlike the entries above): the order inside the matrix instruction is not
+ * documented, and nothing rests on it.  What is promised instead:
+ *   - exact where the inputs make every order exact: if every product and every partial sum is representable, num and den are
+ *     exact and the quotient is the correctly rounded one;
+ *   - otherwise, with u = 2^-53, gamma_k = k u / (1 - k u), A = sum W |x_v| and d = sum W over the valid slots:
+ *     |value - num / den| <= (2 gamma_(s+6) + 2 u) A / d, for any order of summation, with or without fused multiply-add
+ *     (derived in DESIGN 4.14);
+ *   - bit-identical under every change of batching: run to run, range by range, a frame alone or at any position of a tile, and
+ *     with dead (invalid) slots appended.  No result depends on how many frames a workgroup takes.
+ * A null pointer, n, s or P < 1, bad cols / n_values, min_coverage outside (0, 1], a range outside 0 <= fb <= fe <= n:
+ * VBS_EINVAL; s > VBS_FIELD_MAX_SLOTS or P > VBS_FIELD_MAX_POINTS: VBS_ECAPACITY; all decided before the device is touched.
+ * fb == fe emits nothing.  The call allocates nothing.
+ *
+ * vbs_patch_stats_f64 - the contact patch of every frame of a map.  map [dev] float64 [F, P, 1 + n_values] as above, grid_xy
+ * [dev] float64 [P, 2]; component 0 .. n_values-1, or -1 for the squared norm; sign +1 or -1; thr >= 0, for component -1 the
+ * SQUARED threshold, computed by the caller.  A point is COVERED when its flag is nonzero.  Its score is sign * v_component; for
+ * component -1 it is v1 v1 + v2 v2 + v3 v3 (the values there are), added left to right.  It is IN THE PATCH when it is covered and
+ * score >= thr; a NaN score is never in the patch.
+ * patch [dev] float64 [F, VBS_PATCH_COLS] = flag, covered, count, S, cx, cy, peak, peak_index:  S = sum score,
+ * cx = (sum score gx) / S, cy = (sum score gy) / S over the patch; peak = the largest score in the patch and peak_index its p,
+ * the smallest p among equal maxima.  flag 0: nothing is covered, everything else is 0.  flag 1: covered, but the patch is empty
+ * or S <= 0: cx, cy, peak are 0 and peak_index is -1.  flag 2: a patch with a centre.
+ * EVERY SUM FOLLOWS THE RULE OF vbs_axis_displacement, WHICH IS PART OF THE INTERFACE: lane l of 64 adds points l, l + 64, ... in
+ * ascending order (selected, never multiplied by zero), the 64 lane sums are folded a[i] + a[i + 32], then + 16, 8, 4, 2, 1; the
+ * peak folds the same way.  One wave per frame, VBS_PATCH_GROUP frames a workgroup, no result depending on it; float64 without
+ * contraction, no atomics.  A null pointer, F or P < 1, n_values outside 1..3, a component outside -1 .. n_values-1, a sign other
+ * than +-1, thr NaN or negative: VBS_EINVAL; P > VBS_FIELD_MAX_POINTS: VBS_ECAPACITY; decided before the device is touched. */
+#define VBS_FIELD_FRAMES     4       /* frames of a 16-column tile: 4 x (x1, x2, x3, flag)                  */
+#define VBS_FIELD_MAX_SLOTS  1024    /* s at most (the cap of max_markers)                                   */
+#define VBS_FIELD_MAX_POINTS 65536   /* P at most                                                            */
+#define VBS_PATCH_COLS       8       /* flag, covered, count, S, cx, cy, peak, peak_index                    */
+#define VBS_PATCH_GROUP      8       /* frames a workgroup takes, one wave each (no result depends on it)    */
+int vbs_field_map_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* W, const double* wsum,
+                      int P, double min_coverage, int frame_begin, int frame_end, double* map, void* stream);
+int vbs_patch_stats_f64(int device, const double* map, int F, int P, int n_values, const double* grid_xy, int component,
+                        double sign, double thr, double* patch, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

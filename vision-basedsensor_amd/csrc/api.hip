@@ -1049,6 +1049,35 @@ extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_r
     return check_launch(h);
 }
 
+// ---- contact maps along a recording (k_field.hip) -------------------------------------------------------------------------------
+extern "C" int vbs_field_map_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* W,
+                                 const double* wsum, int P, double min_coverage, int frame_begin, int frame_end, double* map,
+                                 void* stream) {
+    if (!rec || !W || !wsum || !map || n < 1 || s < 1 || P < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
+        n_values >= cols || !(min_coverage > 0.0 && min_coverage <= 1.0) || frame_begin < 0 || frame_end > n ||
+        frame_begin > frame_end)
+        return VBS_EINVAL;
+    if (s > VBS_FIELD_MAX_SLOTS || P > VBS_FIELD_MAX_POINTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin) {
+        const int rc = launch_field_map(rec, s, cols, n_values, W, wsum, P, min_coverage, frame_begin, frame_end, map,
+                                        (hipStream_t)stream);
+        if (rc != VBS_OK) { (void)hipGetLastError(); return rc; }
+    }
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_patch_stats_f64(int device, const double* map, int F, int P, int n_values, const double* grid_xy, int component,
+                                   double sign, double thr, double* patch, void* stream) {
+    if (!map || !grid_xy || !patch || F < 1 || P < 1 || n_values < 1 || n_values > 3 || component < -1 || component >= n_values ||
+        !(sign == 1.0 || sign == -1.0) || !(thr >= 0.0))
+        return VBS_EINVAL;
+    if (P > VBS_FIELD_MAX_POINTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_patch_stats(map, F, P, n_values, grid_xy, component, sign, thr, patch, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- the probe-indentation validation (k_steps.hip) ---------------------------------------------------------------------------
 static bool record_shape_ok(int n, int s, int cols, int n_values) {
     return series_shape_ok(n, s, 0) && cols >= 2 && cols <= 8 && n_values >= 1 && n_values < cols;

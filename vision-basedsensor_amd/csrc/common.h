@@ -243,6 +243,12 @@ void launch_fir_series(const double* rec, int n, int s, int cols, int n_values, 
 void launch_pose_series(vbs_handle* h, const float* table, int m_ref, int start_frame, const double* ref_disp, const double* ref_xyz,
                         const u8* slot_mask, int shell, double scale, double reject_k, int frame_begin, int frame_end,
                         double* deviation, double* field, double* pose, hipStream_t s);
+// k_field.hip (f13): the kernel smoother in space on the float64 matrix instruction (VBS_OK, or VBS_EHIP when the LDS it asks
+// for is refused), and the contact patch of every map
+int launch_field_map(const double* rec, int s, int cols, int n_values, const double* W, const double* wsum, int P,
+                     double min_coverage, int frame_begin, int frame_end, double* map, hipStream_t st);
+void launch_patch_stats(const double* map, int F, int P, int n_values, const double* grid_xy, int component, double sign, double thr,
+                        double* patch, hipStream_t st);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

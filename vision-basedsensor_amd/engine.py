@@ -893,6 +893,120 @@ def fir_series_f64(rec, taps, n_values=None, min_coverage=0.5, frame_range=None,
     return out
 
 
+# ---- contact maps along a recording (k_field.hip): the smoother in space, the contact patch ------------------------------------
+def _field_args(n, s, cols, P, w_shape, wsum_shape, min_coverage, n_values, frame_range):
+    """`field_map_f64`'s argument checks (no device needed): -> (a, b, n_values) or ValueError."""
+    if n < 1 or s < 1 or not (2 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
+    if tuple(w_shape) != (P, s) or P < 1:
+        raise ValueError(f"W must be [P >= 1, {s}]: one weight per grid point and slot of rec")
+    if wsum_shape is not None and tuple(wsum_shape) != (P,):
+        raise ValueError(f"wsum must be [{P}]")
+    nv = min(cols - 1, 3) if n_values is None else int(n_values)
+    if not (1 <= nv <= 3 and nv < cols):
+        raise ValueError("n_values must be 1 .. 3 and below cols")
+    mc = float(min_coverage)
+    if not (mc > 0.0 and mc <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    if s > L.FIELD_MAX_SLOTS:
+        raise L.VbsError(f"vbs_field_map_f64: {s} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
+    if P > L.FIELD_MAX_POINTS:
+        raise L.VbsError(f"vbs_field_map_f64: {P} grid points exceed VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} "
+                         f"(status {L.VBS_ECAPACITY})")
+    return a, b, nv
+
+
+def field_map_f64(rec, W, wsum=None, min_coverage=0.5, n_values=None, frame_range=None, device=None):
+    """A normalised kernel smoother in space with gaps (`vbs_field_map_f64`), every frame in one launch.  rec float64
+    [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default min(cols - 1, 3)).
+    W float64 [P, s]: non-negative weights of slot m at grid point p (`fields.gaussian_weights`); wsum [P] its full row sums
+    (default `fields.row_sums(W)`, on the host).  Returns float64 [b-a, P, 1 + n_values] = ok, the weighted mean of every value
+    over the valid slots, for the frames [a, b) of `frame_range` (default all): ok where the valid weight is positive and at
+    least min_coverage * wsum, zeros elsewhere.  An output does not depend on the range it was asked in."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    if wsum is None:
+        from .fields import row_sums
+        wsum = row_sums(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else W)
+    w = torch.as_tensor(W, dtype=torch.float64, device=dev).contiguous()
+    ws = torch.as_tensor(wsum, dtype=torch.float64, device=dev).contiguous()
+    n, s, cols = r.shape
+    P = w.shape[0] if w.dim() == 2 else 0
+    a, b, nv = _field_args(n, s, cols, P, w.shape, ws.shape, min_coverage, n_values, frame_range)
+    out = torch.empty((b - a, P, 1 + nv), dtype=torch.float64, device=dev)
+    if a == b:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_field_map_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(w), _ptr(ws), P, float(min_coverage), a, b,
+                                       _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_field_map_f64: bad argument (min_coverage in (0, 1], 1 <= n_values <= 3, n_values < cols <= 8)")
+    if rc == L.VBS_ECAPACITY:
+        raise L.VbsError(f"vbs_field_map_f64: more than VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} slots or VBS_FIELD_MAX_POINTS = "
+                         f"{L.FIELD_MAX_POINTS} grid points (status {rc})")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_field_map_f64 failed ({rc})")
+    return out
+
+
+def _patch_args(F, P, oc, grid_shape, component, sign, threshold):
+    """`patch_stats_f64`'s argument checks (no device needed): -> (n_values, component, sign, thr as the entry takes it)."""
+    nv = oc - 1
+    if F < 0 or P < 1 or not (1 <= nv <= 3):
+        raise ValueError("map must be [F, P >= 1, 2 .. 4]")
+    if tuple(grid_shape) != (P, 2):
+        raise ValueError(f"grid_xy must be [{P}, 2]")
+    c = int(component)
+    if not (-1 <= c < nv):
+        raise ValueError(f"component must be 0 .. {nv - 1}, or -1 for the squared norm")
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("sign must be +1 or -1")
+    thr = float(threshold)
+    if not (thr >= 0.0):
+        raise ValueError("threshold must be >= 0")
+    if P > L.FIELD_MAX_POINTS:
+        raise L.VbsError(f"vbs_patch_stats_f64: {P} grid points exceed VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} "
+                         f"(status {L.VBS_ECAPACITY})")
+    return nv, c, float(sign), thr * thr if c < 0 else thr
+
+
+def patch_stats_f64(map, grid_xy, component=2, sign=1.0, threshold=0.0, device=None):
+    """The contact patch of every frame of a map (`vbs_patch_stats_f64`).  map float64 [F, P, 1 + n_values] as `field_map_f64`
+    returns it, grid_xy float64 [P, 2].  The score of a covered point is sign * value[component], or for component -1 the squared
+    norm of its values; the patch is the covered points whose score reaches `threshold` (for component -1 `threshold` is a length:
+    its square is what is compared).  Returns float64 [F, 8] = flag (0 nothing covered, 1 no patch, 2 a patch with a centre),
+    covered, count, sum of the scores, score-weighted centre cx, cy, peak score, index of the peak (the first of equal ones)."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    m = torch.as_tensor(map, dtype=torch.float64, device=dev).contiguous()
+    g = torch.as_tensor(grid_xy, dtype=torch.float64, device=dev).contiguous()
+    if m.dim() != 3:
+        raise ValueError("map must be [F, P, 1 + n_values]")
+    F, P, oc = m.shape
+    nv, c, sg, thr = _patch_args(F, P, oc, g.shape, component, sign, threshold)
+    out = torch.empty((F, L.PATCH_COLS), dtype=torch.float64, device=dev)
+    if F == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_patch_stats_f64(dev.index, _ptr(m), F, P, nv, _ptr(g), c, sg, thr, _ptr(out),
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_patch_stats_f64: bad argument (component -1 .. n_values-1, sign +-1, threshold >= 0)")
+    if rc == L.VBS_ECAPACITY:
+        raise L.VbsError(f"vbs_patch_stats_f64: more than VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} grid points (status {rc})")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_patch_stats_f64 failed ({rc})")
+    return out
+
+
 # ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
 def _steps_call(name, what, fn):
     rc = fn()

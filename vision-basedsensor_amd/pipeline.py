@@ -302,6 +302,127 @@ def to_pose_frame(field, pose, pose_filtered=None, frame_offset=0, path=None):
     return df
 
 
+# ---- contact maps along a recording (k_field.hip): field on a grid, contact patch, centre, with their trend ----------------------
+_CONTACT_COMPONENT = {"x": 0, "y": 1, "z": 2, "xyz": -1}
+CONTACT_FRAME_COLUMNS = ("frameno", "flag", "covered", "count", "area_mm2", "sum", "cx", "cy", "peak", "peak_x", "peak_y")
+CONTACT_TREND_COLUMNS = ("sum_f", "cx_f", "cy_f")
+
+
+def _contact_args(n, m, grid_shape, bandwidth, component, sign, threshold, ref_frame, min_coverage, keep_maps, max_map_bytes):
+    """`contact_analysis`'s argument checks (no device needed): -> (P, frames per range, sorted kept frames) or ValueError."""
+    if len(tuple(grid_shape)) != 2 or int(grid_shape[0]) < 1 or int(grid_shape[1]) < 1:
+        raise ValueError("grid_shape must be (rows >= 1, columns >= 1)")
+    P = int(grid_shape[0]) * int(grid_shape[1])
+    if P > L.FIELD_MAX_POINTS:
+        raise ValueError(f"grid_shape {tuple(grid_shape)} has more than VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} points")
+    if m > L.FIELD_MAX_SLOTS:
+        raise ValueError(f"the table's {m} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS}")
+    if component not in _CONTACT_COMPONENT:
+        raise ValueError(f"component must be one of {sorted(_CONTACT_COMPONENT)}")
+    if float(sign) not in (1.0, -1.0):
+        raise ValueError("sign must be +1 or -1")
+    if not (float(threshold) >= 0.0):
+        raise ValueError("threshold must be >= 0")
+    if bandwidth is not None and not (np.isfinite(float(bandwidth)) and float(bandwidth) > 0.0):
+        raise ValueError("bandwidth must be finite and > 0")
+    if not (0 <= int(ref_frame) < n):
+        raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+    if not (0.0 < float(min_coverage) <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    keep = sorted({int(f) for f in keep_maps})
+    if keep and (keep[0] < 0 or keep[-1] >= n):
+        raise ValueError(f"keep_maps outside the table's {n} frames")
+    per_frame = P * 4 * 8
+    if int(max_map_bytes) < per_frame:
+        raise ValueError(f"max_map_bytes {max_map_bytes} holds no frame of the map ({per_frame} bytes)")
+    return P, int(max_map_bytes) // per_frame, keep
+
+
+def contact_analysis(eng: Engine, table: torch.Tensor, grid_shape=(64, 64), bandwidth=None, component="z", sign=1.0, threshold=0.1,
+                     ref_frame=0, slots=None, taps=None, min_coverage=0.5, keep_maps=(), max_map_bytes=256 << 20):
+    """The contact along a recording (the reference draws arrows on the markers only) from a table [N, M, 10]:
+    the displacement of every slot against `ref_frame` (`Engine.axis_displacement`) spread over a regular grid by a gap-aware
+    Gaussian smoother (`field_map_f64`; nodes = the X, Y of the selected slots valid in `ref_frame`, other slots get zero weight;
+    `bandwidth` default `fields.default_bandwidth`), and per frame the contact patch of that map (`patch_stats_f64`): the grid
+    points where `sign` * `component` ("x", "y", "z", or "xyz" = the norm) reaches `threshold` (in the table's units).  The maps
+    are computed in frame ranges of at most `max_map_bytes` and dropped again, except the frames listed in `keep_maps`; no
+    result depends on the ranges.  Returns a dict: `grid_xy` [P, 2], `cell_area`, `bandwidth`, `total` [N, 5], `patch` [N, 8],
+    `maps` {frame: [P, 4]} and, with `taps` (a full odd-length symmetric FIR), `patch_filtered` [N, 7] = flag, trend and
+    residual of S, cx, cy over the frames that have a patch with a centre (flag 2)."""
+    from . import fields
+    from .engine import field_map_f64, fir_series_f64, patch_stats_f64
+    n, m = int(table.shape[0]), int(table.shape[1])
+    P, per_range, keep = _contact_args(n, m, grid_shape, bandwidth, component, sign, threshold, ref_frame, min_coverage, keep_maps,
+                                       max_map_bytes)
+    dev = eng.device.index
+    axis, total = eng.axis_displacement(table, ref_frame, slots)
+    ref = table[int(ref_frame)].detach().cpu().numpy()
+    valid = (ref[:, 0].astype(np.int64) & L.FLAG_XYZ) != 0
+    if slots is not None:
+        pick = np.zeros(m, dtype=bool)
+        pick[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
+        valid &= pick
+    if not valid.any():
+        raise ValueError(f"no selected slot has a 3-D point in ref_frame {ref_frame}")
+    nodes = np.where(valid[:, None], ref[:, 6:8].astype(np.float64), np.nan)
+    h = fields.default_bandwidth(nodes) if bandwidth is None else float(bandwidth)
+    grid_xy, cell_area = fields.grid_over(nodes, grid_shape, 0.0)
+    W = fields.gaussian_weights(nodes, grid_xy, h)
+    Wd = torch.from_numpy(W).to(eng.device)
+    wsum = torch.from_numpy(fields.row_sums(W)).to(eng.device)
+    grid_d = torch.from_numpy(grid_xy).to(eng.device)
+    patch = torch.empty((n, L.PATCH_COLS), dtype=torch.float64, device=eng.device)
+    maps = {}
+    for a in range(0, n, per_range):
+        b = min(n, a + per_range)
+        mp = field_map_f64(axis, Wd, wsum, min_coverage, 3, (a, b), device=dev)
+        patch[a:b] = patch_stats_f64(mp, grid_d, _CONTACT_COMPONENT[component], sign, threshold, device=dev)
+        for f in keep:
+            if a <= f < b:
+                maps[f] = mp[f - a].clone()
+    out = {"grid_xy": grid_d, "cell_area": cell_area, "bandwidth": h, "total": total, "patch": patch, "maps": maps}
+    if taps is not None:
+        rec = torch.stack([(patch[:, 0] == 2.0).to(torch.float64), patch[:, 3], patch[:, 4], patch[:, 5]], dim=1)
+        out["patch_filtered"] = fir_series_f64(rec[:, None, :], taps, 3, min_coverage, device=dev)[:, 0]
+    return out
+
+
+def to_contact_frame(patch, cell_area, grid_xy, patch_filtered=None, frame_offset=0, path=None):
+    """The sheet of `contact_analysis`: one row per frame with `CONTACT_FRAME_COLUMNS` from `patch` [N, 8] - area_mm2 = count *
+    `cell_area`, peak_x / peak_y the grid point of the peak - and with `patch_filtered` [N, 7] also `CONTACT_TREND_COLUMNS`.
+    cx .. peak_y are NaN (empty cells) where the frame has no patch with a centre (flag != 2), the trend columns where it has no
+    trend (flag != 3).  `path`: also written, as .csv (`DataFrame.to_csv(index=False)`, the form the drop-in's CSV has) or as
+    .xlsx (`xlsx_io.dataframe_to_xlsx`)."""
+    import pandas as pd
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    pa, g = host(patch), host(grid_xy)
+    if pa.ndim != 2 or pa.shape[1] != L.PATCH_COLS or g.ndim != 2 or g.shape[1] != 2:
+        raise ValueError(f"patch must be [N, {L.PATCH_COLS}] and grid_xy [P, 2]")
+    has = pa[:, 0] == 2.0
+    idx = np.where(has, pa[:, 7], 0).astype(np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= g.shape[0]):
+        raise ValueError("a peak index lies outside grid_xy")
+    nan = lambda v: np.where(has, v, np.nan).astype(np.float64)                                    # noqa: E731
+    cols = {"frameno": np.arange(pa.shape[0], dtype=np.int64) + int(frame_offset), "flag": pa[:, 0].astype(np.int64),
+            "covered": pa[:, 1].astype(np.int64), "count": pa[:, 2].astype(np.int64),
+            "area_mm2": pa[:, 2].astype(np.float64) * float(cell_area), "sum": pa[:, 3].astype(np.float64),
+            "cx": nan(pa[:, 4]), "cy": nan(pa[:, 5]), "peak": nan(pa[:, 6]), "peak_x": nan(g[idx, 0]), "peak_y": nan(g[idx, 1])}
+    if patch_filtered is not None:
+        pf = host(patch_filtered)
+        if pf.shape != (pa.shape[0], 7):
+            raise ValueError("patch_filtered must be [N, 7]")
+        t = np.where((pf[:, 0] == 3.0)[:, None], pf[:, 1:4], np.nan)
+        cols["sum_f"], cols["cx_f"], cols["cy_f"] = t[:, 0], t[:, 1], t[:, 2]
+    df = pd.DataFrame(cols)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- the probe-indentation validation (k_steps.hip): the reference's Figure 6(b) from a tracked table -------------------------
 @dataclass
 class IndentationResult:
