@@ -765,6 +765,75 @@ int vbs_field_map_f64(int device, const double* rec, int n, int s, int cols, int
 int vbs_patch_stats_f64(int device, const double* map, int F, int P, int n_values, const double* grid_xy, int component,
                         double sign, double thr, double* patch, void* stream);
 
+/* ---- Displacement spectra along a recording (the reference's Figure 11(b) shows the oscillation; it ships no code for this) ----
+ * The bonnet spins and precesses, so every marker's displacement is periodic.  A gap-aware least-squares fit of
+ * x ~ c0 + a cos(theta) + b sin(theta) at every frequency of a list the caller chooses (a zoom grid round the spindle line,
+ * harmonics), in two entries without a handle: a gap-aware projection of every series onto a basis given by the caller, and a
+ * small kernel that turns those projections into fits and peaks.  Operator, conditioning rule and peak rule are this project's
+ * (DESIGN 4.15, 7).  A full-band spectrum on the natural grid q / n is an FFT's job; this is the tool for a BAND of Q << n
+ * frequencies at arbitrary real values.
+ *
+ * vbs_project_series_f64 - rec [dev] float64 [n, s, cols], time-major, the record layout vbs_fir_series_f64 takes: col 0 the flag
+ * (nonzero = valid), cols 1 .. n_values the values, 1 <= n_values <= 3, n_values < cols <= 8 (one range of vbs_axis_displacement's
+ * `axis` or `total`, of vbs_pose_series's `deviation`, or a FIR output's residual columns repacked, are valid inputs).  basis [dev]
+ * float64 [R, n], row-major, finite, computed by the caller (as the FIR's taps and the smoother's weights are: no sin / cos of the
+ * device enters a result).  For slot i and basis row r, over the VALID frames only:
+ *     den = sum basis[r,f],   num_v = sum basis[r,f] x_v[f,i]
+ * proj [dev] float64 [s, R, 1 + n_values] = (den, num_1 ..), SERIES-MAJOR: the projections of a series are contiguous, which is
+ * what vbs_harmonic_fit_f64 and a user read.  Invalid entries are selected out when they are staged, never multiplied by zero:
+ * they may hold NaN or 1e300, and so may every column beyond n_values.  A series with no valid frame gives exact zeros.
+ * The kernel is a float64 matrix product on v_mfma_f64_16x16x4_f64 with the frame axis as K: a tile is 16 basis rows x 16
+ * columns = VBS_PROJ_SLOTS slots x (x1, x2, x3, flag as 1.0 / 0.0), so the flag column's product IS den; padding (frames >= n
+ * inside a chunk, rows >= R, slots >= s, columns >= n_values) is selected zeros, never a read past n, R or s.  No atomics and NO
+ * SPLIT OF K ACROSS WORKGROUPS: every output is one accumulator chain over the frames, chunk after chunk of VBS_PROJ_CHUNK in
+ * ascending order from frame 0, so a result depends on its own basis row and its own series only.
+ * THE ORDER OF SUMMATION IS NOT PART OF THIS INTERFACE, as for vbs_field_map_f64.  What is promised instead:
+ *   - exact where the inputs make every order exact: if every product and every partial sum is representable, num and den are
+ *     exact;
+ *   - otherwise, with u = 2^-53, gamma_k = k u / (1 - k u), over the valid frames:
+ *     |num^ - num| <= gamma_(n+6) sum |basis x_v|   and   |den^ - den| <= gamma_(n+6) sum |basis|,
+ *     for any order of summation, with or without fused multiply-add (derived in DESIGN 4.15);
+ *   - bit-identical run to run, a basis row alone against the same row among R, a series alone against the same series among s,
+ *     with dead (invalid) slots appended and with dead frames appended at the end (zero-selected entries add exact zeros).
+ * A null pointer, n, s or R < 1, bad cols / n_values: VBS_EINVAL; n > VBS_PROJ_MAX_FRAMES, s > VBS_PROJ_MAX_SLOTS or
+ * R > VBS_PROJ_MAX_ROWS: VBS_ECAPACITY; a bad argument comes before a capacity; all decided before the device is touched.  The
+ * call allocates nothing.
+ *
+ * vbs_harmonic_fit_f64 - reads a proj [dev] float64 [s, R, 1 + n_values] whose basis had R == 1 + 4 Q rows in this order: row 0
+ * all ones; rows 1 + 2q, 2 + 2q the cos and sin of 2 pi nu_q f; rows 1 + 2Q + 2q, 2 + 2Q + 2q the cos and sin of 2 pi (2 nu_q) f.
+ * Per slot i, with N = proj[i,0,0] (the number of valid frames, an exact integer), per value v, m = proj[i,0,v] / N, and per bin q:
+ *     c1, s1 = den of rows 1+2q, 2+2q        c2, s2 = den of rows 1+2Q+2q, 2+2Q+2q
+ *     CC = 0.5 * (N + c2) - (c1 * c1) / N    SS = 0.5 * (N - c2) - (s1 * s1) / N    CS = 0.5 * s2 - (c1 * s1) / N
+ *     det = CC * SS - CS * CS                ok = N >= min_count && det > det_min * (N * N)
+ *     pc = num_v(row 1+2q) - m * c1          ps = num_v(row 2+2q) - m * s1
+ *     a = (pc * SS - ps * CS) / det          b = (ps * CC - pc * CS) / det          p = a * pc + b * ps
+ * the floating-mean least-squares fit solved by elimination; p is the drop in the sum of squares; the half-angle identities stand
+ * in for sum cos^2, sum sin^2, sum cos sin over the valid frames, which is why the 2 nu rows travel.  EVERY EXPRESSION IS EVALUATED
+ * AS WRITTEN, FLOAT64 WITHOUT CONTRACTION, AND THAT IS PART OF THIS INTERFACE; nothing here runs on a matrix instruction.  No
+ * square root and no atan2: amplitude hypot(a, b) and phase degrees(atan2(b, a)) (x ~ A cos(theta - phi)) are the caller's, as
+ * std is in vbs_dwell_stats_f64.
+ * fit (may be NULL) [dev] float64 [s, Q, 1 + 3 n_values] = ok, then (a, b, p) per value; all zeros where !ok.
+ * peak (may be NULL; not both) [dev] float64 [s, n_values, VBS_PEAK_COLS] = flag, N, mean, bin, a, b, p: the bin is the ok bin
+ * with the largest p; a NaN p never wins and never suppresses; the smallest q wins among equal maxima.  flag 2: a peak.  flag 1:
+ * N >= min_count but no ok bin with a non-NaN p: bin -1, a, b, p are 0.  flag 0: N < min_count: mean 0, bin -1, a, b, p 0.
+ * One wave per slot, VBS_FIT_GROUP slots a workgroup (no result depends on it); lane l of 64 takes bins l, l + 64, .. ascending,
+ * the peak folds 32, 16, 8, 4, 2, 1 with the tie rule, as vbs_patch_stats_f64 folds its peak.
+ * min_count < 3, det_min outside [0, 0.25), Q < 1 or above (VBS_PROJ_MAX_ROWS - 1) / 4, s < 1, R != 1 + 4 Q, n_values outside 1..3, a null proj, fit and peak both
+ * null: VBS_EINVAL, decided before the device is touched. */
+#define VBS_PROJ_SLOTS      4        /* slots of a 16-column tile: 4 x (x1, x2, x3, flag)                    */
+#define VBS_PROJ_CHUNK      64       /* frames staged at a time (no result depends on it)                    */
+#define VBS_PROJ_ROWS       64       /* basis rows a workgroup takes (no result depends on it)               */
+#define VBS_PROJ_WG_SLOTS   16       /* slots a workgroup takes (no result depends on it)                    */
+#define VBS_PROJ_MAX_ROWS   8192     /* R at most (Q = 2047 bins)                                            */
+#define VBS_PROJ_MAX_FRAMES 1048576  /* n at most                                                            */
+#define VBS_PROJ_MAX_SLOTS  1024     /* s at most (the cap of max_markers); the total series has s = 1       */
+#define VBS_FIT_GROUP       4        /* slots a workgroup of the fit takes, one wave each                    */
+#define VBS_PEAK_COLS       7        /* flag, N, mean, bin, a, b, p                                          */
+int vbs_project_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* basis, int R,
+                           double* proj, void* stream);
+int vbs_harmonic_fit_f64(int device, const double* proj, int s, int R, int n_values, int Q, int min_count, double det_min,
+                         double* fit, double* peak, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

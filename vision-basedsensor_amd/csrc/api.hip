@@ -1078,6 +1078,28 @@ extern "C" int vbs_patch_stats_f64(int device, const double* map, int F, int P, 
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- displacement spectra along a recording (k_spectrum.hip) --------------------------------------------------------------------
+extern "C" int vbs_project_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* basis,
+                                      int R, double* proj, void* stream) {
+    if (!rec || !basis || !proj || n < 1 || s < 1 || R < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
+        n_values >= cols)
+        return VBS_EINVAL;
+    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS || R > VBS_PROJ_MAX_ROWS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_project_series(rec, n, s, cols, n_values, basis, R, proj, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_harmonic_fit_f64(int device, const double* proj, int s, int R, int n_values, int Q, int min_count,
+                                    double det_min, double* fit, double* peak, void* stream) {
+    if (!proj || (!fit && !peak) || s < 1 || Q < 1 || Q > (VBS_PROJ_MAX_ROWS - 1) / 4 || R != 1 + 4 * Q || n_values < 1 ||
+        n_values > 3 || min_count < 3 || !(det_min >= 0.0 && det_min < 0.25))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_harmonic_fit(proj, s, R, n_values, Q, min_count, det_min, fit, peak, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- the probe-indentation validation (k_steps.hip) ---------------------------------------------------------------------------
 static bool record_shape_ok(int n, int s, int cols, int n_values) {
     return series_shape_ok(n, s, 0) && cols >= 2 && cols <= 8 && n_values >= 1 && n_values < cols;

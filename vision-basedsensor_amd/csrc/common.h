@@ -249,6 +249,12 @@ int launch_field_map(const double* rec, int s, int cols, int n_values, const dou
                      double min_coverage, int frame_begin, int frame_end, double* map, hipStream_t st);
 void launch_patch_stats(const double* map, int F, int P, int n_values, const double* grid_xy, int component, double sign, double thr,
                         double* patch, hipStream_t st);
+// k_spectrum.hip (f14): the projection of every series onto a caller's basis on the float64 matrix instruction, and the harmonic
+// fit and peak of those projections
+void launch_project_series(const double* rec, int n, int s, int cols, int n_values, const double* basis, int R, double* proj,
+                           hipStream_t st);
+void launch_harmonic_fit(const double* proj, int s, int R, int n_values, int Q, int min_count, double det_min, double* fit,
+                         double* peak, hipStream_t st);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

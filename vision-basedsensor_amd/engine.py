@@ -1007,6 +1007,94 @@ def patch_stats_f64(map, grid_xy, component=2, sign=1.0, threshold=0.0, device=N
     return out
 
 
+# ---- displacement spectra along a recording (k_spectrum.hip): the projection onto a basis, the harmonic fit ------------------------
+def _project_args(n, s, cols, basis_shape, n_values):
+    """`project_series_f64`'s argument checks (no device needed): -> (R, n_values) or ValueError."""
+    if n < 1 or s < 1 or not (2 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
+    bs = tuple(basis_shape)
+    if len(bs) != 2 or bs[0] < 1 or bs[1] != n:
+        raise ValueError(f"basis must be [R >= 1, {n}]: one value per basis row and frame of rec")
+    nv = min(cols - 1, 3) if n_values is None else int(n_values)
+    if not (1 <= nv <= 3 and nv < cols):
+        raise ValueError("n_values must be 1 .. 3 and below cols")
+    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS),
+                                 ("basis rows", bs[0], "VBS_PROJ_MAX_ROWS", L.PROJ_MAX_ROWS)):
+        if got > cap:
+            raise L.VbsError(f"vbs_project_series_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
+    return int(bs[0]), nv
+
+
+def project_series_f64(rec, basis, n_values=None, device=None):
+    """The gap-aware projection of every series onto a basis (`vbs_project_series_f64`), a float64 matrix product over the time
+    axis.  rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default
+    min(cols - 1, 3)).  basis float64 [R, n], finite (`spectra.harmonic_basis`).  Returns float64 [s, R, 1 + n_values] = den, num
+    per value: the sums of basis[r, f] and of basis[r, f] * x_v[f, i] over the valid frames of slot i."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    b = torch.as_tensor(basis, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    R, nv = _project_args(n, s, cols, b.shape, n_values)
+    out = torch.empty((s, R, 1 + nv), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_project_series_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(b), R, _ptr(out),
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_project_series_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_project_series_f64 failed ({rc})")
+    return out
+
+
+def _fit_args(s, R, oc, Q, min_count, det_min):
+    """`harmonic_fit_f64`'s argument checks (no device needed): -> (n_values, min_count, det_min) or ValueError."""
+    nv, Q, mc, dm = int(oc) - 1, int(Q), int(min_count), float(det_min)
+    if s < 1 or not (1 <= nv <= 3):
+        raise ValueError("proj must be [s >= 1, R, 2 .. 4]")
+    if Q < 1 or Q > (L.PROJ_MAX_ROWS - 1) // 4 or R != 1 + 4 * Q:
+        raise ValueError(f"proj has {R} basis rows: harmonic_fit_f64 needs 1 + 4 Q = {1 + 4 * Q} in the order of "
+                         f"spectra.harmonic_basis, 1 <= Q <= {(L.PROJ_MAX_ROWS - 1) // 4}")
+    if mc < 3:
+        raise ValueError("min_count must be >= 3 (a mean, a cosine and a sine)")
+    if not (0.0 <= dm < 0.25):
+        raise ValueError("det_min must lie in [0, 0.25)")
+    return nv, mc, dm
+
+
+def harmonic_fit_f64(proj, Q, min_count=8, det_min=1e-3, want_fit=True, want_peak=True, device=None):
+    """The floating-mean least-squares fit x ~ c0 + a cos + b sin at every frequency of a `spectra.harmonic_basis`
+    (`vbs_harmonic_fit_f64`).  proj float64 [s, 1 + 4 Q, 1 + n_values] as `project_series_f64` returns it for that basis.  A bin is
+    ok where the series has at least `min_count` valid frames and the determinant of its normal equations exceeds `det_min` N^2
+    (N^2 / 4 is what a whole number of periods without gaps gives).  Returns `(fit, peak)`: fit float64 [s, Q, 1 + 3 n_values] =
+    ok, then a, b and the power p (the drop in the sum of squares) per value, zeros where not ok; peak float64 [s, n_values, 7] =
+    flag (0 too few frames, 1 no ok bin, 2 a peak), N, mean, bin, a, b, p of the ok bin with the largest p (the first of equal
+    ones).  Amplitude and phase: `spectra.amplitude_phase(a, b)`.  `want_fit` / `want_peak` False: None in its place."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    p = torch.as_tensor(proj, dtype=torch.float64, device=dev).contiguous()
+    if p.dim() != 3:
+        raise ValueError("proj must be [s, 1 + 4 Q, 1 + n_values]")
+    if not (want_fit or want_peak):
+        raise ValueError("at least one of fit and peak")
+    s, R, oc = p.shape
+    nv, mc, dm = _fit_args(s, R, oc, Q, min_count, det_min)
+    fit = torch.empty((s, int(Q), 1 + 3 * nv), dtype=torch.float64, device=dev) if want_fit else None
+    peak = torch.empty((s, nv, L.PEAK_COLS), dtype=torch.float64, device=dev) if want_peak else None
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_harmonic_fit_f64(dev.index, _ptr(p), s, R, nv, int(Q), mc, dm, _ptr(fit), _ptr(peak),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_harmonic_fit_f64: bad argument (R == 1 + 4 Q, min_count >= 3, det_min in [0, 0.25))")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_harmonic_fit_f64 failed ({rc})")
+    return fit, peak
+
+
 # ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
 def _steps_call(name, what, fn):
     rc = fn()

@@ -423,6 +423,145 @@ def to_contact_frame(patch, cell_area, grid_xy, patch_filtered=None, frame_offse
     return df
 
 
+# ---- displacement spectra along a recording (k_spectrum.hip): fit, peak and phase of every marker in a band -------------------------
+_SPECTRUM_AXES = ("x", "y", "z")
+SPECTRUM_FRAME_COLUMNS = ("marker_id", "axis", "freq", "amplitude", "phase_deg", "power", "explained", "count")
+SPECTRUM_COLS = 6              # freq, amplitude, phase_deg, power, explained, count of `spectral_analysis`'s `marker` and `total`
+
+
+def _spectrum_args(n, m, freqs, ref_frame, slot_mask, min_count, det_min, axis="z"):
+    """`spectral_analysis`'s argument checks (no device needed): -> (freqs [Q], min_count, slot indices or None, axis index)."""
+    from . import spectra
+    nu = spectra._freqs(freqs)
+    if 1 + 4 * nu.size > L.PROJ_MAX_ROWS:
+        raise ValueError(f"{nu.size} frequencies need {1 + 4 * nu.size} basis rows, above VBS_PROJ_MAX_ROWS = {L.PROJ_MAX_ROWS}")
+    if n > L.PROJ_MAX_FRAMES or m > L.PROJ_MAX_SLOTS:
+        raise ValueError(f"the table's {n} frames x {m} slots exceed VBS_PROJ_MAX_FRAMES = {L.PROJ_MAX_FRAMES} or "
+                         f"VBS_PROJ_MAX_SLOTS = {L.PROJ_MAX_SLOTS}")
+    if not (0 <= int(ref_frame) < n):
+        raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+    mc = max(8, n // 4) if min_count is None else int(min_count)
+    if mc < 3:
+        raise ValueError("min_count must be >= 3")
+    if not (0.0 <= float(det_min) < 0.25):
+        raise ValueError("det_min must lie in [0, 0.25)")
+    if axis not in _SPECTRUM_AXES:
+        raise ValueError(f"axis must be one of {_SPECTRUM_AXES}")
+    slots = None
+    if slot_mask is not None:
+        k = np.asarray(slot_mask)
+        if k.shape != (m,):
+            raise ValueError(f"slot_mask must be [{m}]: nonzero = the slot takes part")
+        slots = np.nonzero(k)[0]
+    return nu, mc, slots, _SPECTRUM_AXES.index(axis)
+
+
+def _peak_rows(peak, M2, nu):
+    """peak [s, 3, 7] and M2 [s, 3] (host) -> [s, 3, SPECTRUM_COLS] = freq, amplitude, phase_deg, power, explained, count; the
+    first five are NaN where the series has no peak (flag != 2)."""
+    from . import spectra
+    has = peak[..., 0] == 2.0
+    amp, ph = spectra.amplitude_phase(peak[..., 4], peak[..., 5])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        expl = peak[..., 6] / M2
+    nan = lambda v: np.where(has, v, np.nan)                                                      # noqa: E731
+    return np.stack([nan(nu[np.where(has, peak[..., 3], 0).astype(np.int64)]), nan(amp), nan(ph), nan(peak[..., 6]), nan(expl),
+                     peak[..., 1]], axis=-1)
+
+
+def spectral_analysis(eng: Engine, table: torch.Tensor, freqs, ref_frame=0, taps=None, slot_mask=None, min_count=None, det_min=1e-3,
+                      fps=None, axis="z"):
+    """How the displacement oscillates (the reference's Figure 11(b) shows the oscillation and ships no code for
+    it) from a table [N, M, 10]: the displacement of every slot against `ref_frame` (`Engine.axis_displacement`; `slot_mask` [M],
+    nonzero = the slot takes part) - with `taps` (a full odd-length symmetric FIR) its FIR residual over the entries that have a
+    trend (flag 3), so that the trend does not leak into the low bins - projected onto `spectra.harmonic_basis(N, freqs)`
+    (`project_series_f64`) and fitted at every frequency (`harmonic_fit_f64`; `min_count` default max(8, N // 4)), and the same
+    pair for the per-frame `total` over its complete frames, a record of one series.  `freqs`: cycles per frame, each in
+    (0, 0.25] (`spectra.zoom_grid`).  Returns a dict.  Device tensors (float64): `series` [N, M, 4] and `total_series` [N, 1, 4]
+    (what was projected), `proj`, `fit` [M, Q, 10], `peak` [M, 3, 7], `total_fit` [1, Q, 10], `total_peak` [1, 3, 7].  Host arrays:
+    `freqs` [Q]; `marker` [M, 3, 6] and `total` [3, 6] = per series and axis the peak's freq, amplitude, phase_deg
+    (x ~ A cos(theta - phi)), power (the drop in the sum of squares), explained (power / the series' sum of squared deviations,
+    from `series_stats_f64`) and count, the first five NaN where there is no peak; the COMMON LINE of `axis`: `common_power` [Q] =
+    the sum over the slots, ascending, of the power of every ok bin, `common_bin` its largest (the smallest of equal ones, -1
+    without an ok bin), `common_freq`; and the PHASE MAP `phase_map` [M, 3] = ok, amplitude, phase_deg of every slot at that bin.
+    With `fps`: `freqs_hz`, `common_freq_hz`."""
+    from . import spectra
+    from .engine import fir_series_f64, harmonic_fit_f64, project_series_f64, series_stats_f64
+    n, m = int(table.shape[0]), int(table.shape[1])
+    nu, mc, slots, ax = _spectrum_args(n, m, freqs, ref_frame, slot_mask, min_count, det_min, axis)
+    dev = eng.device.index
+    ax_rec, tot = eng.axis_displacement(table, ref_frame, slots)
+
+    def series_of(rec):
+        if taps is None:
+            return rec[..., :4].contiguous()
+        f = fir_series_f64(rec, taps, 3, device=dev)
+        return torch.cat([(f[..., :1] == 3.0).to(torch.float64), f[..., 4:7]], dim=2)
+    Q = int(nu.size)
+    basis = torch.from_numpy(spectra.harmonic_basis(n, nu)).to(eng.device)
+    out = {"freqs": nu}
+    for name, rec in (("", ax_rec), ("total_", tot[:, None, :])):
+        series = series_of(rec)
+        proj = project_series_f64(series, basis, 3, device=dev)
+        fit, peak = harmonic_fit_f64(proj, Q, mc, det_min, device=dev)
+        k = series.shape[1]
+        packed = torch.zeros((n, k, L.DISP_COLS), dtype=torch.float64, device=eng.device)     # the layout series_stats_f64 reads
+        packed[..., 0] = (series[..., 0] != 0).to(torch.float64)
+        M2 = np.empty((k, 3))
+        for a in range(3):
+            packed[..., 4] = series[..., 1 + a]
+            st = series_stats_f64(packed, device=dev).cpu().numpy()
+            M2[:, a] = st[:, 2] * st[:, 2] * (st[:, 0] - 1.0)
+        out.update({name + "series": series, name + "proj": proj, name + "fit": fit, name + "peak": peak})
+        rows = _peak_rows(peak.cpu().numpy(), M2, nu)
+        out["marker" if not name else "total"] = rows if not name else rows[0]
+    fh = out["fit"].cpu().numpy()
+    ok, a, b, p = fh[..., 0] != 0, fh[..., 1 + 3 * ax], fh[..., 2 + 3 * ax], fh[..., 3 + 3 * ax]
+    common = np.zeros(Q)
+    for i in range(m):                                                   # ascending slots; a bin that is not ok, or a NaN, adds nothing
+        common = common + np.where(ok[i] & ~np.isnan(p[i]), p[i], 0.0)
+    cb = int(np.argmax(common)) if ok.any() else -1                     # (argmax: the smallest of equal ones)
+    out.update({"common_power": common, "common_bin": cb, "common_freq": float(nu[cb]) if cb >= 0 else float("nan")})
+    pm = np.zeros((m, 3))
+    if cb >= 0:
+        amp, ph = spectra.amplitude_phase(a[:, cb], b[:, cb])
+        pm = np.stack([ok[:, cb].astype(np.float64), np.where(ok[:, cb], amp, 0.0), np.where(ok[:, cb], ph, 0.0)], axis=1)
+    out["phase_map"] = pm
+    if fps is not None:
+        out["freqs_hz"] = spectra.to_hz(nu, fps)
+        out["common_freq_hz"] = float(spectra.to_hz(out["common_freq"], fps))
+    return out
+
+
+def to_spectrum_frame(marker, ids=None, fps=None, path=None):
+    """The sheet of `spectral_analysis`: one row `SPECTRUM_FRAME_COLUMNS` per slot and axis (slot-major; axis "x", "y", "z") from
+    its `marker` [M, 3, 6]; `marker_id` = `ids.marker_ids` (slot number + 1 without `ids`); with `fps` also `freq_hz`.  freq ..
+    explained are NaN (empty cells) where the series has no peak.  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    mk = marker.detach().cpu().numpy() if isinstance(marker, torch.Tensor) else np.asarray(marker, dtype=np.float64)
+    if mk.ndim != 3 or mk.shape[1:] != (3, SPECTRUM_COLS):
+        raise ValueError(f"marker must be [M, 3, {SPECTRUM_COLS}]")
+    mid = _ids.marker_ids(ids) if ids is not None else np.arange(1, mk.shape[0] + 1, dtype=np.int64)
+    if len(mid) != mk.shape[0]:
+        raise ValueError(f"marker has {mk.shape[0]} slots, ids {len(mid)}")
+    flat = mk.reshape(-1, SPECTRUM_COLS)
+    cols = {"marker_id": np.repeat(np.asarray(mid), 3), "axis": np.tile(np.array(_SPECTRUM_AXES, dtype=object), mk.shape[0])}
+    for k, name in enumerate(SPECTRUM_FRAME_COLUMNS[2:7]):
+        cols[name] = flat[:, k].astype(np.float64)
+    cols["count"] = flat[:, 5].astype(np.int64)
+    if fps is not None:
+        from . import spectra
+        cols["freq_hz"] = spectra.to_hz(flat[:, 0], fps)
+    df = pd.DataFrame(cols)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- the probe-indentation validation (k_steps.hip): the reference's Figure 6(b) from a tracked table -------------------------
 @dataclass
 class IndentationResult:
