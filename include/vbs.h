@@ -834,6 +834,81 @@ int vbs_project_series_f64(int device, const double* rec, int n, int s, int cols
 int vbs_harmonic_fit_f64(int device, const double* proj, int s, int R, int n_values, int Q, int min_count, double det_min,
                          double* fit, double* peak, void* stream);
 
+/* ---- Shear, torsion and strain along a recording (the reference's Figure 4(c) stops at arrows; it ships no code for this) ----
+ * How a marker's displacement depends on where the marker sits: the affine part of the displacement field of every frame (drag,
+ * twist about the normal, dilation, shear, tilt of dZ), what is left once that smooth motion is removed, and the same fit over
+ * the neighbourhood of every marker.  Two entries without a handle, on the record layout of vbs_fir_series_f64.  The operator,
+ * the conditioning rule, the rejection and `worst` are this project's.
+ *
+ * vbs_motion_series_f64 - rec [dev] float64 [n, s, cols], 4 <= cols <= 8: col 0 the flag (nonzero = valid), cols 1 .. 3 dX, dY, dZ
+ * (vbs_axis_displacement's `axis` and vbs_pose_series's `deviation` are valid inputs as they are).  pos [dev] float64 [s, 2]: the
+ * rest position (x, y) of every slot.  slot_mask [dev] uint8 [s] as vbs_axis_displacement's (may be NULL = all).  A slot is USED
+ * in frame f when it is selected and its flag is nonzero.  Nothing else of a slot is ever read into a sum: invalid entries,
+ * columns >= 4 and the pos of unselected slots may hold NaN or 1e300.
+ * EVERY SUM FOLLOWS THE RULE OF vbs_axis_displacement, WHICH IS PART OF THE INTERFACE: lane l of 64 adds slots l, l + 64, ... in
+ * ascending order (selected, never multiplied by zero), the 64 lane sums are folded a[i] + a[i + 32], then + 16, 8, 4, 2, 1.
+ * Float64 without contraction, no atomics: no result depends on the launch shape, on the range or on VBS_MOTION_GROUP.
+ * The fit over the used slots, for k = X, Y, Z: the means mx, my of pos and md_k of d_k; on the centred values x = px - mx,
+ * y = py - my, e_k = d_k - md_k the sums xx, xy, yy, xe_k, ye_k, recomputed from rec (never from a rounded output);
+ * det = xx yy - xy xy; a fit exists iff count >= 3 and |det| > 1e-300 (the rule of vbs_pose_series);
+ *     g_kx = (xe_k yy - ye_k xy) / det     g_ky = (ye_k xx - xe_k xy) / det     t_k = md_k - g_kx mx - g_ky my
+ * (left to right: the model's displacement at the origin of pos, as c is in the pose).  The residual of a slot is
+ * r_k = e_k - (g_kx x + g_ky y), q = r_X r_X + r_Y r_Y + r_Z r_Z added left to right, SSR_k = the sum of r_k r_k by the rule and
+ * SSR = (SSR_X + SSR_Y) + SSR_Z.
+ * One round of outlier rejection, exactly as vbs_pose_series: only when reject_k > 0, a fit exists and SSR > 0, the used slots
+ * with q <= (reject_k reject_k) (SSR / count) are kept.  If fewer are kept than are used and the kept set gives a fit of its own
+ * (kept >= 3, |det| > 1e-300 of its own centred sums), everything is the kept set's, flag = 2 and n_used = kept; otherwise the
+ * first fit stands with flag = 1 and n_used = count.  flag = 0: no fit; everything else of the row is 0 (worst: -1) and
+ * n_used = count.
+ *   grad [dev] float64 [fe-fb, 3, 4] = (flag, t_k, g_kx, g_ky) for k = X, Y, Z: a FIR record as it is (s = 3, cols = 4,
+ *       n_values = 3)
+ *   strain [dev] float64 [fe-fb, VBS_STRAIN_COLS].  With F = I + the in-plane block, F11 = 1 + g_Xx, F12 = g_Xy, F21 = g_Yx,
+ *       F22 = 1 + g_Yy, and DEG = 57.29577951308232:
+ *        0 - 2   flag, count, n_used
+ *        3       dilation = g_Xx + g_Yy
+ *        4       omega = 0.5 (g_Yx - g_Xy), the linearised torsion in radians
+ *        5, 6    e1 = 0.5 (g_Xx - g_Yy), e2 = 0.5 (g_Xy + g_Yx)
+ *        7       max_shear = sqrt(e1 e1 + e2 e2)
+ *        8       shear_deg = 0.5 atan2(e2, e1) DEG
+ *        9       rot_deg = atan2(q_, p_) DEG, p_ = F11 + F22, q_ = F21 - F12: the rotation of the polar decomposition, any angle
+ *        10, 11  lambda1 = 0.5 (h + w), lambda2 = 0.5 (h - w), h = sqrt(p_ p_ + q_ q_), w = sqrt(a_ a_ + b_ b_), a_ = F11 - F22,
+ *                b_ = F12 + F21: the principal stretches
+ *        12      tilt_deg = atan(sqrt(g_Zx g_Zx + g_Zy g_Zy)) DEG
+ *        13, 14  rms_inplane = sqrt((SSR_X + SSR_Y) / n_used), rms_z = sqrt(SSR_Z / n_used)
+ *        15      worst = the slot with the largest q among the slots of the final fit (-1: no fit); the smallest index wins among
+ *                equals, a NaN never wins; it folds as vbs_patch_stats_f64's peak
+ *   residual [dev] float64 [fe-fb, s, 4] = (1 kept or 2 rejected, r_X, r_Y, r_Z) for every used slot against the FINAL fit's
+ *       means and gradient; zeros where the slot is not used or there is no fit.  Both flags are nonzero: a valid rec of
+ *       vbs_fir_series_f64, vbs_field_map_f64, vbs_project_series_f64 and the step entries (the non-affine part)
+ * Any of the three may be NULL (not all).  A null rec or pos, n or s < 1, cols outside 4 .. 8, reject_k negative or not finite, a
+ * range outside 0 <= fb <= fe <= n: VBS_EINVAL; s > VBS_FIELD_MAX_SLOTS: VBS_ECAPACITY; a bad argument comes before a capacity;
+ * all decided before the device is touched.  fb == fe emits nothing.  The call allocates nothing.
+ *
+ * vbs_local_strain_f64 - the same fit around every marker.  rec, pos as above (no mask).  nbr [dev] int32 [s, K],
+ * 1 <= K <= VBS_STRAIN_MAX_NBR, computed by the caller: an entry outside [0, s) reads as "no neighbour" and is never an address;
+ * duplicates are used as given.  The member list of slot i is i, nbr[i][0], .., nbr[i][K-1], in that order; a member is USED when
+ * it is in range and its flag in frame f is nonzero.  THE ORDER IS PART OF THE INTERFACE: one thread adds the used members in
+ * LIST order from 0.0, the means first, then the centred sums xx, xy, yy, xe_k, ye_k as above.  Slot i has a result iff i itself
+ * is used, cnt >= min_count (3 <= min_count <= K + 1) and det > det_rel (xx yy), 0 <= det_rel < 1: det / (xx yy) is 1 - rho^2, so
+ * det_rel refuses neighbourhoods close to a line without depending on the units.  Gradients by the formulas above.
+ *   out [dev] float64 [fe-fb, s, VBS_LSTRAIN_COLS] = (cnt, dilation, omega, max_shear, e1, e2, g_Zx, g_Zy), zeros where there is no
+ *       result.  cnt is nonzero: `out` with n_values = 3 is a valid rec of vbs_field_map_f64 (maps of local dilation, torsion and
+ *       shear), and vbs_patch_stats_f64 with component 2 gives the shear zone
+ * No atomics, no contraction: no result depends on the launch shape, on the range or on VBS_LSTRAIN_GROUP.  A null pointer, n or
+ * s < 1, cols outside 4 .. 8, K, min_count or det_rel outside the ranges above, a range outside 0 <= fb <= fe <= n: VBS_EINVAL;
+ * s > VBS_FIELD_MAX_SLOTS: VBS_ECAPACITY; decided before the device is touched.  fb == fe emits nothing. */
+#define VBS_STRAIN_COLS    16  /* flag, count, n_used, dilation, omega, e1, e2, max_shear, shear_deg, rot_deg, lambda1, lambda2,
+                                  tilt_deg, rms_inplane, rms_z, worst                                    */
+#define VBS_LSTRAIN_COLS   8   /* cnt, dilation, omega, max_shear, e1, e2, g_Zx, g_Zy                    */
+#define VBS_MOTION_GROUP   8   /* frames a workgroup takes, one wave each (no result depends on it)     */
+#define VBS_LSTRAIN_GROUP  8   /* frames a workgroup takes, one after another (no result depends on it) */
+#define VBS_STRAIN_MAX_NBR 12  /* K at most                                                             */
+int vbs_motion_series_f64(int device, const double* rec, int n, int s, int cols, const double* pos, const uint8_t* slot_mask,
+                          double reject_k, int frame_begin, int frame_end, double* grad, double* strain, double* residual,
+                          void* stream);
+int vbs_local_strain_f64(int device, const double* rec, int n, int s, int cols, const double* pos, const int32_t* nbr, int K,
+                         int min_count, double det_rel, int frame_begin, int frame_end, double* out, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

@@ -1100,6 +1100,38 @@ extern "C" int vbs_harmonic_fit_f64(int device, const double* proj, int s, int R
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- shear, torsion and strain along a recording (k_motion.hip) ------------------------------------------------------------------
+static bool motion_shape_ok(const double* rec, const double* pos, int n, int s, int cols, int frame_begin, int frame_end) {
+    return rec && pos && n >= 1 && s >= 1 && cols >= 4 && cols <= 8 && frame_begin >= 0 && frame_end <= n && frame_begin <= frame_end;
+}
+
+extern "C" int vbs_motion_series_f64(int device, const double* rec, int n, int s, int cols, const double* pos,
+                                     const uint8_t* slot_mask, double reject_k, int frame_begin, int frame_end, double* grad,
+                                     double* strain, double* residual, void* stream) {
+    if (!motion_shape_ok(rec, pos, n, s, cols, frame_begin, frame_end) || (!grad && !strain && !residual) ||
+        !std::isfinite(reject_k) || reject_k < 0.0)
+        return VBS_EINVAL;
+    if (s > VBS_FIELD_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_motion_series(rec, s, cols, pos, slot_mask, reject_k, frame_begin, frame_end, grad, strain, residual,
+                             (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_local_strain_f64(int device, const double* rec, int n, int s, int cols, const double* pos, const int32_t* nbr,
+                                    int K, int min_count, double det_rel, int frame_begin, int frame_end, double* out,
+                                    void* stream) {
+    if (!motion_shape_ok(rec, pos, n, s, cols, frame_begin, frame_end) || !nbr || !out || K < 1 || K > VBS_STRAIN_MAX_NBR ||
+        min_count < 3 || min_count > K + 1 || !(det_rel >= 0.0 && det_rel < 1.0))
+        return VBS_EINVAL;
+    if (s > VBS_FIELD_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_local_strain(rec, s, cols, pos, nbr, K, min_count, det_rel, frame_begin, frame_end, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- the probe-indentation validation (k_steps.hip) ---------------------------------------------------------------------------
 static bool record_shape_ok(int n, int s, int cols, int n_values) {
     return series_shape_ok(n, s, 0) && cols >= 2 && cols <= 8 && n_values >= 1 && n_values < cols;

@@ -255,6 +255,12 @@ void launch_project_series(const double* rec, int n, int s, int cols, int n_valu
                            hipStream_t st);
 void launch_harmonic_fit(const double* proj, int s, int R, int n_values, int Q, int min_count, double det_min, double* fit,
                          double* peak, hipStream_t st);
+// k_motion.hip (f15): the affine fit of every frame's displacement field with its invariants and residual, and the same fit over
+// the neighbourhood of every marker
+void launch_motion_series(const double* rec, int s, int cols, const double* pos, const u8* slot_mask, double reject_k,
+                          int frame_begin, int frame_end, double* grad, double* strain, double* residual, hipStream_t st);
+void launch_local_strain(const double* rec, int s, int cols, const double* pos, const int32_t* nbr, int K, int min_count,
+                         double det_rel, int frame_begin, int frame_end, double* out, hipStream_t st);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

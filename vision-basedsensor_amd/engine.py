@@ -1095,6 +1095,120 @@ def harmonic_fit_f64(proj, Q, min_count=8, det_min=1e-3, want_fit=True, want_pea
     return fit, peak
 
 
+# ---- shear, torsion and strain along a recording (k_motion.hip): the global affine fit, the fit around every marker -----------------
+_MOTION_WANT = ("grad", "strain", "residual")
+
+
+def _motion_shape(n, s, cols, pos_shape, frame_range):
+    if n < 1 or s < 1 or not (4 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 4 <= cols <= 8]: flag, dX, dY, dZ")
+    if tuple(pos_shape) != (s, 2):
+        raise ValueError(f"pos must be [{s}, 2]: the rest position of every slot of rec")
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    return a, b
+
+
+def _motion_args(n, s, cols, pos_shape, slots, reject_k, frame_range, want):
+    """`motion_series_f64`'s argument checks (no device needed): -> (a, b, want as a tuple) or ValueError / VbsError."""
+    a, b = _motion_shape(n, s, cols, pos_shape, frame_range)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _MOTION_WANT for w in want):
+        raise ValueError(f"want must name at least one of {_MOTION_WANT}")
+    if not (np.isfinite(float(reject_k)) and float(reject_k) >= 0.0):
+        raise ValueError(f"reject_k {reject_k} must be finite and >= 0 (0 = no rejection)")
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= s):
+            raise ValueError(f"slots outside the record's {s} slots")
+    if s > L.FIELD_MAX_SLOTS:
+        raise L.VbsError(f"vbs_motion_series_f64: {s} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
+    return a, b, want
+
+
+def motion_series_f64(rec, pos, slots=None, reject_k=0.0, frame_range=None, want=_MOTION_WANT, device=None):
+    """The affine fit of the displacement field of every frame (`vbs_motion_series_f64`): d_k ~ t_k + g_kx x + g_ky y over the
+    used slots, its invariants and what it leaves.  rec float64 [n, s, cols >= 4] (host or device): col 0 the flag (nonzero =
+    valid), cols 1 .. 3 dX, dY, dZ (`Engine.axis_displacement`'s `axis` as it is); pos float64 [s, 2] the rest positions; `slots`
+    selects markers as `axis_displacement` does; `reject_k > 0`: one round of rejection at reject_k times the rms residual.
+    Returns a dict of float64 device tensors for the frames [a, b) of `frame_range`, with the keys of `want`: `grad` [b-a, 3, 4] =
+    flag (0 no fit, 1, 2 = refitted), t_k, g_kx, g_ky for k = X, Y, Z (a FIR record); `strain` [b-a, 16] = flag, count, n_used,
+    dilation, omega, e1, e2, max_shear, shear_deg, rot_deg, lambda1, lambda2, tilt_deg, rms_inplane, rms_z, worst; `residual`
+    [b-a, s, 4] = (1 kept | 2 rejected, r_X, r_Y, r_Z), zeros where not used: a record for every other series entry."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    p = torch.as_tensor(pos, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    a, b, want = _motion_args(n, s, cols, p.shape, slots, reject_k, frame_range, want)
+    mask = None
+    if slots is not None:
+        mask = torch.zeros((s,), dtype=torch.uint8, device=dev)
+        mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=dev)] = 1
+    shapes = {"grad": (b - a, 3, 4), "strain": (b - a, L.STRAIN_COLS), "residual": (b - a, s, 4)}
+    out = {w: torch.empty(shapes[w], dtype=torch.float64, device=dev) for w in want}
+    if a == b:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_motion_series_f64(dev.index, _ptr(r), n, s, cols, _ptr(p), _ptr(mask), float(reject_k), a, b,
+                                           _ptr(out.get("grad")), _ptr(out.get("strain")), _ptr(out.get("residual")),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_motion_series_f64: bad argument (4 <= cols <= 8, reject_k finite and >= 0, at least one output)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_motion_series_f64 failed ({rc})")
+    return out
+
+
+def _lstrain_args(n, s, cols, pos_shape, nbr_shape, min_count, det_rel, frame_range):
+    """`local_strain_f64`'s argument checks (no device needed): -> (a, b, K) or ValueError / VbsError."""
+    a, b = _motion_shape(n, s, cols, pos_shape, frame_range)
+    ns = tuple(nbr_shape)
+    if len(ns) != 2 or ns[0] != s or not (1 <= ns[1] <= L.STRAIN_MAX_NBR):
+        raise ValueError(f"nbr must be [{s}, 1 <= K <= {L.STRAIN_MAX_NBR}] (`strain.neighbour_lists`)")
+    K = int(ns[1])
+    if not (3 <= int(min_count) <= K + 1):
+        raise ValueError(f"min_count must lie in 3 .. K + 1 = {K + 1}")
+    if not (0.0 <= float(det_rel) < 1.0):
+        raise ValueError("det_rel must lie in [0, 1)")
+    if s > L.FIELD_MAX_SLOTS:
+        raise L.VbsError(f"vbs_local_strain_f64: {s} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
+    return a, b, K
+
+
+def local_strain_f64(rec, pos, nbr, min_count=4, det_rel=0.01, frame_range=None, device=None):
+    """The affine fit around every marker (`vbs_local_strain_f64`).  rec, pos as `motion_series_f64`; nbr int32 [s, K] from
+    `strain.neighbour_lists` (an entry outside [0, s) = no neighbour).  Slot i has a result in a frame where it is valid itself,
+    at least `min_count` of i and its neighbours are, and these do not lie close to a line (1 - rho^2 > det_rel).  Returns float64
+    [b-a, s, 8] = cnt, dilation, omega, max_shear, e1, e2, g_Zx, g_Zy (zeros where there is no result): with n_values = 3 a
+    record `field_map_f64` turns into maps of local dilation, torsion and shear."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    p = torch.as_tensor(pos, dtype=torch.float64, device=dev).contiguous()
+    nb = torch.as_tensor(nbr, device=dev).to(torch.int32).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    a, b, K = _lstrain_args(n, s, cols, p.shape, nb.shape, min_count, det_rel, frame_range)
+    out = torch.empty((b - a, s, L.LSTRAIN_COLS), dtype=torch.float64, device=dev)
+    if a == b:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_local_strain_f64(dev.index, _ptr(r), n, s, cols, _ptr(p), _ptr(nb), K, int(min_count), float(det_rel), a, b,
+                                          _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_local_strain_f64: bad argument (4 <= cols <= 8, 1 <= K <= 12, 3 <= min_count <= K + 1, 0 <= det_rel < 1)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_local_strain_f64 failed ({rc})")
+    return out
+
+
 # ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
 def _steps_call(name, what, fn):
     rc = fn()

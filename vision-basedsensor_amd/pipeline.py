@@ -302,6 +302,89 @@ def to_pose_frame(field, pose, pose_filtered=None, frame_offset=0, path=None):
     return df
 
 
+# ---- shear, torsion and strain along a recording (k_motion.hip): the affine part of the field, globally and around every marker ----
+def motion_analysis(eng: Engine, table: torch.Tensor, ref_frame=0, slots=None, reject_k=0.0, neighbours=6, radius=None, min_count=4,
+                    det_rel=0.01, taps=None, min_coverage=0.5):
+    """The decomposition of the displacement field of every frame of a table [N, M, 10]: drag, twist about the
+    normal, dilation and shear, what is left once that smooth motion is removed, and the same around every marker.  The rest
+    positions are the X, Y of frame `ref_frame`; of the selected slots (`slots`, as `Engine.axis_displacement`) those without a
+    3-D point there are masked out.  Returns a dict of device tensors (float64 unless said): `axis` [N, M, 4], `total` [N, 5]
+    (`Engine.axis_displacement`); `pos` [M, 2] (zeros where masked out) and `nbr` int32 [M, neighbours]
+    (`strain.neighbour_lists` within `radius`); `grad` [N, 3, 4], `strain` [N, 16], `residual` [N, M, 4]
+    (`engine.motion_series_f64` with `reject_k`); `local` [N, M, 8] (`engine.local_strain_f64` with `min_count`, `det_rel`); and
+    with `taps` (a full odd-length symmetric FIR, `filters.lowpass_taps`): `grad_filtered` [N, 3, 7] = flag, trend and residual
+    of t_k, g_kx, g_ky over the frames that have a fit (`fir_series_f64`), and `trend` [N, 11] = flag (1 where the frame has a
+    trend), then `strain.invariants` OF THE FILTERED gradient - angles and roots are never filtered themselves.
+    The call SYNCHRONISES its stream twice: the reference frame's row is copied to the host for `pos` and the neighbour lists, and
+    with `taps` the filtered gradient is, for the trend (NumPy).  It is an analysis off the timed path, as `misalignment_analysis`."""
+    from .engine import fir_series_f64, local_strain_f64, motion_series_f64
+    from .strain import invariants, neighbour_lists
+    axis, total = eng.axis_displacement(table, ref_frame, slots)
+    m = int(axis.shape[1])
+    row = table[int(ref_frame)].detach().to(torch.float64).cpu().numpy()
+    valid = (row[:, 0].astype(np.int64) & L.FLAG_XYZ) != 0
+    if slots is not None:
+        chosen = np.zeros(m, dtype=bool)
+        chosen[np.asarray(slots, dtype=np.int64).reshape(-1)] = True
+        valid &= chosen
+    pos = np.where(valid[:, None], row[:, 6:8], 0.0)
+    nbr = neighbour_lists(pos, neighbours, radius, valid)
+    dev = eng.device.index
+    pos_d = torch.as_tensor(pos, dtype=torch.float64, device=eng.device)
+    nbr_d = torch.as_tensor(nbr, dtype=torch.int32, device=eng.device)
+    out = {"axis": axis, "total": total, "pos": pos_d, "nbr": nbr_d}
+    out.update(motion_series_f64(axis, pos_d, np.flatnonzero(valid), reject_k, device=dev))
+    out["local"] = local_strain_f64(axis, pos_d, nbr_d, min_count, det_rel, device=dev)
+    if taps is not None:
+        gf = fir_series_f64(out["grad"], taps, 3, min_coverage, device=dev)
+        g = gf[..., :4].detach().cpu().numpy().copy()
+        ok = (g[..., 0] == 3.0).all(axis=1)
+        g[..., 0] = ok[:, None]
+        out["grad_filtered"] = gf
+        out["trend"] = torch.as_tensor(np.concatenate([ok[:, None].astype(np.float64), invariants(g)], axis=1), device=eng.device)
+    return out
+
+
+MOTION_FRAME_COLUMNS = ("frameno", "flag", "count", "n_used", "tX", "tY", "tZ", "gXx", "gXy", "gYx", "gYy", "gZx", "gZy", "dilation",
+                        "omega", "e1", "e2", "max_shear", "shear_deg", "rot_deg", "lambda1", "lambda2", "tilt_deg", "rms_inplane",
+                        "rms_z", "worst")
+MOTION_TREND_COLUMNS = ("dilation_f", "omega_f", "e1_f", "e2_f", "max_shear_f", "shear_deg_f", "rot_deg_f", "lambda1_f", "lambda2_f",
+                        "tilt_deg_f")
+
+
+def to_motion_frame(strain, grad, trend=None, frame_offset=0, path=None):
+    """The sheet of `motion_analysis`: one row per frame with `MOTION_FRAME_COLUMNS` from `strain` [N, 16] and `grad` [N, 3, 4], and
+    with `trend` [N, 11] also `MOTION_TREND_COLUMNS`.  tX .. rms_z are NaN (empty cells) where the frame has no fit (flag 0; worst
+    is -1 there), the trend columns where it has no trend.  `path`: also written as .xlsx (`xlsx_io.dataframe_to_xlsx`)."""
+    import pandas as pd
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    st, gr = host(strain), host(grad)
+    if st.ndim != 2 or st.shape[1] != L.STRAIN_COLS or gr.shape != (st.shape[0], 3, 4):
+        raise ValueError(f"strain must be [N, {L.STRAIN_COLS}] and grad [N, 3, 4]")
+    fit = (st[:, 0] != 0)[:, None]
+    cols = {"frameno": np.arange(st.shape[0], dtype=np.int64) + int(frame_offset), "flag": st[:, 0].astype(np.int64),
+            "count": st[:, 1].astype(np.int64), "n_used": st[:, 2].astype(np.int64)}
+    g = np.where(fit, np.concatenate([gr[:, :, 1], gr[:, :, 2:4].reshape(-1, 6)], axis=1), np.nan)
+    for k, name in enumerate(MOTION_FRAME_COLUMNS[4:13]):
+        cols[name] = g[:, k]
+    v = np.where(fit, st[:, 3:15], np.nan)
+    for k, name in enumerate(MOTION_FRAME_COLUMNS[13:25]):
+        cols[name] = v[:, k]
+    cols["worst"] = st[:, 15].astype(np.int64)
+    if trend is not None:
+        tr = host(trend)
+        if tr.shape != (st.shape[0], 11):
+            raise ValueError("trend must be [N, 11]")
+        t = np.where((tr[:, 0] != 0)[:, None], tr[:, 1:], np.nan)
+        for k, name in enumerate(MOTION_TREND_COLUMNS):
+            cols[name] = t[:, k]
+    df = pd.DataFrame(cols)
+    if path is not None:
+        from .xlsx_io import dataframe_to_xlsx
+        dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- contact maps along a recording (k_field.hip): field on a grid, contact patch, centre, with their trend ----------------------
 _CONTACT_COMPONENT = {"x": 0, "y": 1, "z": 2, "xyz": -1}
 CONTACT_FRAME_COLUMNS = ("frameno", "flag", "covered", "count", "area_mm2", "sum", "cx", "cy", "peak", "peak_x", "peak_y")
