@@ -909,6 +909,45 @@ int vbs_motion_series_f64(int device, const double* rec, int n, int s, int cols,
 int vbs_local_strain_f64(int device, const double* rec, int n, int s, int cols, const double* pos, const int32_t* nbr, int K,
                          int min_count, double det_rel, int frame_begin, int frame_end, double* out, void* stream);
 
+/* ---- Despiking a tracked series (the reference has no temporal outlier handling; the operator and its rules are this project's) ----
+ * The tracker takes the nearest detection within min_dist for every reference marker: a neighbour taken in a dropout, a merged
+ * blob or a bad ellipse puts an isolated jump into one marker's series.  Every analysis above is gap-aware, so a spike only has to
+ * become a gap; this entry finds it along time: a gap-aware rolling median with the median absolute deviation (the Hampel
+ * identifier).  An order statistic has no order of summation: THE DEFINITIONS BELOW ARE THE INTERFACE, the algorithm is not.
+ *
+ * vbs_hampel_series_f64 - no handle.  rec [dev] float64 [n, s, cols], time-major, the record layout vbs_fir_series_f64 takes: col 0
+ * the flag (nonzero = valid), cols 1 .. n_values the values, 1 <= n_values < cols <= 8.  Invalid entries and the columns past the
+ * values may hold NaN or anything else: they are selected out and never enter a comparison.  A VALID value must not be NaN; one
+ * that is gives unspecified results in the windows that hold it, in those only, and no fault.
+ * For frame f of [frame_begin, frame_end), series i and h = half_window (0 <= h <= VBS_ROBUST_MAX_HALF):
+ *   window   the valid frames g of [f-h, f+h] within [0, n), f itself included when it is valid; c = its population
+ *   judged   c >= min_count (1 <= min_count <= 2h + 1), whether or not f itself is valid
+ *   order    for a value column v the candidates are ordered by (x, g): a before b when x_a < x_b, or x_a == x_b and a < b (so
+ *            -0.0 and +0.0 tie and the earlier frame comes first); sorted as q_0 .. q_{c-1},
+ *              med_v = q_{(c-1)/2}                      for odd c
+ *              med_v = 0.5 q_{c/2-1} + 0.5 q_{c/2}      for even c: two products and one add, no contraction
+ *   mad_v    the same statistic of d_g = |x_g - med_v| over the same window
+ *   spike    thr = k_sigma * 1.4826, one IEEE product on the host.  Where f is valid and judged: dev_v = |x_{f,v} - med_v|,
+ *            spike_v = dev_v > thr * mad_v && dev_v > min_scale; the entry is a spike when any v is.  min_scale is an absolute
+ *            floor in the units of the data: a series quantised to a constant has mad = 0, and without the floor every sample
+ *            off the median would be a spike
+ * out [dev] float64 [fe-fb, s, 2 + 2 n_values] = flag, c, med[n_values], mad[n_values]; flag = valid + 2 judged + 4 spike (0, 1, 2,
+ * 3 or 7); med and mad are 0 where the entry is not judged.  Flag 2: the marker is missing in the frame, and the median of its
+ * neighbours is the value to fill the gap with.
+ * clean [dev] float64 [fe-fb, s, cols] (may be NULL): the rows of rec copied BIT FOR BIT (NaN payloads of invalid cells included)
+ * with col 0 set to 0.0 where the entry is a spike: a record vbs_fir_series_f64, vbs_field_map_f64, vbs_project_series_f64, the
+ * step entries and vbs_motion_series_f64 take as it is.
+ * An output depends on its window only: not on the tile (VBS_ROBUST_TILE frames x 64 series a workgroup, stated for tests of its
+ * edges), the range, s or what else is in the batch.  No atomics.  A null rec or out, n or s < 1, bad cols / n_values, half_window
+ * outside [0, VBS_ROBUST_MAX_HALF], min_count outside [1, 2h + 1], k_sigma not finite or <= 0, min_scale not finite or < 0, a range
+ * outside 0 <= fb <= fe <= n: VBS_EINVAL, decided before the device is touched.  fb == fe emits nothing.  The call allocates
+ * nothing. */
+#define VBS_ROBUST_MAX_HALF 31   /* window 2h + 1 <= 63 */
+#define VBS_ROBUST_TILE     64   /* frames a workgroup emits (no result depends on it) */
+int vbs_hampel_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, int half_window, int min_count,
+                          double k_sigma, double min_scale, int frame_begin, int frame_end, double* out, double* clean,
+                          void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

@@ -1030,6 +1030,22 @@ extern "C" int vbs_fir_series_f64(int device, const double* rec, int n, int s, i
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- despiking a tracked series (k_robust.hip) ----------------------------------------------------------------------------------
+extern "C" int vbs_hampel_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, int half_window,
+                                     int min_count, double k_sigma, double min_scale, int frame_begin, int frame_end, double* out,
+                                     double* clean, void* stream) {
+    if (!rec || !out || !series_shape_ok(n, s, 0) || cols < 2 || cols > 8 || n_values < 1 || n_values >= cols || half_window < 0 ||
+        half_window > VBS_ROBUST_MAX_HALF || min_count < 1 || min_count > 2 * half_window + 1 || !std::isfinite(k_sigma) ||
+        !(k_sigma > 0.0) || !std::isfinite(min_scale) || !(min_scale >= 0.0) || frame_begin < 0 || frame_end > n ||
+        frame_begin > frame_end)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_hampel_series(rec, n, s, cols, n_values, half_window, min_count, k_sigma * 1.4826, min_scale, frame_begin, frame_end,
+                             out, clean, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- pose misalignment along a recording (k_pose.hip) ---------------------------------------------------------------------------
 extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
                                const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k,

@@ -261,6 +261,9 @@ void launch_motion_series(const double* rec, int s, int cols, const double* pos,
                           int frame_begin, int frame_end, double* grad, double* strain, double* residual, hipStream_t st);
 void launch_local_strain(const double* rec, int s, int cols, const double* pos, const int32_t* nbr, int K, int min_count,
                          double det_rel, int frame_begin, int frame_end, double* out, hipStream_t st);
+// k_robust.hip (f16): gap-aware rolling median and MAD along time, the Hampel rule, the record with its spikes turned into gaps
+void launch_hampel_series(const double* rec, int n, int s, int cols, int n_values, int half_window, int min_count, double thr,
+                          double min_scale, int frame_begin, int frame_end, double* out, double* clean, hipStream_t st);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

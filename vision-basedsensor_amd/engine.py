@@ -893,6 +893,64 @@ def fir_series_f64(rec, taps, n_values=None, min_coverage=0.5, frame_range=None,
     return out
 
 
+# ---- despiking a tracked series (k_robust.hip): rolling median, MAD, the Hampel rule ---------------------------------------------
+def _robust_args(n, s, cols, half_window, k_sigma, min_scale, min_count, n_values, frame_range):
+    """`hampel_series_f64`'s argument checks (no device needed): -> (a, b, n_values, h, min_count) or ValueError."""
+    if n < 1 or s < 1 or not (2 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
+    nv = cols - 1 if n_values is None else int(n_values)
+    if not (1 <= nv < cols):
+        raise ValueError("n_values must be >= 1 and below cols")
+    h = int(half_window)
+    if h != half_window or not (0 <= h <= L.ROBUST_MAX_HALF):
+        raise ValueError(f"half_window must be an integer in [0, {L.ROBUST_MAX_HALF}] (VBS_ROBUST_MAX_HALF)")
+    mc = h + 1 if min_count is None else int(min_count)
+    if (min_count is not None and mc != min_count) or not (1 <= mc <= 2 * h + 1):
+        raise ValueError(f"min_count must be an integer in [1, 2 half_window + 1 = {2 * h + 1}]")
+    if not (np.isfinite(float(k_sigma)) and float(k_sigma) > 0.0):
+        raise ValueError(f"k_sigma {k_sigma} must be finite and > 0")
+    if not (np.isfinite(float(min_scale)) and float(min_scale) >= 0.0):
+        raise ValueError(f"min_scale {min_scale} must be finite and >= 0")
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    return a, b, nv, h, mc
+
+
+def hampel_series_f64(rec, half_window, k_sigma=3.0, min_scale=0.0, min_count=None, n_values=None, frame_range=None,
+                      want_clean=True, device=None):
+    """A gap-aware rolling median and median absolute deviation along time with the Hampel rule (`vbs_hampel_series_f64`).  rec
+    float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default cols - 1).  The
+    window of frame f is the valid frames of [f - h, f + h], h = `half_window` <= VBS_ROBUST_MAX_HALF; an entry is judged when the
+    window holds at least `min_count` (default h + 1) of them, and a valid judged entry is a spike when for any value
+    |x - med| > k_sigma * 1.4826 * mad and > `min_scale` (an absolute floor in the units of the data).  Returns (out, clean) for
+    the frames [a, b) of `frame_range` (default all): out float64 [b-a, s, 2 + 2 n_values] = flag (valid + 2 judged + 4 spike),
+    the population of the window, med, mad - flag 2 is a missing entry whose median is the value to fill the gap with; clean
+    float64 [b-a, s, cols] = those rows of rec bit for bit with the flag of every spike set to 0 (None when `want_clean` is
+    false).  An output does not depend on the range it was asked in."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    a, b, nv, h, mc = _robust_args(n, s, cols, half_window, k_sigma, min_scale, min_count, n_values, frame_range)
+    out = torch.empty((b - a, s, 2 + 2 * nv), dtype=torch.float64, device=dev)
+    clean = torch.empty((b - a, s, cols), dtype=torch.float64, device=dev) if want_clean else None
+    if a == b:
+        return out, clean
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_hampel_series_f64(dev.index, _ptr(r), n, s, cols, nv, h, mc, float(k_sigma), float(min_scale), a, b,
+                                           _ptr(out), _ptr(clean), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError(f"vbs_hampel_series_f64: bad argument (half_window in [0, {L.ROBUST_MAX_HALF}], min_count in "
+                         f"[1, 2 half_window + 1], k_sigma finite and > 0, min_scale finite and >= 0, 1 <= n_values < cols <= 8)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_hampel_series_f64 failed ({rc})")
+    return out, clean
+
+
 # ---- contact maps along a recording (k_field.hip): the smoother in space, the contact patch ------------------------------------
 def _field_args(n, s, cols, P, w_shape, wsum_shape, min_coverage, n_values, frame_range):
     """`field_map_f64`'s argument checks (no device needed): -> (a, b, n_values) or ValueError."""

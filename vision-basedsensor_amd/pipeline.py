@@ -232,6 +232,84 @@ def to_total_frame(total, total_filtered, frame_offset=0, path=None):
     return df
 
 
+# ---- despiking a tracked table (k_robust.hip): the Hampel rule along time, spikes turned into gaps ----------------------------------
+_SPIKE_SOURCES = {"xyz": (L.FLAG_XYZ, L.FLAG_XYZ, (6, 7, 8), ("Xw", "Yw", "Zw")),
+                  "pixel": (L.FLAG_TRACKED, L.FLAG_TRACKED | L.FLAG_XYZ, (1, 2), ("Cx", "Cy"))}
+
+
+def despike_table(eng: Engine, table: torch.Tensor, half_window=7, k_sigma=3.0, *, min_scale, source="xyz", slots=None):
+    """The rows of a table [N, M, 10] that are isolated jumps of one marker's series along time - a neighbour taken during a
+    dropout, a merged blob, a bad ellipse - found by `engine.hampel_series_f64` and turned into gaps, which every
+    `*_analysis` of this module handles.  `source` "xyz": the rows with VBS_FLAG_XYZ, values X, Y, Z (cols 6-8); "pixel": the rows
+    with VBS_FLAG_TRACKED, values Cx, Cy.  A row is a spike when ANY of its values is.  `min_scale` (required: millimetres and
+    pixels share no default) is the absolute floor below which a deviation is never a spike; `slots` (indices) restricts the
+    test to those markers.  Returns (clean_table, report): clean_table is a copy of the table in which the spike rows have
+    VBS_FLAG_XYZ cleared ("xyz") or both flag bits ("pixel": the 3-D row derives from the 2-D one), every other bit and column
+    untouched.  report, a dict of tensors on the table's device: `spike` bool [N, M]; `per_marker` [M] and `per_frame` [N] int64
+    counts; `median`, `mad` float64 [N, M, nv] (0 where not judged); `fill` bool [N, M]: the marker is missing and `median` is
+    the value to fill the gap with; `ref_spikes` int64: the slots whose row in frame 0 is a spike - such a slot drops out of
+    every analysis that takes frame 0 as its reference, so the caller may want another `ref_frame`; nothing is chosen for them
+    here; `source`, which `to_spike_frame` reads."""
+    from . import engine as _engine
+    if source not in _SPIKE_SOURCES:
+        raise ValueError(f"source must be one of {sorted(_SPIKE_SOURCES)}")
+    bit, clear, cols, _ = _SPIKE_SOURCES[source]
+    t = table if isinstance(table, torch.Tensor) else torch.as_tensor(np.asarray(table), device=eng.device)
+    if t.dim() != 3 or t.shape[2] != L.TABLE_COLS:
+        raise ValueError(f"table must be [N, M, {L.TABLE_COLS}]")
+    flags = t[..., 0].to(torch.int64)
+    valid = (flags & bit) != 0
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= t.shape[1]):
+            raise ValueError(f"slots outside the table's {t.shape[1]} slots")
+        pick = torch.zeros(t.shape[1], dtype=torch.bool, device=t.device)
+        pick[torch.as_tensor(idx, device=t.device)] = True
+        valid = valid & pick[None, :]
+    rec = torch.cat([valid.to(torch.float64)[..., None], t[..., list(cols)].to(torch.float64)], dim=2).contiguous()
+    out, _ = _engine.hampel_series_f64(rec, half_window, k_sigma, min_scale, want_clean=False, device=eng.device.index)
+    out = torch.as_tensor(out, device=t.device)
+    nv = len(cols)
+    spike, fill = out[..., 0] == 7.0, out[..., 0] == 2.0
+    clean = t.clone()
+    clean[..., 0] = torch.where(spike, (flags & ~clear).to(t.dtype), t[..., 0])
+    report = {"spike": spike, "per_marker": spike.sum(dim=0), "per_frame": spike.sum(dim=1),
+              "median": out[..., 2:2 + nv], "mad": out[..., 2 + nv:2 + 2 * nv], "fill": fill,
+              "ref_spikes": torch.nonzero(spike[0]).reshape(-1), "source": source}
+    return clean, report
+
+
+def to_spike_frame(report, table, ids=None, frame_offset=0, path=None):
+    """The sheet of `despike_table`: one row per spike, frame-major, from its `report` and the table it was given: `frameno,
+    marker_id`, the values (`Xw, Yw, Zw` or `Cx, Cy` by the report's source), their medians (`*_med`) and MADs (`*_mad`);
+    `marker_id` = `ids.marker_ids` (slot number + 1 without `ids`).  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    t, spike, med, mad = host(table), host(report["spike"]), host(report["median"]), host(report["mad"])
+    _, _, cols, names = _SPIKE_SOURCES[report["source"]]
+    if t.ndim != 3 or t.shape[2] != L.TABLE_COLS or spike.shape != t.shape[:2] or med.shape != t.shape[:2] + (len(cols),):
+        raise ValueError(f"table must be the [N, M, {L.TABLE_COLS}] table the report was made from")
+    mid = _ids.marker_ids(ids) if ids is not None else np.arange(1, t.shape[1] + 1, dtype=np.int64)
+    if len(mid) != t.shape[1]:
+        raise ValueError(f"table has {t.shape[1]} slots, ids {len(mid)}")
+    f, s = np.nonzero(spike)
+    data = {"frameno": (f + int(frame_offset)).astype(np.int64), "marker_id": np.asarray(mid)[s]}
+    for k, name in enumerate(names):
+        data[name] = t[f, s, cols[k]].astype(np.float64)
+    for k, name in enumerate(names):
+        data[name + "_med"] = med[f, s, k].astype(np.float64)
+    for k, name in enumerate(names):
+        data[name + "_mad"] = mad[f, s, k].astype(np.float64)
+    df = pd.DataFrame(data)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- pose misalignment along a recording (k_pose.hip): `deviation_pose` for every frame, with its trend ----------------------------
 _DEG = 57.29577951308232
 
