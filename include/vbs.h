@@ -948,6 +948,64 @@ int vbs_hampel_series_f64(int device, const double* rec, int n, int s, int cols,
                           double k_sigma, double min_scale, int frame_begin, int frame_end, double* out, double* clean,
                           void* stream);
 
+/* ---- Time-resolved amplitude and phase along a recording (the reference's Figure 11(b) shows the oscillation setting in, bursting
+ * and settling; it ships no code for this) ----
+ * The fit of vbs_harmonic_fit_f64, x ~ c0 + a cos(theta) + b sin(theta), in a SLIDING WINDOW at one known frequency nu, weighted
+ * by a symmetric window w, in two entries without a handle: the weighted sums of every window, then a small kernel that turns them
+ * into the fit of every frame.  Operator, window, coverage and conditioning rules are this project's.
+ *
+ * vbs_window_moments_f64 - rec [dev] float64 [n, s, cols], time-major, the record layout vbs_fir_series_f64 takes: col 0 the flag
+ * (nonzero = valid), cols 1 .. n_values the values, 1 <= n_values <= 3, n_values < cols <= 8; the values of VALID entries are
+ * finite with finite squares.  carrier [dev] float64 [4, n], row-major, finite, computed by the caller: rows c, s, c2, s2 = cos
+ * and sin of 2 pi nu f and of 2 pi (2 nu) f at the GLOBAL frame f (no sin / cos of the device enters a result; any finite carrier
+ * is taken).  half HOST [n_half]: the centre weight, then the weights at distance 1 .. h, h = n_half - 1, so w[k] = half[|k|],
+ * symmetric by construction, exactly as the FIR's taps travel; 0 <= h <= VBS_ENV_MAX_HALF (2h + 1 <= VBS_FIR_MAX_TAPS), every
+ * weight finite and >= 0, the centre > 0.  For every frame f of [frame_begin, frame_end) and every slot i the sums run over the
+ * VALID frames j of [f - h, f + h] n [0, n), with w = w[j - f]: M = 5 + 4 n_values sums, in this column order:
+ *     W = sum w    C1 = sum w c[j]    S1 = sum w s[j]    C2 = sum w c2[j]    S2 = sum w s2[j]
+ *     per value v:   X = sum w x    XC = sum w (x c[j])    XS = sum w (x s[j])    XX = sum w (x x)
+ * mom [dev] float64 [frame_end - frame_begin, s, M].  Invalid entries and frames outside [0, n) are selected out when they are
+ * staged, never multiplied by zero: they may hold NaN or 1e300, and so may every column beyond n_values.  A window with no valid
+ * frame gives exact zeros.  The call allocates nothing.
+ * The kernel is a banded float64 matrix product on v_mfma_f64_16x16x4_f64: a tile is 16 output frames x 16 columns of the
+ * flattened axis i M + m (the memory layout of mom), K the input frames, A[r][k] = w[k - r - h] inside the band and 0.0 outside
+ * (which is why a valid value must be finite with a finite square: 0.0 times it must be 0.0), B the staged, selected terms, the
+ * products x c, x s, x x rounded once each when staged.  Frame tiles are aligned to multiples of VBS_ENV_TILE of the GLOBAL frame
+ * index, never to frame_begin.  No atomics.
+ * THE ORDER OF SUMMATION IS NOT PART OF THIS INTERFACE, as for vbs_field_map_f64 and vbs_project_series_f64.  What is promised:
+ *   - exact where the inputs make every order exact: if every product and every partial sum is representable, every sum is exact;
+ *   - otherwise, with u = 2^-53, gamma_k = k u / (1 - k u), K = 2h + 1, every sum satisfies
+ *         |sum^ - sum| <= gamma_(K+8) sum w |term|      (term = 1, c, s, c2, s2, x, x c, x s, x x; derived in DESIGN 4.18)
+ *     for any order of summation, with or without fused multiply-add;
+ *   - bit-identical run to run, range by range (any frame_begin, frame_end) against the full call, a series alone against the same
+ *     series among s, with dead (invalid) slots appended and with dead frames appended at the end.
+ * A null pointer, n or s < 1, bad cols / n_values, n_half < 1 or h > VBS_ENV_MAX_HALF, a negative or non-finite weight, a centre
+ * <= 0, a range outside 0 <= fb <= fe <= n: VBS_EINVAL; n > VBS_PROJ_MAX_FRAMES or s > VBS_PROJ_MAX_SLOTS: VBS_ECAPACITY; a bad
+ * argument comes before a capacity; all decided before the device is touched.  fb == fe emits nothing.
+ *
+ * vbs_window_fit_f64 - mom [dev] float64 [F, s, M = 5 + 4 n_values] as above; sw = the ascending sum of all 2h + 1 weights
+ * (finite, > 0; the caller's, on the host), min_coverage in (0, 1], det_min in [0, 0.25).  Per (frame, slot), then per value:
+ *     CC = 0.5 * (W + C2) - (C1 * C1) / W    SS = 0.5 * (W - C2) - (S1 * S1) / W    CS = 0.5 * S2 - (C1 * S1) / W
+ *     det = CC * SS - CS * CS                ok = W > 0 && W >= min_coverage * sw && det > det_min * (W * W)
+ *     m = X / W     pc = XC - m * C1     ps = XS - m * S1
+ *     a = (pc * SS - ps * CS) / det          b = (ps * CC - pc * CS) / det          p = a * pc + b * ps
+ *     c0 = m - (a * C1 + b * S1) / W         M2 = XX - m * X
+ * the weighted floating-mean fit of vbs_harmonic_fit_f64 with W in the place of N (the half-angle identities hold under weights,
+ * which is why c2 and s2 travel); p is the drop in the weighted sum of squares M2.  EVERY EXPRESSION IS EVALUATED AS WRITTEN,
+ * FLOAT64 WITHOUT CONTRACTION (min_coverage * sw one product on the host), AND THAT IS PART OF THIS INTERFACE.  A comparison with
+ * a NaN is false, so a NaN W or det is not ok.  No square root and no atan2: amplitude and phase are the caller's.  M2 cancels
+ * where the mean dwarfs the oscillation: feed residuals.
+ * fit [dev] float64 [F, s, 1 + 5 n_values] = ok (1.0 / 0.0), then (a, b, p, c0, M2) per value; all zeros where !ok.  The flag
+ * makes fit a record that vbs_field_map_f64, vbs_fir_series_f64 and the step entries take as it is.  One thread per (frame, slot).
+ * A null pointer, F or s < 1, n_values outside 1..3, sw not finite or <= 0, min_coverage outside (0, 1], det_min outside [0, 0.25):
+ * VBS_EINVAL; F > VBS_PROJ_MAX_FRAMES or s > VBS_PROJ_MAX_SLOTS: VBS_ECAPACITY, after the arguments; before the device is touched. */
+#define VBS_ENV_TILE     64      /* frames a workgroup emits (no result depends on it)          */
+#define VBS_ENV_MAX_HALF 127     /* h at most: a window of 2h + 1 <= VBS_FIR_MAX_TAPS frames     */
+int vbs_window_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* carrier,
+                           const double* half, int n_half, int frame_begin, int frame_end, double* mom, void* stream);
+int vbs_window_fit_f64(int device, const double* mom, int F, int s, int n_values, double sw, double min_coverage, double det_min,
+                       double* fit, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

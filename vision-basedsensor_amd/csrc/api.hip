@@ -1046,6 +1046,34 @@ extern "C" int vbs_hampel_series_f64(int device, const double* rec, int n, int s
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- time-resolved amplitude and phase along a recording (k_envelope.hip) -------------------------------------------------------
+extern "C" int vbs_window_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* carrier,
+                                      const double* half, int n_half, int frame_begin, int frame_end, double* mom, void* stream) {
+    if (!rec || !carrier || !half || !mom || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
+        n_values >= cols || n_half < 1 || n_half - 1 > VBS_ENV_MAX_HALF || frame_begin < 0 || frame_end > n ||
+        frame_begin > frame_end)
+        return VBS_EINVAL;
+    for (int i = 0; i < n_half; ++i)
+        if (!std::isfinite(half[i]) || !(half[i] >= 0.0)) return VBS_EINVAL;
+    if (!(half[0] > 0.0)) return VBS_EINVAL;
+    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_window_moments(rec, n, s, cols, n_values, carrier, half, n_half, frame_begin, frame_end, mom, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_window_fit_f64(int device, const double* mom, int F, int s, int n_values, double sw, double min_coverage,
+                                  double det_min, double* fit, void* stream) {
+    if (!mom || !fit || F < 1 || s < 1 || n_values < 1 || n_values > 3 || !std::isfinite(sw) || !(sw > 0.0) ||
+        !(min_coverage > 0.0 && min_coverage <= 1.0) || !(det_min >= 0.0 && det_min < 0.25))
+        return VBS_EINVAL;
+    if (F > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_window_fit(mom, F, s, n_values, min_coverage * sw, det_min, fit, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- pose misalignment along a recording (k_pose.hip) ---------------------------------------------------------------------------
 extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
                                const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k,

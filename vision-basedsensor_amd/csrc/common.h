@@ -264,6 +264,11 @@ void launch_local_strain(const double* rec, int s, int cols, const double* pos, 
 // k_robust.hip (f16): gap-aware rolling median and MAD along time, the Hampel rule, the record with its spikes turned into gaps
 void launch_hampel_series(const double* rec, int n, int s, int cols, int n_values, int half_window, int min_count, double thr,
                           double min_scale, int frame_begin, int frame_end, double* out, double* clean, hipStream_t st);
+// k_envelope.hip (f17): the weighted sums of a sliding window at one frequency as a banded product on the float64 matrix
+// instruction, and the floating-mean fit of every window
+void launch_window_moments(const double* rec, int n, int s, int cols, int n_values, const double* carrier, const double* half,
+                           int n_half, int frame_begin, int frame_end, double* mom, hipStream_t st);
+void launch_window_fit(const double* mom, int F, int s, int n_values, double need, double det_min, double* fit, hipStream_t st);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

@@ -1267,6 +1267,115 @@ def local_strain_f64(rec, pos, nbr, min_count=4, det_rel=0.01, frame_range=None,
     return out
 
 
+# ---- time-resolved amplitude and phase (k_envelope.hip): the sums of a sliding window at one frequency, the fit of every window ----
+def taps_sum(half):
+    """The ascending sum of all 2h + 1 weights w[k] = half[|k|], k = -h .. h: `sw` of `vbs_window_fit_f64`, as the FIR adds its own."""
+    half = np.asarray(half, dtype=np.float64)
+    sw = np.float64(0.0)
+    for k in range(-(half.size - 1), half.size):
+        sw = sw + half[abs(k)]
+    return float(sw)
+
+
+def _envelope_args(n, s, cols, carrier_shape, half, n_values, frame_range):
+    """`window_moments_f64`'s argument checks (no device needed): -> (n_values, a, b) or ValueError."""
+    if n < 1 or s < 1 or not (2 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
+    if tuple(carrier_shape) != (4, n):
+        raise ValueError(f"carrier must be [4, {n}]: cos, sin of 2 pi nu f and of 2 pi (2 nu) f at every frame of rec (spectra.carrier)")
+    nv = min(cols - 1, 3) if n_values is None else int(n_values)
+    if not (1 <= nv <= 3 and nv < cols):
+        raise ValueError("n_values must be 1 .. 3 and below cols")
+    half = np.asarray(half, dtype=np.float64)
+    if half.ndim != 1 or half.size < 1 or half.size - 1 > L.ENV_MAX_HALF:
+        raise ValueError(f"the window must have 1 .. {2 * L.ENV_MAX_HALF + 1} taps (half_window <= VBS_ENV_MAX_HALF = {L.ENV_MAX_HALF})")
+    if not np.isfinite(half).all() or (half < 0.0).any() or not half[0] > 0.0:
+        raise ValueError("the window's weights must be finite and >= 0, the centre > 0")
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS)):
+        if got > cap:
+            raise L.VbsError(f"vbs_window_moments_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
+    return nv, a, b
+
+
+def window_moments_f64(rec, carrier, taps, n_values=None, frame_range=None, device=None):
+    """The weighted sums of a sliding window at one frequency for every frame and series (`vbs_window_moments_f64`), a banded
+    float64 matrix product over the time axis.  rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols
+    1 .. n_values the values (default min(cols - 1, 3)).  carrier float64 [4, n], finite (`spectra.carrier(n, nu)`).  `taps`: the
+    FULL odd-length symmetric window (`spectra.window_taps`), through `filters.half_taps` as `fir_series_f64` takes its own; at
+    most 2 * 127 + 1 weights, each >= 0, the centre > 0.  Returns float64 [b-a, s, 5 + 4 n_values] = W, C1, S1, C2, S2, then X, XC,
+    XS, XX per value, over the valid frames of [f - h, f + h], for the frames [a, b) of `frame_range` (default all); an output
+    does not depend on the range it was asked in."""
+    from .filters import half_taps
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    half = np.ascontiguousarray(half_taps(taps), dtype=np.float64)
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    c = torch.as_tensor(carrier, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    nv, a, b = _envelope_args(n, s, cols, c.shape, half, n_values, frame_range)
+    out = torch.empty((b - a, s, 5 + 4 * nv), dtype=torch.float64, device=dev)
+    if a == b:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_window_moments_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(c), half.ctypes.data_as(C.c_void_p), half.size,
+                                            a, b, _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_window_moments_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8, finite weights >= 0)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_window_moments_f64 failed ({rc})")
+    return out
+
+
+def _envelope_fit_args(F, s, M, taps_sum, min_coverage, det_min):
+    """`window_fit_f64`'s argument checks (no device needed): -> (n_values, sw, min_coverage, det_min) or ValueError."""
+    nv = (int(M) - 5) // 4
+    if F < 1 or s < 1 or int(M) != 5 + 4 * nv or not (1 <= nv <= 3):
+        raise ValueError("mom must be [F >= 1, s >= 1, 9 | 13 | 17]")
+    sw, mc, dm = float(taps_sum), float(min_coverage), float(det_min)
+    if not (np.isfinite(sw) and sw > 0.0):
+        raise ValueError("taps_sum must be finite and > 0 (engine.taps_sum of the window's half taps)")
+    if not (0.0 < mc <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    if not (0.0 <= dm < 0.25):
+        raise ValueError("det_min must lie in [0, 0.25)")
+    for what, got, name, cap in (("frames", F, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS)):
+        if got > cap:
+            raise L.VbsError(f"vbs_window_fit_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
+    return nv, sw, mc, dm
+
+
+def window_fit_f64(mom, taps_sum, min_coverage=0.5, det_min=1e-3, device=None):
+    """The weighted floating-mean fit x ~ c0 + a cos + b sin of every window (`vbs_window_fit_f64`).  mom float64
+    [F, s, 5 + 4 n_values] as `window_moments_f64` returns it; `taps_sum` the ascending sum of the window's weights
+    (`engine.taps_sum(filters.half_taps(taps))`).  A window is ok where W > 0, W >= `min_coverage` x taps_sum and the determinant
+    of its normal equations exceeds `det_min` W^2 (W^2 / 4 is what a whole number of periods without gaps gives).  Returns float64
+    [F, s, 1 + 5 n_values] = ok, then a, b, the power p, c0 and the weighted sum of squared deviations M2 per value; zeros where
+    not ok.  Amplitude and phase: `spectra.amplitude_phase(a, b)`."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    m = torch.as_tensor(mom, dtype=torch.float64, device=dev).contiguous()
+    if m.dim() != 3:
+        raise ValueError("mom must be [F, s, 5 + 4 n_values]")
+    F, s, M = m.shape
+    nv, sw, mc, dm = _envelope_fit_args(F, s, M, taps_sum, min_coverage, det_min)
+    out = torch.empty((F, s, 1 + 5 * nv), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_window_fit_f64(dev.index, _ptr(m), F, s, nv, sw, mc, dm, _ptr(out),
+                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_window_fit_f64: bad argument (taps_sum > 0, min_coverage in (0, 1], det_min in [0, 0.25))")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_window_fit_f64 failed ({rc})")
+    return out
+
+
 # ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
 def _steps_call(name, what, fn):
     rc = fn()

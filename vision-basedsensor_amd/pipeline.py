@@ -590,6 +590,16 @@ SPECTRUM_FRAME_COLUMNS = ("marker_id", "axis", "freq", "amplitude", "phase_deg",
 SPECTRUM_COLS = 6              # freq, amplitude, phase_deg, power, explained, count of `spectral_analysis`'s `marker` and `total`
 
 
+def _oscillation_series(rec, taps, dev):
+    """The record [N, k, 4] = flag, x, y, z that `spectral_analysis` and `envelope_analysis` analyse: the first three values of
+    `rec` as they are, or with `taps` their FIR residual over the entries that have a trend (flag 3)."""
+    from .engine import fir_series_f64
+    if taps is None:
+        return rec[..., :4].contiguous()
+    f = fir_series_f64(rec, taps, 3, device=dev)
+    return torch.cat([(f[..., :1] == 3.0).to(torch.float64), f[..., 4:7]], dim=2)
+
+
 def _spectrum_args(n, m, freqs, ref_frame, slot_mask, min_count, det_min, axis="z"):
     """`spectral_analysis`'s argument checks (no device needed): -> (freqs [Q], min_count, slot indices or None, axis index)."""
     from . import spectra
@@ -647,22 +657,16 @@ def spectral_analysis(eng: Engine, table: torch.Tensor, freqs, ref_frame=0, taps
     without an ok bin), `common_freq`; and the PHASE MAP `phase_map` [M, 3] = ok, amplitude, phase_deg of every slot at that bin.
     With `fps`: `freqs_hz`, `common_freq_hz`."""
     from . import spectra
-    from .engine import fir_series_f64, harmonic_fit_f64, project_series_f64, series_stats_f64
+    from .engine import harmonic_fit_f64, project_series_f64, series_stats_f64
     n, m = int(table.shape[0]), int(table.shape[1])
     nu, mc, slots, ax = _spectrum_args(n, m, freqs, ref_frame, slot_mask, min_count, det_min, axis)
     dev = eng.device.index
     ax_rec, tot = eng.axis_displacement(table, ref_frame, slots)
-
-    def series_of(rec):
-        if taps is None:
-            return rec[..., :4].contiguous()
-        f = fir_series_f64(rec, taps, 3, device=dev)
-        return torch.cat([(f[..., :1] == 3.0).to(torch.float64), f[..., 4:7]], dim=2)
     Q = int(nu.size)
     basis = torch.from_numpy(spectra.harmonic_basis(n, nu)).to(eng.device)
     out = {"freqs": nu}
     for name, rec in (("", ax_rec), ("total_", tot[:, None, :])):
-        series = series_of(rec)
+        series = _oscillation_series(rec, taps, dev)
         proj = project_series_f64(series, basis, 3, device=dev)
         fit, peak = harmonic_fit_f64(proj, Q, mc, det_min, device=dev)
         k = series.shape[1]
@@ -713,6 +717,165 @@ def to_spectrum_frame(marker, ids=None, fps=None, path=None):
     if fps is not None:
         from . import spectra
         cols["freq_hz"] = spectra.to_hz(flat[:, 0], fps)
+    df = pd.DataFrame(cols)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
+# ---- time-resolved amplitude and phase (k_envelope.hip): the fit of every marker in a sliding window at one frequency -------------
+ENVELOPE_FRAME_COLUMNS = ("frameno", "marker_id", "axis", "amplitude", "phase_deg", "explained")
+ENVELOPE_SUMMARY_COLS = 5      # peak amplitude, its frame, level, onset, count of ok frames
+
+
+def _envelope_analysis_args(n, m, nu, half_window, window, ref_frame, slot_mask, min_coverage, det_min, onset_frac, axis="z"):
+    """`envelope_analysis`'s argument checks (no device needed): -> (nu, the window's full taps, slot indices or None, axis index)."""
+    from . import spectra
+    if isinstance(nu, dict):
+        nu = nu["common_freq"]
+    nu = float(spectra._freqs([nu])[0])
+    w = spectra.window_taps(half_window, window)
+    if w.size > 2 * L.ENV_MAX_HALF + 1:
+        raise ValueError(f"half_window {half_window} above VBS_ENV_MAX_HALF = {L.ENV_MAX_HALF}")
+    if n > L.PROJ_MAX_FRAMES or m > L.PROJ_MAX_SLOTS:
+        raise ValueError(f"the table's {n} frames x {m} slots exceed VBS_PROJ_MAX_FRAMES = {L.PROJ_MAX_FRAMES} or "
+                         f"VBS_PROJ_MAX_SLOTS = {L.PROJ_MAX_SLOTS}")
+    if not (0 <= int(ref_frame) < n):
+        raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+    if not (0.0 < float(min_coverage) <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    if not (0.0 <= float(det_min) < 0.25):
+        raise ValueError("det_min must lie in [0, 0.25)")
+    if not (0.0 < float(onset_frac) <= 1.0):
+        raise ValueError("onset_frac must lie in (0, 1]")
+    if axis not in _SPECTRUM_AXES:
+        raise ValueError(f"axis must be one of {_SPECTRUM_AXES}")
+    slots = None
+    if slot_mask is not None:
+        k = np.asarray(slot_mask)
+        if k.shape != (m,):
+            raise ValueError(f"slot_mask must be [{m}]: nonzero = the slot takes part")
+        slots = np.nonzero(k)[0]
+    return nu, w, slots, _SPECTRUM_AXES.index(axis)
+
+
+def _envelope_rows(fit, onset_frac=0.5):
+    """The host arithmetic of `envelope_analysis`: fit [F, k, 16] (host, as `window_fit_f64` writes it for 3 values) -> a dict of
+    `amplitude`, `phase_deg`, `explained` = p / M2 [F, k, 3], NaN where the window is not ok; `freq_dev` [k, 3] = minus the
+    least-squares slope of the unwrapped phase over the longest run of consecutive ok frames (the first of equal ones; at least 3
+    frames, else NaN), in cycles per frame: how far the line lies above the carrier; `summary` [k, 3, 5] = the peak amplitude
+    (NaN without an ok frame), its frame (the first of equal ones, -1), `level` = the median amplitude over the ok frames, `onset`
+    = the first ok frame whose amplitude reaches `onset_frac` x peak (-1 without one), and the count of ok frames."""
+    from . import spectra
+    fit = np.asarray(fit, dtype=np.float64)
+    F, k = fit.shape[0], fit.shape[1]
+    ok = fit[..., 0] != 0.0
+    a, b, p, M2 = fit[..., 1::5], fit[..., 2::5], fit[..., 3::5], fit[..., 5::5]
+    amp, ph = spectra.amplitude_phase(a, b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        expl = p / M2
+    nan = lambda v: np.where(ok[..., None], v, np.nan)                                           # noqa: E731
+    out = {"amplitude": nan(amp), "phase_deg": nan(ph), "explained": nan(expl)}
+    summary = np.zeros((k, 3, ENVELOPE_SUMMARY_COLS))
+    freq_dev = np.full((k, 3), np.nan)
+    for i in range(k):
+        fr = np.nonzero(ok[:, i])[0]
+        if fr.size == 0:
+            summary[i] = (np.nan, -1.0, np.nan, -1.0, 0.0)
+            continue
+        # the longest run of consecutive ok frames, the first of equal ones
+        cut = np.nonzero(np.diff(fr) != 1)[0] + 1
+        runs = np.split(fr, cut)
+        run = runs[int(np.argmax([r.size for r in runs]))]
+        for v in range(3):
+            av = amp[fr, i, v]
+            if np.isnan(av).all():
+                summary[i, v] = (np.nan, -1.0, np.nan, -1.0, fr.size)
+                continue
+            j = int(np.nanargmax(av))
+            reach = np.nonzero(av >= onset_frac * av[j])[0]
+            summary[i, v] = (av[j], fr[j], np.nanmedian(av), fr[reach[0]] if reach.size else -1.0, fr.size)
+            if run.size >= 3 and np.isfinite(ph[run, i, v]).all():
+                un = np.unwrap(np.radians(ph[run, i, v]))
+                freq_dev[i, v] = -np.polyfit(run.astype(np.float64) - run[0], un, 1)[0] / (2.0 * np.pi)
+    out["freq_dev"], out["summary"] = freq_dev, summary
+    return out
+
+
+def envelope_analysis(eng: Engine, table: torch.Tensor, nu, half_window=32, window="hann", ref_frame=0, taps=None, slot_mask=None,
+                      min_coverage=0.5, det_min=1e-3, onset_frac=0.5, fps=None, grid=None, axis="z"):
+    """How the oscillation at the known frequency `nu` changes along the recording (the reference's Figure 11(b)
+    shows it set in, burst and settle, and ships no code for it) from a table [N, M, 10]: the series `spectral_analysis` analyses
+    (`Engine.axis_displacement` against `ref_frame`, `slot_mask` [M]; with `taps` its FIR residual over flag 3) fitted by
+    c0 + a cos + b sin in a sliding window of 2 `half_window` + 1 frames weighted by `spectra.window_taps(half_window, window)`:
+    `window_moments_f64` then `window_fit_f64` for the markers, and the same pair for the per-frame `total` as a record of one
+    series.  `nu`: cycles per frame in (0, 0.25], or the dict `spectral_analysis` returned (its `common_freq`).  Returns a dict.
+    Device tensors (float64): `series` [N, M, 4], `fit` [N, M, 16], `total_series` [N, 1, 4], `total_fit` [N, 1, 16].  Host arrays
+    (`_envelope_rows`): `amplitude`, `phase_deg`, `explained` [N, M, 3], NaN where the window is not ok; `freq_dev` [M, 3];
+    `summary` [M, 3, 5] = peak amplitude, its frame, level (the median amplitude over the ok frames), onset (the first ok frame
+    whose amplitude reaches `onset_frac` x peak, -1 without one), count of ok frames; and `total_amplitude`, `total_phase_deg`,
+    `total_explained` [N, 3], `total_freq_dev` [3], `total_summary` [3, 5]; `nu`, `taps_sum`.  With `grid` = (weights [P, M], wsum
+    [P]) from `fields.gaussian_weights` / `fields.row_sums`: `amplitude_map` [N, P, 2] = `field_map_f64` of the record (ok,
+    amplitude of `axis`): where on the bonnet the oscillation is strongest, frame by frame.  With `fps`: `nu_hz`, `freq_dev_hz`,
+    `total_freq_dev_hz`."""
+    from . import spectra
+    from .engine import field_map_f64, taps_sum, window_fit_f64, window_moments_f64
+    from .filters import half_taps
+    n, m = int(table.shape[0]), int(table.shape[1])
+    nu, w, slots, ax = _envelope_analysis_args(n, m, nu, half_window, window, ref_frame, slot_mask, min_coverage, det_min, onset_frac,
+                                               axis)
+    dev = eng.device.index
+    ax_rec, tot = eng.axis_displacement(table, ref_frame, slots)
+    car = torch.from_numpy(spectra.carrier(n, nu)).to(eng.device)
+    sw = taps_sum(half_taps(w))
+    out = {"nu": nu, "taps_sum": sw}
+    for name, rec in (("", ax_rec), ("total_", tot[:, None, :])):
+        series = _oscillation_series(rec, taps, dev)
+        mom = window_moments_f64(series, car, w, 3, device=dev)
+        fit = window_fit_f64(mom, sw, min_coverage, det_min, device=dev)
+        out.update({name + "series": series, name + "fit": fit})
+        rows = _envelope_rows(fit.cpu().numpy(), onset_frac)
+        for key, val in rows.items():
+            out[name + key] = val if not name else (val[0] if key in ("freq_dev", "summary") else val[:, 0])
+    if grid is not None:
+        Wg, wsum = grid
+        amp = out["amplitude"][..., ax]
+        rec = torch.from_numpy(np.stack([(~np.isnan(amp)).astype(np.float64), np.nan_to_num(amp, nan=0.0)], axis=2)).to(eng.device)
+        out["amplitude_map"] = field_map_f64(rec, torch.as_tensor(Wg, dtype=torch.float64, device=eng.device),
+                                             torch.as_tensor(wsum, dtype=torch.float64, device=eng.device), min_coverage, 1, device=dev)
+    if fps is not None:
+        out["nu_hz"] = float(spectra.to_hz(nu, fps))
+        out["freq_dev_hz"] = spectra.to_hz(out["freq_dev"], fps)
+        out["total_freq_dev_hz"] = spectra.to_hz(out["total_freq_dev"], fps)
+    return out
+
+
+def to_envelope_frame(result, ids=None, fps=None, path=None):
+    """The long sheet of `envelope_analysis`: one row `ENVELOPE_FRAME_COLUMNS` per frame, slot and axis (frame-major, then slot,
+    then axis "x", "y", "z") from its `amplitude`, `phase_deg`, `explained` [N, M, 3]; `frameno` counts from 1, `marker_id` =
+    `ids.marker_ids` (slot number + 1 without `ids`); with `fps` also `time_s` = (frameno - 1) / fps.  amplitude .. explained are
+    NaN (empty cells) where the window is not ok.  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    amp, ph, ex = (np.asarray(result[k], dtype=np.float64) for k in ("amplitude", "phase_deg", "explained"))
+    if amp.ndim != 3 or amp.shape[2] != 3 or ph.shape != amp.shape or ex.shape != amp.shape:
+        raise ValueError("amplitude, phase_deg and explained must be [N, M, 3]")
+    N, M = amp.shape[:2]
+    mid = _ids.marker_ids(ids) if ids is not None else np.arange(1, M + 1, dtype=np.int64)
+    if len(mid) != M:
+        raise ValueError(f"the result has {M} slots, ids {len(mid)}")
+    cols = {"frameno": np.repeat(np.arange(1, N + 1, dtype=np.int64), 3 * M),
+            "marker_id": np.tile(np.repeat(np.asarray(mid), 3), N),
+            "axis": np.tile(np.array(_SPECTRUM_AXES, dtype=object), N * M),
+            "amplitude": amp.reshape(-1), "phase_deg": ph.reshape(-1), "explained": ex.reshape(-1)}
+    if fps is not None:
+        fps = float(fps)
+        if not (np.isfinite(fps) and fps > 0.0):
+            raise ValueError("fps must be finite and > 0")
+        cols["time_s"] = (cols["frameno"] - 1) / fps
     df = pd.DataFrame(cols)
     if path is not None:
         if str(path).lower().endswith(".csv"):

@@ -32,6 +32,27 @@ def harmonic_basis(n, freqs):
     return B
 
 
+def carrier(n, nu):
+    """The carrier `engine.window_moments_f64` expects, float64 [4, n]: cos and sin of 2 pi nu f and of 2 pi (2 nu) f at the frames
+    f = 0 .. n-1 (rows 1, 2 and 3, 4 of `harmonic_basis(n, [nu])`, bit for bit).  nu in cycles per frame, in (0, 0.25]."""
+    return np.ascontiguousarray(harmonic_basis(n, [float(nu)])[1:5])
+
+
+def window_taps(half_window, kind="hann"):
+    """The full odd-length window of 2 h + 1 weights for `engine.window_moments_f64`, exactly symmetric.  "hann":
+    0.5 (1 + cos(pi k / (h + 1))), k = -h .. h, strictly positive (the zeros of the Hann window lie one step outside); "rect":
+    all ones."""
+    h = int(half_window)
+    if h != half_window or h < 0:
+        raise ValueError(f"half_window must be an integer >= 0, got {half_window!r}")
+    if kind == "rect":
+        return np.ones(2 * h + 1)
+    if kind != "hann":
+        raise ValueError('kind must be "hann" or "rect"')
+    k = np.abs(np.arange(-h, h + 1)).astype(np.float64)
+    return 0.5 * (1.0 + np.cos(np.pi * k / (h + 1)))
+
+
 def zoom_grid(centre, half_width, Q):
     """Q equally spaced frequencies over [centre - half_width, centre + half_width] (Q = 1: the centre alone): a grid finer than
     the natural 1 / n round a known line.  With Q odd the centre is bin (Q - 1) / 2."""
