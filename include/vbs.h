@@ -1006,6 +1006,113 @@ int vbs_window_moments_f64(int device, const double* rec, int n, int s, int cols
 int vbs_window_fit_f64(int device, const double* mom, int F, int s, int n_values, double sw, double min_coverage, double det_min,
                        double* fit, void* stream);
 
+/* ---- Principal modes of the displacement field along a recording (the reference ships no code for this; every other analysis
+ * here reduces the recording with a model chosen in advance) ----
+ * Which spatial patterns of marker displacement a recording consists of, how much of the variance each carries and how each
+ * evolves along time: PCA / proper orthogonal decomposition with gaps, in four entries without a handle on the record layout of
+ * vbs_fir_series_f64 (rec [dev] float64 [n, s, cols], time-major, col 0 the flag, cols 1 .. n_values the values, 1 <= n_values <= 3,
+ * n_values < cols <= 8; invalid entries are selected out when they are read, never multiplied by zero: they and every column
+ * beyond n_values may hold NaN or 1e300).  The estimators, the drop rule, the sign rule and `resid` are this project's (DESIGN
+ * 4.19, 7).  No call allocates; no atomics, no wait across workgroups.
+ *
+ * vbs_cross_moments_f64 - shift [dev] float64 [s, n_values] (may be NULL = 0) is subtracted ONCE, rounded, when a valid entry is
+ * staged: z = x - shift, AND THAT SUBTRACTION IS PART OF THE INTERFACE; it keeps the later centring free of cancellation, so the
+ * caller passes the per-series means.  Per slot the columns are col_0..2 = z_1, z_2, z_3 (a column beyond n_values is 0) and
+ * col_3 = the flag as 1.0 / 0.0, all 0 in a frame where the slot is invalid.
+ * mom [dev] float64 [s, s, 4, 4]: mom[i, j, v, w] = sum over the frames of col_v(i) col_w(j).  The 3 x 3 corner: the cross sums over
+ * the frames where BOTH slots are valid; row or column 3: the sum of one slot's values over the frames where the other is valid
+ * too (what pairwise-complete centring needs); [3][3]: the pair count, an exact integer.
+ * The kernel is a float64 matrix product on v_mfma_f64_16x16x4_f64 with the frame axis as K, both operands staged from the record;
+ * a workgroup takes one pair of tiles of VBS_MOM_WG_SLOTS slots with j-tile >= i-tile and writes the mirror block too:
+ * mom[j, i, w, v] HAS THE BITS OF mom[i, j, v, w].  NO SPLIT OF K ACROSS WORKGROUPS: every output is one accumulator chain over the
+ * frames, chunk after chunk of VBS_MOM_CHUNK in ascending order from frame 0.
+ * THE ORDER OF SUMMATION IS NOT PART OF THIS INTERFACE, as for vbs_project_series_f64.  What is promised instead:
+ *   - exact where the inputs make every order exact: if every z, every product and every partial sum is representable;
+ *   - otherwise, with u = 2^-53, gamma_k = k u / (1 - k u), over the frames:
+ *     |mom^ - mom| <= gamma_(n+6) sum |col_v(i) col_w(j)|   (mom the sums of the ROUNDED z; derived in DESIGN 4.19),
+ *     for any order of summation, with or without fused multiply-add;
+ *   - bit-identical run to run, a pair of slots alone against the same pair among s, with dead (invalid) slots appended and with
+ *     dead frames appended at the end.
+ * A null rec or mom, n or s < 1, bad cols / n_values: VBS_EINVAL; n > VBS_PROJ_MAX_FRAMES or s > VBS_MOM_MAX_SLOTS: VBS_ECAPACITY; a
+ * bad argument comes before a capacity; all decided before the device is touched.
+ *
+ * vbs_covariance_f64 - mom as above.  cov [dev] float64 [C, C], C = s n_values, c = i n_values + v.  With N = mom[i,j,3,3],
+ * S = mom[i,j,v,w], a = mom[i,j,v,3], b = mom[i,j,3,w], for c = (i, v) <= c' = (j, w):
+ *     mode 0, pairwise:   cov = (S - (a * b) / N) / (N - 1)
+ *     mode 1, filled:     m_i = mom[i,i,v,3] / mom[i,i,3,3],   m_j = mom[j,j,w,3] / mom[j,j,3,3]
+ *                         cov = (S - m_i * b - m_j * a + N * (m_i * m_j)) / denom        (left to right)
+ * and cov[c', c] is a copy of cov[c, c'].  EVERY EXPRESSION IS EVALUATED AS WRITTEN, FLOAT64 WITHOUT CONTRACTION, AND THAT IS PART OF
+ * THIS INTERFACE.  Mode 1 is the Gram matrix of the data with every gap filled by its series' mean, divided by denom (the pipeline
+ * passes n - 1): positive semidefinite as long as no pair of unmasked slots falls below min_count (a block zeroed for that
+ * breaks the Gram structure; a masked slot, whose whole rows and columns go, does not), biased towards zero by the share of gaps
+ * (DESIGN 7).  Mode 0 is unbiased pair by pair and may be INDEFINITE.  ok = N >= min_count (min_count >= 2) and neither slot masked; where !ok the nine cells are exact zeros.
+ * slot_mask [dev] uint8 [s] (may be NULL = all): a slot with 0 gives !ok rows and columns.  ok [dev] uint8 [s, s] (may be NULL).
+ * One thread per slot pair.  A null mom or cov, s < 1, n_values outside 1..3, mode not 0 or 1, min_count < 2, in mode 1 a denom
+ * that is not finite or <= 0: VBS_EINVAL; s > VBS_MOM_MAX_SLOTS: VBS_ECAPACITY, after the arguments; before the device is touched.
+ *
+ * vbs_leading_modes_f64 - the r <= VBS_MODES_MAX leading eigenpairs of a symmetric A [dev] float64 [C, C] (only what is stated
+ * below is read of it; an unsymmetric A gives what the operations give) by orthogonal iteration with a FIXED number of
+ * iterations: nothing is tested for convergence, `resid` says what was reached.  The iteration finds the invariant subspace of
+ * the LARGEST |lambda|: of an indefinite A (mode 0 above) these may be negative; within the subspace the values come descending.
+ * work [dev] float64 [2 C VBS_MODES_MAX], the caller's.  Blocks are [C][VBS_MODES_MAX], r columns used.
+ *   start    Q0[c][k] = (double)(int32)h(c VBS_MODES_MAX + k + 1) * 2^-31, h(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13;
+ *            x *= 0xc2b2ae35; x ^= x >> 16 on uint32; then `orth`
+ *   iterate  `iters` times: Y = A Q (`apply`), Q = orth of Y
+ *   apply    one wave per row of A: lane l of 64 adds a[c] * Q[c][k] for c = l, l + 64, .. ascending from 0.0, the 64 sums are
+ *            folded a[i] + a[i + 32], then + 16, 8, 4, 2, 1: the order of vbs_axis_displacement
+ *   sums     every other sum over the rows c of a block: thread t of 256 adds rows t, t + 256, .. ascending from 0.0, each of the
+ *            four waves folds its 64 sums as above, the wave sums are added ((W0 + W1) + W2) + W3
+ *   orth     big = the largest of the r squared column norms as they came in.  Twice: for j = 0 .. r-1 ascending: S_k = sum
+ *            x_j x_k for k = j .. r-1 (the current columns); the column is DROPPED (zeros, counted in the first round) unless
+ *            S_j > tiny * big (first round) or S_j > 0 (second); else nrm = sqrt(S_j), x_j = x_j / nrm, and for k > j
+ *            x_k = x_k - (S_k / nrm) * x_j with the new x_j: modified Gram-Schmidt, row-oriented
+ *   ritz     Y = A Q once more; T[k][l] = sum Q_k Y_l for k <= l, mirrored; cyclic Jacobi on T, pairs (p, q), p < q, row by row,
+ *            VBS_MODES_SWEEPS sweeps: skipped where T[p][q] == 0, else theta = (T[q][q] - T[p][p]) / (2 T[p][q]),
+ *            t = (theta < 0 ? -1 : 1) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c; for every k the columns
+ *            (T[k][p], T[k][q]) = (c x - s y, s x + c y), then the rows likewise, then the columns of V (from the identity), then
+ *            T[p][q] = T[q][p] = 0.  Values = the diagonal, sorted descending, the smaller index first among equals.
+ *            u_k[c] = sum over l ascending of Q[c][l] V[l][k], (A u)_k[c] likewise from Y; resid_k = sqrt of the sum (by `sums`) of
+ *            ((A u)_k[c] - lambda_k u_k[c])^2.  Every mode's sign makes its entry of largest magnitude positive, the smallest
+ *            index among equals.
+ * values [dev] float64 [r]; modes [dev] float64 [r, C], orthonormal rows, zeros for a dropped column, whose value 0 and resid 0
+ * take the place the descending sort gives a 0: behind the others where every kept value is positive, BETWEEN the positive and
+ * the negative ones of an indefinite A - a dropped row is told by its zeros, not by its place;
+ * resid [dev] float64 [r] = || A u - lambda u ||_2: THE HONEST CONVERGENCE MEASURE, the fixed `iters` guarantees nothing by itself
+ * (the error of a value is at most its resid; the subspace converges like (|lambda_(r+1)| / |lambda_k|)^iters);
+ * info [dev] int32 [2] = rank found (r - dropped), columns dropped, of the last orth.  THE ORDER OF EVERY OPERATION IS PART OF THIS
+ * INTERFACE.  A null pointer, C < 1, r outside 1 .. min(C, VBS_MODES_MAX), iters outside 0 .. VBS_MODES_MAX_ITERS, tiny outside
+ * [0, 1): VBS_EINVAL; C > VBS_MODES_MAX_DIM: VBS_ECAPACITY, after the arguments; before the device is touched.
+ *
+ * vbs_mode_scores_f64 - rec as above; center [dev] float64 [C] (shift plus mean, the caller's); modes [dev] float64 [r, C].  For
+ * every frame f of [frame_begin, frame_end), over the VALID columns c = i n_values + v of the frame, lane l of 64 adding
+ * c = l, l + 64, .. ascending from 0.0 and the 64 sums folded 32, 16, 8, 4, 2, 1 (THE ORDER IS PART OF THIS INTERFACE), with
+ * d_c = x_c - center_c:   num_k = sum d_c u_k[c]     den_k = sum u_k[c] u_k[c]     e = sum d_c d_c
+ * scores [dev] float64 [fe-fb, r, 3] = (1, num_k / den_k, den_k) where den_k >= min_coverage, else (0, 0, den_k): u has unit norm,
+ * so den is the share of the mode that was seen, and num / den the least-squares amplitude of the mode over what was seen.  A
+ * record with cols 3, n_values 1, s = r that vbs_fir_series_f64, vbs_hampel_series_f64, vbs_project_series_f64,
+ * vbs_window_moments_f64 and vbs_step_response_f64 take as it is.  energy (may be NULL) [dev] float64 [fe-fb, 2] = the number of
+ * valid columns, e.  One wave per frame, VBS_SCORE_GROUP frames a workgroup (no result depends on it).  A null rec, center, modes
+ * or scores, n or s < 1, bad cols / n_values, r outside 1 .. VBS_MODES_MAX, min_coverage outside (0, 1], a range outside
+ * 0 <= fb <= fe <= n: VBS_EINVAL; n > VBS_PROJ_MAX_FRAMES or s > VBS_MOM_MAX_SLOTS: VBS_ECAPACITY, after the arguments; before the
+ * device is touched.  fb == fe emits nothing. */
+#define VBS_MOM_CHUNK       32       /* frames staged at a time (no result depends on it)                    */
+#define VBS_MOM_WG_SLOTS    16       /* slots of a tile; a workgroup takes a pair of tiles (no result depends on it) */
+#define VBS_MOM_MAX_SLOTS   1024     /* s at most                                                            */
+#define VBS_MODES_MAX       16       /* r at most                                                            */
+#define VBS_MODES_MAX_DIM   3072     /* C at most                                                            */
+#define VBS_MODES_SWEEPS    10       /* Jacobi sweeps of the Ritz step                                       */
+#define VBS_MODES_MAX_ITERS 4096     /* iters at most                                                        */
+#define VBS_SCORE_GROUP     8        /* frames a workgroup of the scores takes, one wave each                */
+int vbs_cross_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* shift, double* mom,
+                          void* stream);
+int vbs_covariance_f64(int device, const double* mom, int s, int n_values, int mode, int min_count, double denom,
+                       const uint8_t* slot_mask, double* cov, uint8_t* ok, void* stream);
+int vbs_leading_modes_f64(int device, const double* A, int C, int r, int iters, double tiny, double* work, double* values,
+                          double* modes, double* resid, int32_t* info, void* stream);
+int vbs_mode_scores_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* center,
+                        const double* modes, int r, double min_coverage, int frame_begin, int frame_end, double* scores,
+                        double* energy, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

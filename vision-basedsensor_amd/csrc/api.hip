@@ -1074,6 +1074,54 @@ extern "C" int vbs_window_fit_f64(int device, const double* mom, int F, int s, i
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- principal modes of the displacement field (k_modes.hip) ----------------------------------------------------------------------
+extern "C" int vbs_cross_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* shift,
+                                     double* mom, void* stream) {
+    if (!rec || !mom || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 || n_values >= cols) return VBS_EINVAL;
+    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_MOM_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_cross_moments(rec, n, s, cols, n_values, shift, mom, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_covariance_f64(int device, const double* mom, int s, int n_values, int mode, int min_count, double denom,
+                                  const uint8_t* slot_mask, double* cov, uint8_t* ok, void* stream) {
+    if (!mom || !cov || s < 1 || n_values < 1 || n_values > 3 || (mode != 0 && mode != 1) || min_count < 2 ||
+        (mode == 1 && (!std::isfinite(denom) || !(denom > 0.0))))
+        return VBS_EINVAL;
+    if (s > VBS_MOM_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_covariance(mom, s, n_values, mode, min_count, denom, slot_mask, cov, ok, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_leading_modes_f64(int device, const double* A, int C, int r, int iters, double tiny, double* work, double* values,
+                                     double* modes, double* resid, int32_t* info, void* stream) {
+    if (!A || !work || !values || !modes || !resid || !info || C < 1 || r < 1 || r > VBS_MODES_MAX || iters < 0 ||
+        iters > VBS_MODES_MAX_ITERS || !(tiny >= 0.0 && tiny < 1.0))
+        return VBS_EINVAL;
+    if (r > C) return VBS_EINVAL;
+    if (C > VBS_MODES_MAX_DIM) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_leading_modes(A, C, r, iters, tiny, work, values, modes, resid, info, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_mode_scores_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* center,
+                                   const double* modes, int r, double min_coverage, int frame_begin, int frame_end, double* scores,
+                                   double* energy, void* stream) {
+    if (!rec || !center || !modes || !scores || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
+        n_values >= cols || r < 1 || r > VBS_MODES_MAX || !(min_coverage > 0.0 && min_coverage <= 1.0) || frame_begin < 0 ||
+        frame_end > n || frame_begin > frame_end)
+        return VBS_EINVAL;
+    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_MOM_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_mode_scores(rec, s, cols, n_values, center, modes, r, min_coverage, frame_begin, frame_end, scores, energy,
+                           (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- pose misalignment along a recording (k_pose.hip) ---------------------------------------------------------------------------
 extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
                                const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k,

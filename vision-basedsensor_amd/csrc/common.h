@@ -269,6 +269,15 @@ void launch_hampel_series(const double* rec, int n, int s, int cols, int n_value
 void launch_window_moments(const double* rec, int n, int s, int cols, int n_values, const double* carrier, const double* half,
                            int n_half, int frame_begin, int frame_end, double* mom, hipStream_t st);
 void launch_window_fit(const double* mom, int F, int s, int n_values, double need, double det_min, double* fit, hipStream_t st);
+// k_modes.hip (f18): the cross moments of all pairs of series on the float64 matrix instruction, the covariance they give, its
+// leading eigenpairs by orthogonal iteration (apply, orthogonalise, Ritz step), and the score of every mode in every frame
+void launch_cross_moments(const double* rec, int n, int s, int cols, int n_values, const double* shift, double* mom, hipStream_t st);
+void launch_covariance(const double* mom, int s, int n_values, int mode, int min_count, double denom, const u8* slot_mask, double* cov,
+                       u8* ok, hipStream_t st);
+void launch_leading_modes(const double* A, int C, int r, int iters, double tiny, double* work, double* values, double* modes,
+                          double* resid, int32_t* info, hipStream_t st);
+void launch_mode_scores(const double* rec, int s, int cols, int n_values, const double* center, const double* modes, int r,
+                        double min_coverage, int frame_begin, int frame_end, double* scores, double* energy, hipStream_t st);
 // k_steps.hip (f11): step response, peak search, dwell statistics
 void launch_step_response(const double* rec, int n, int s, int cols, int n_values, int w, int min_count, double* out,
                           hipStream_t st);

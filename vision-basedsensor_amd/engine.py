@@ -1376,6 +1376,195 @@ def window_fit_f64(mom, taps_sum, min_coverage=0.5, det_min=1e-3, device=None):
     return out
 
 
+# ---- principal modes of the displacement field (k_modes.hip): cross moments, covariance, leading eigenpairs, scores -----------------
+def _moments_args(n, s, cols, shift_shape, n_values):
+    """`cross_moments_f64`'s argument checks (no device needed): -> n_values or ValueError / VbsError."""
+    if n < 1 or s < 1 or not (2 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
+    nv = min(cols - 1, 3) if n_values is None else int(n_values)
+    if not (1 <= nv <= 3 and nv < cols):
+        raise ValueError("n_values must be 1 .. 3 and below cols")
+    if shift_shape is not None and tuple(shift_shape) != (s, nv):
+        raise ValueError(f"shift must be [{s}, {nv}]: one value per slot and value column")
+    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_MOM_MAX_SLOTS", L.MOM_MAX_SLOTS)):
+        if got > cap:
+            raise L.VbsError(f"vbs_cross_moments_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
+    return nv
+
+
+def cross_moments_f64(rec, shift=None, n_values=None, device=None):
+    """The cross moments of all pairs of series (`vbs_cross_moments_f64`), a symmetric float64 matrix product over the time axis.
+    rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default
+    min(cols - 1, 3)).  `shift` float64 [s, n_values] (default none) is subtracted from every valid value first: pass the series'
+    means.  Returns float64 [s, s, 4, 4]: [i, j, v, w] the sum over the frames of col_v(i) col_w(j), the columns of a slot being its
+    shifted values (0 beyond n_values) and its flag as 1.0 / 0.0, all 0 where the slot is invalid - so [.., 3, 3] is the number
+    of frames where both slots are valid and row / column 3 the sums pairwise-complete centring needs."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    sh = None if shift is None else torch.as_tensor(shift, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    nv = _moments_args(n, s, cols, None if sh is None else sh.shape, n_values)
+    out = torch.empty((s, s, 4, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_cross_moments_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(sh), _ptr(out),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_cross_moments_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_cross_moments_f64 failed ({rc})")
+    return out
+
+
+_COV_MODES = {"pairwise": 0, "filled": 1, 0: 0, 1: 1}
+
+
+def _covariance_args(mom_shape, n_values, mode, min_count, denom, mask_shape):
+    """`covariance_f64`'s argument checks (no device needed): -> (s, n_values, mode, min_count, denom) or ValueError / VbsError."""
+    ms = tuple(mom_shape)
+    if len(ms) != 4 or ms[0] < 1 or ms[0] != ms[1] or ms[2:] != (4, 4):
+        raise ValueError("mom must be [s >= 1, s, 4, 4] (`cross_moments_f64`)")
+    nv = int(n_values)
+    if not (1 <= nv <= 3):
+        raise ValueError("n_values must be 1 .. 3")
+    if mode not in _COV_MODES:
+        raise ValueError("mode must be 'pairwise' (0) or 'filled' (1)")
+    m, mc = _COV_MODES[mode], int(min_count)
+    if mc < 2:
+        raise ValueError("min_count must be >= 2")
+    d = 1.0 if denom is None else float(denom)
+    if m == 1 and (denom is None or not (np.isfinite(d) and d > 0.0)):
+        raise ValueError("mode 'filled' needs a finite denom > 0 (n - 1)")
+    if mask_shape is not None and tuple(mask_shape) != (ms[0],):
+        raise ValueError(f"slot_mask must be [{ms[0]}]")
+    if ms[0] > L.MOM_MAX_SLOTS:
+        raise L.VbsError(f"vbs_covariance_f64: {ms[0]} slots exceed VBS_MOM_MAX_SLOTS = {L.MOM_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
+    return ms[0], nv, m, mc, d
+
+
+def covariance_f64(mom, n_values, mode="filled", min_count=2, denom=None, slot_mask=None, want_ok=False, device=None):
+    """The covariance of all pairs of value columns from their cross moments (`vbs_covariance_f64`).  mom float64 [s, s, 4, 4] as
+    `cross_moments_f64` returns it.  mode 'pairwise': every pair over the frames where both are valid, unbiased, possibly
+    indefinite; 'filled': the Gram matrix of the data with gaps filled by the series' means over `denom` (n - 1), positive
+    semidefinite while no pair falls below `min_count`.  A pair with fewer than `min_count` common frames, or with a slot whose `slot_mask` (uint8 [s]) is 0, gives exact
+    zeros.  Returns float64 [C, C], C = s n_values, column c = i n_values + v; with `want_ok` also the uint8 [s, s] pair flags."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    m = torch.as_tensor(mom, dtype=torch.float64, device=dev).contiguous()
+    mk = None if slot_mask is None else torch.as_tensor(slot_mask, device=dev).to(torch.uint8).contiguous()
+    s, nv, md, mc, d = _covariance_args(m.shape, n_values, mode, min_count, denom, None if mk is None else mk.shape)
+    cov = torch.empty((s * nv, s * nv), dtype=torch.float64, device=dev)
+    ok = torch.empty((s, s), dtype=torch.uint8, device=dev) if want_ok else None
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_covariance_f64(dev.index, _ptr(m), s, nv, md, mc, d, _ptr(mk), _ptr(cov), _ptr(ok),
+                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_covariance_f64: bad argument (mode 0 or 1, min_count >= 2, denom > 0)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_covariance_f64 failed ({rc})")
+    return (cov, ok) if want_ok else cov
+
+
+def _modes_args(a_shape, r, iters, tiny):
+    """`leading_modes_f64`'s argument checks (no device needed): -> (C, r, iters, tiny) or ValueError / VbsError."""
+    sh = tuple(a_shape)
+    if len(sh) != 2 or sh[0] < 1 or sh[0] != sh[1]:
+        raise ValueError("A must be [C >= 1, C], symmetric")
+    Cn, r, it, tn = sh[0], int(r), int(iters), float(tiny)
+    if not (1 <= r <= min(Cn, L.MODES_MAX)):
+        raise ValueError(f"n_modes must lie in 1 .. min(C, VBS_MODES_MAX = {L.MODES_MAX})")
+    if not (0 <= it <= L.MODES_MAX_ITERS):
+        raise ValueError(f"iters must lie in 0 .. {L.MODES_MAX_ITERS}")
+    if not (0.0 <= tn < 1.0):
+        raise ValueError("tiny must lie in [0, 1)")
+    if Cn > L.MODES_MAX_DIM:
+        raise L.VbsError(f"vbs_leading_modes_f64: {Cn} columns exceed VBS_MODES_MAX_DIM = {L.MODES_MAX_DIM} (status {L.VBS_ECAPACITY})")
+    return Cn, r, it, tn
+
+
+def leading_modes_f64(A, n_modes, iters=48, tiny=1e-24, work=None, device=None):
+    """The `n_modes` <= 16 leading eigenpairs of a symmetric float64 [C, C] matrix (`vbs_leading_modes_f64`) by orthogonal
+    iteration from a fixed start block with a FIXED number of iterations: deterministic, nothing is tested for convergence, and
+    `resid` says what was reached.  The iteration finds the largest |lambda| (an indefinite A may give negative values); the
+    values come descending.  A column whose squared norm falls below `tiny` times the largest is dropped (a rank-deficient A).
+    `work`: an optional float64 device tensor of 2 * C * 16 elements to reuse.  Returns `(values [r], modes [r, C], resid [r],
+    info int32 [2] = rank found, columns dropped)`: every mode has unit norm and its entry of largest magnitude positive."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    a = torch.as_tensor(A, dtype=torch.float64, device=dev).contiguous()
+    Cn, r, it, tn = _modes_args(a.shape, n_modes, iters, tiny)
+    if work is None:
+        work = torch.empty((2 * Cn * L.MODES_MAX,), dtype=torch.float64, device=dev)
+    elif work.dtype != torch.float64 or work.device != dev or not work.is_contiguous() or work.numel() < 2 * Cn * L.MODES_MAX:
+        raise ValueError(f"work must be a contiguous float64 tensor of 2 * C * {L.MODES_MAX} elements on {dev}")
+    values = torch.empty((r,), dtype=torch.float64, device=dev)
+    modes = torch.empty((r, Cn), dtype=torch.float64, device=dev)
+    resid = torch.empty((r,), dtype=torch.float64, device=dev)
+    info = torch.empty((2,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_leading_modes_f64(dev.index, _ptr(a), Cn, r, it, tn, _ptr(work), _ptr(values), _ptr(modes), _ptr(resid),
+                                           _ptr(info), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_leading_modes_f64: bad argument (1 <= r <= min(C, 16), iters >= 0, 0 <= tiny < 1)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_leading_modes_f64 failed ({rc})")
+    return values, modes, resid, info
+
+
+def _scores_args(n, s, cols, center_shape, modes_shape, n_values, min_coverage, frame_range):
+    """`mode_scores_f64`'s argument checks (no device needed): -> (n_values, r, min_coverage, a, b) or ValueError / VbsError."""
+    nv = _moments_args(n, s, cols, None, n_values)
+    Cn = s * nv
+    ms = tuple(modes_shape)
+    if len(ms) != 2 or not (1 <= ms[0] <= L.MODES_MAX) or ms[1] != Cn:
+        raise ValueError(f"modes must be [1 .. {L.MODES_MAX}, {Cn}] (`leading_modes_f64`)")
+    if tuple(center_shape) != (Cn,):
+        raise ValueError(f"center must be [{Cn}]: one value per value column of rec")
+    mc = float(min_coverage)
+    if not (0.0 < mc <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    return nv, int(ms[0]), mc, a, b
+
+
+def mode_scores_f64(rec, center, modes, n_values=None, min_coverage=0.5, frame_range=None, want_energy=True, device=None):
+    """The score of every mode in every frame (`vbs_mode_scores_f64`): the least-squares amplitude of the mode over the columns
+    that are valid in the frame.  rec float64 [n, s, cols]; center float64 [s n_values] (what the covariance was centred on);
+    modes float64 [r, s n_values], unit norm.  Returns `(scores, energy)` for the frames [a, b) of `frame_range`: scores float64
+    [b-a, r, 3] = flag, score, den - den the share of the mode that was seen, flag 1 where it reaches `min_coverage`, else
+    (0, 0, den) - a record every series entry takes (cols 3, n_values 1, s = r); energy float64 [b-a, 2] = the number of valid
+    columns and the sum of their squared centred values (None without `want_energy`)."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r_ = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    c = torch.as_tensor(center, dtype=torch.float64, device=dev).contiguous()
+    m = torch.as_tensor(modes, dtype=torch.float64, device=dev).contiguous()
+    if r_.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r_.shape
+    nv, r, mc, a, b = _scores_args(n, s, cols, c.shape, m.shape, n_values, min_coverage, frame_range)
+    scores = torch.empty((b - a, r, 3), dtype=torch.float64, device=dev)
+    energy = torch.empty((b - a, 2), dtype=torch.float64, device=dev) if want_energy else None
+    if a == b:
+        return scores, energy
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_mode_scores_f64(dev.index, _ptr(r_), n, s, cols, nv, _ptr(c), _ptr(m), r, mc, a, b, _ptr(scores), _ptr(energy),
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_mode_scores_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8, min_coverage in (0, 1])")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_mode_scores_f64 failed ({rc})")
+    return scores, energy
+
+
 # ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
 def _steps_call(name, what, fn):
     rc = fn()

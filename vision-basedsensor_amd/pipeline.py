@@ -886,6 +886,116 @@ def to_envelope_frame(result, ids=None, fps=None, path=None):
     return df
 
 
+# ---- principal modes of the displacement field (k_modes.hip): which patterns a recording consists of ----------------------------
+MODE_FRAME_COLUMNS = ("frameno", "mode", "flag", "score", "coverage", "value", "explained")
+
+
+def _modal_args(n, m, n_modes, iters, mode, ref_frame, slot_mask, min_coverage):
+    """`modal_analysis`'s argument checks (no device needed): -> (n_modes, iters, slot indices or None)."""
+    from .engine import _COV_MODES
+    r, it = int(n_modes), int(iters)
+    if n < 2:
+        raise ValueError("a covariance needs at least 2 frames")
+    if not (1 <= r <= min(3 * m, L.MODES_MAX)):
+        raise ValueError(f"n_modes must lie in 1 .. min(3 M, VBS_MODES_MAX = {L.MODES_MAX})")
+    if not (0 <= it <= L.MODES_MAX_ITERS):
+        raise ValueError(f"iters must lie in 0 .. {L.MODES_MAX_ITERS}")
+    if mode not in _COV_MODES:
+        raise ValueError("mode must be 'filled' or 'pairwise'")
+    if not (0 <= int(ref_frame) < n):
+        raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+    if not (0.0 < float(min_coverage) <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    slots = None
+    if slot_mask is not None:
+        k = np.asarray(slot_mask)
+        if k.shape != (m,):
+            raise ValueError(f"slot_mask must be [{m}]: nonzero = the slot takes part")
+        slots = np.nonzero(k)[0]
+    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", m, "VBS_MOM_MAX_SLOTS", L.MOM_MAX_SLOTS)):
+        if got > cap:                                             # after the arguments, as the entries decide it
+            raise L.VbsError(f"modal_analysis: the table's {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
+    return r, it, slots
+
+
+def modal_analysis(eng: Engine, table: torch.Tensor, n_modes=6, iters=48, mode="filled", ref_frame=0, slot_mask=None,
+                   min_coverage=0.5, taps=None, grid=None):
+    """Which spatial patterns of marker displacement a recording consists of, how much of the variance each carries and how each
+    evolves along time (PCA with gaps; the reference ships no code for it) from a table [N, M, 10]:
+    `Engine.axis_displacement` against `ref_frame` (`slot_mask` [M]: nonzero = the slot takes part), the means of every series as
+    the shift, then `cross_moments_f64`, `covariance_f64` (`mode` 'filled': positive semidefinite, biased by the share of gaps;
+    'pairwise': unbiased pair by pair, possibly indefinite), `leading_modes_f64` (`n_modes` <= 16, a fixed `iters`) and
+    `mode_scores_f64`.  Returns a dict.  Device tensors (float64): `series` [N, M, 4], `cov` [3 M, 3 M], `scores` [N, r, 3] = flag,
+    score, coverage (a record of r series: the entries for filtering, despiking, spectra and steps take it), `energy` [N, 2].
+    Host arrays: `values` [r], `explained`, `cumulative` [r] (shares of the trace), `modes` [r, M, 3] (unit norm, the largest
+    entry positive), `resid` [r] = |A u - lambda u| (the convergence reached: compare with `values`), `info` = rank found, columns
+    dropped, `center` [M, 3], `reconstructed` [N] = the share of the frame's energy the flagged modes carry (NaN for an empty
+    frame), `loners` [M] = the share of every slot's variance outside the leading subspace and `loner_order`.  With `taps`:
+    `scores_trend` = `fir_series_f64` of the scores.  With `grid` = (weights [P, M], wsum [P]): `mode_maps` [r, P, 4] =
+    `field_map_f64` of `modes.mode_record`."""
+    from . import modes as MD
+    from .engine import covariance_f64, cross_moments_f64, field_map_f64, fir_series_f64, leading_modes_f64, mode_scores_f64
+    n, m = int(table.shape[0]), int(table.shape[1])
+    r, it, slots = _modal_args(n, m, n_modes, iters, mode, ref_frame, slot_mask, min_coverage)
+    dev = eng.device.index
+    ax_rec, _ = eng.axis_displacement(table, ref_frame, slots)
+    rec = ax_rec[..., :4].contiguous()
+    valid = rec[..., :1] != 0.0
+    cnt = valid.sum(dim=0).to(torch.float64)                                                   # [M, 1]
+    tot = torch.where(valid, rec[..., 1:], torch.zeros((), dtype=torch.float64, device=rec.device)).sum(dim=0)
+    shift = torch.where(cnt > 0, tot / cnt.clamp(min=1.0), torch.zeros_like(tot))              # [M, 3]
+    mom = cross_moments_f64(rec, shift, 3, device=dev)
+    mask = None if slots is None else torch.as_tensor(np.asarray(slot_mask) != 0, device=eng.device).to(torch.uint8)
+    cov = covariance_f64(mom, 3, mode, 2, float(n - 1), mask, device=dev)
+    values, md, resid, info = leading_modes_f64(cov, r, it, device=dev)
+    diag = torch.diagonal(mom, dim1=0, dim2=1).permute(2, 0, 1)                                # [M, 4, 4]
+    nn = diag[:, 3, 3:4]
+    center = shift + torch.where(nn > 0, diag[:, :3, 3] / nn.clamp(min=1.0), torch.zeros_like(shift))
+    scores, energy = mode_scores_f64(rec, center.reshape(-1), md, 3, min_coverage, device=dev)
+    cov_h, md_h, val_h = cov.cpu().numpy(), md.cpu().numpy(), values.cpu().numpy()
+    share, cum = MD.explained(val_h, cov_h)
+    sc_h, en_h = scores.cpu().numpy(), energy.cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recon = np.where(en_h[:, 1] > 0.0, (sc_h[..., 0] * sc_h[..., 1] ** 2 * sc_h[..., 2]).sum(axis=1) / en_h[:, 1], np.nan)
+    loners, order = MD.loner_slots(cov_h, md_h, val_h, 3)
+    out = {"series": rec, "cov": cov, "scores": scores, "energy": energy, "values": val_h, "explained": share, "cumulative": cum,
+           "modes": md_h.reshape(r, m, 3), "resid": resid.cpu().numpy(), "info": info.cpu().numpy(), "center": center.cpu().numpy(),
+           "reconstructed": recon, "loners": loners, "loner_order": order}
+    if taps is not None:
+        out["scores_trend"] = fir_series_f64(scores, taps, 1, device=dev)
+    if grid is not None:
+        Wg, wsum = grid
+        mrec = torch.from_numpy(MD.mode_record(md_h, m, 3, None if slot_mask is None else np.asarray(slot_mask))).to(eng.device)
+        out["mode_maps"] = field_map_f64(mrec, torch.as_tensor(Wg, dtype=torch.float64, device=eng.device),
+                                         torch.as_tensor(wsum, dtype=torch.float64, device=eng.device), min_coverage, 3, device=dev)
+    return out
+
+
+def to_mode_frame(result, frame_offset=0, path=None):
+    """The long sheet of `modal_analysis`: one row `MODE_FRAME_COLUMNS` per frame and mode (frame-major) from its `scores`
+    [N, r, 3]; `frameno` counts from 1 + `frame_offset`, `mode` from 1; `value` and `explained` repeat the mode's eigenvalue and
+    share; score is NaN (an empty cell) where the mode was not seen enough.  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    sc = result["scores"]
+    sc = np.asarray(sc.cpu().numpy() if hasattr(sc, "cpu") else sc, dtype=np.float64)
+    val, ex = np.asarray(result["values"], dtype=np.float64), np.asarray(result["explained"], dtype=np.float64)
+    if sc.ndim != 3 or sc.shape[2] != 3 or val.shape != (sc.shape[1],) or ex.shape != val.shape:
+        raise ValueError("scores must be [N, r, 3], values and explained [r]")
+    N, r = sc.shape[:2]
+    flag = sc[..., 0] != 0.0
+    df = pd.DataFrame({"frameno": np.repeat(np.arange(1, N + 1, dtype=np.int64) + int(frame_offset), r),
+                       "mode": np.tile(np.arange(1, r + 1, dtype=np.int64), N), "flag": flag.reshape(-1).astype(np.int64),
+                       "score": np.where(flag, sc[..., 1], np.nan).reshape(-1), "coverage": sc[..., 2].reshape(-1),
+                       "value": np.tile(val, N), "explained": np.tile(ex, N)})
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- the probe-indentation validation (k_steps.hip): the reference's Figure 6(b) from a tracked table -------------------------
 @dataclass
 class IndentationResult:
