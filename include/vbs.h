@@ -241,6 +241,12 @@ int64_t vbs_format_csv(const int64_t* frameno, const int64_t* row, const int64_t
  * (_gkern :138-143, _normxcorr2 :152,162). */
 int vbs_gaussian_taps_q8(int ksize, double sigma, int32_t* out);
 int vbs_ncc_template(int l, double sigma, double* g, double* stats);
+/* host-only: may the NCC kernel skip windows that hold no area pixel?  Such a window is background as long as
+ * d0 = (template mass) - (samples) * mean(t) of its in-image part is not negative; -> 1 if the minimum of d0 over every
+ * window cut of a height x width frame lies above -5e-5 (half of what the kernel's own decision allows), else 0
+ * (vbs_create then leaves the kernel as it was for that handle); the minimum goes to *min_d0 if given.  tbar_shift is
+ * added to mean(t): 0 for the library's own use, anything else only shows the check failing. */
+int vbs_ncc_trim_guard(int l, double sigma, int height, int width, double tbar_shift, double* min_d0);
 
 /* MarkerTracker._undistort_frame (marker_detection.py:93-109), optional (`calibration_params` in the config):
  * getOptimalNewCameraMatrix(K, D, (w,h), 0) + initUndistortRectifyMap(CV_16SC2) are evaluated ONCE here (the

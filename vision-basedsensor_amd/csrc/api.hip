@@ -106,6 +106,42 @@ extern "C" int vbs_ncc_template(int l, double sigma, double* g, double* stats) {
     return VBS_OK;
 }
 
+// The empty-window bound behind k_ncc_mfma's pre-scan.  A window without an area pixel has G = 0 and c = 0, so
+// num = -mu (sum_t - n tbar) with sum_t the template mass and n the sample count of the window's in-image part: it is
+// background whatever the frame's mean mu >= 0 as long as d0 = sum_t - n tbar >= 0, and the kernel's border tiles decide it
+// so without the exact path for d0 > -1e-4.  -> the minimum of d0 over every cut a height x width frame can produce (row cuts
+// x column cuts; rows / columns with the same cut share their sums, so the first and last l of each suffice), in float64
+// with the sums formed as vbs_create forms ncc_ry / ncc_rx.  `tbar_shift` is added to the template mean (tests).
+static double ncc_trim_guard(const NccConst& nc, int l, int height, int width, double tbar_shift) {
+    const int lo = -((l - 1) - (l - 1) / 2);
+    auto cuts = [&](int size) {
+        std::vector<std::pair<int, double>> out;
+        for (int p = 0; p < size; ++p) {
+            if (p == l && size - l > l) p = size - l;   // (the positions between have the whole window, as position l - 1 has)
+            double s = 0;
+            int cnt = 0;
+            for (int j = 0; j < l; ++j) { const int pp = p + lo + j; if (pp >= 0 && pp < size) { s += nc.g[j]; ++cnt; } }
+            out.emplace_back(cnt, s);
+        }
+        return out;
+    };
+    const auto rows = cuts(height), cols = cuts(width);
+    double mn = 1e300;
+    for (const auto& r : rows)
+        for (const auto& c : cols) mn = std::min(mn, r.second * c.second - (double)(r.first * c.first) * (nc.tbar + tbar_shift));
+    return mn;
+}
+static constexpr double NCC_TRIM_SLACK = -5e-5;         // half of the -1e-4 the kernel's border decision allows
+
+extern "C" int vbs_ncc_trim_guard(int l, double sigma, int height, int width, double tbar_shift, double* min_d0) {
+    if (l < 2 || l > VBS_NCC_MAXL || !(sigma > 0) || height < 1 || width < 1) return VBS_EINVAL;
+    NccConst nc;
+    ncc_consts(l, sigma, &nc);
+    const double mn = ncc_trim_guard(nc, l, height, width, tbar_shift);
+    if (min_d0) *min_d0 = mn;
+    return mn > NCC_TRIM_SLACK ? 1 : 0;
+}
+
 extern "C" int vbs_destroy(vbs_handle* h) {
     if (!h) return VBS_EINVAL;
     (void)hipSetDevice(h->device);
@@ -233,6 +269,8 @@ extern "C" int vbs_create(int device, int height, int width, int max_markers, in
         }
         HIPCHK(h, hipMemcpy(h->ncc_rowf, rowf.data(), height * sizeof(float2), hipMemcpyHostToDevice));
     }
+    // k_ncc_mfma may skip the strips and rows whose windows are empty only where such a window is background for certain
+    h->ncc_trim_ok = ncc_trim_guard(h->ncc, bp.ncc_l, height, width, 0.0) > NCC_TRIM_SLACK;
     HIPCHK(h, hipMemcpy(h->ncc_tab, h->ncc.g, VBS_NCC_MAXL * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->ncc_tab + VBS_NCC_MAXL, h->ncc.cg, (VBS_NCC_MAXL + 1) * sizeof(double), hipMemcpyHostToDevice));
     {

@@ -98,6 +98,7 @@ struct vbs_handle {
     double* ncc_ry;    // [H]
     uint4* ncc_frags;  // Toeplitz operand fragments of k_ncc_mfma (ncc_mfma_fragments)
     float2* ncc_rowf;  // [H] {rows of the NCC window inside the image, (float) ncc_ry}: border tiles of k_ncc_mfma
+    bool ncc_trim_ok = false;   // an empty NCC window is background for every window cut of this frame size (ncc_trim_guard): k_ncc_mfma may skip them
     double* ncc_tab;   // [VBS_NCC_MAXL] g, then [VBS_NCC_MAXL + 1] cg: the exact path of k_ncc_mfma reads them from memory
     u8* lut;           // [256] contour vertex table
     u32* step_lut = nullptr;   // [256] outgoing chain steps of a border pixel (make_step_lut, k_diameter.hip)

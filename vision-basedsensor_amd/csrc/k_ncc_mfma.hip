@@ -38,6 +38,8 @@
 // three float32 operations per pixel (c (l^2 - c) < 2^24 is exact).  An empty window has G = 0 exactly on both
 // paths and var = 0 up to rounding: its decision is taken once per wave with the float64 formula.  Border tiles
 // (windows that leave the image) evaluate theta per pixel in float64.
+// Before its loop a wave looks which rows of its window hold an area pixel at all and runs only the tiles whose windows
+// reach one (the pre-scan in the prologue, NCC_TRIM_BIT): the rest is background without a product.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(256, 4) void k_ncc_mfma(const u64* __restrict__ bit
                                                      int tiles_per_seg,
                                                      int dbg_arg, float rel_arg, NccConst nc) {
 #ifdef VBS_DEBUG_KNOBS
-    const int dbg = dbg_arg;                            // tools/ phase timing and dumps
+    const int dbg = dbg_arg & (NCC_TRIM_BIT - 1);       // tools/ phase timing and dumps
 #else
     constexpr int dbg = 0;
 #endif
@@ -105,9 +107,9 @@ __global__ __launch_bounds__(256, 4) void k_ncc_mfma(const u64* __restrict__ bit
     const int n = blockIdx.z;
     const int tilesY = (H + 15) / 16;
     const int tile0 = blockIdx.y * tiles_per_seg;
-    const int ntiles = min(tiles_per_seg, tilesY - tile0);
+    int ntiles = min(tiles_per_seg, tilesY - tile0);
     if (ntiles <= 0) return;
-    const int Y0 = tile0 * 16, nsteps = ntiles + NT - 1;
+    int Y0 = tile0 * 16;
     const int xw = blockIdx.x * 64 + 16 * wave;         // first column of this wave's strip
     const u64* fbits = bits + (int64_t)n * H * WW;
     {
@@ -116,23 +118,88 @@ __global__ __launch_bounds__(256, 4) void k_ncc_mfma(const u64* __restrict__ bit
         for (int d = 0; d < 4; ++d) w[d] = (((u32)tid >> (2 * d)) & 1u ? 0x3C00u : 0u) | (((u32)tid >> (2 * d + 1)) & 1u ? 0x3C000000u : 0u);
         sm.lut[tid] = make_uint4(w[0], w[1], w[2], w[3]);
     }
-    for (int i = lane; i < 2 * 16 * RSTR / 8; i += 64) reinterpret_cast<uint4*>(&sm.ring[wave][0][0])[i] = make_uint4(0, 0, 0, 0);
-    for (int i = lane; i < 16 * CSTR / 16; i += 64) reinterpret_cast<uint4*>(&sm.ringc[wave][0])[i] = make_uint4(0, 0, 0, 0);
-    h8 whi[NKS], wlo[NKS], one[NKS];
+    // ---- pre-scan (NCC_TRIM_BIT): which rows of this wave's window hold an area pixel at all ----
+    // An output row y can be foreground only if one of the rows y + LO .. y + HI has a set bit among the 16 + L - 1 columns
+    // the strip's windows cover: with none, every window of the row is empty (c = 0, G = 0 exactly), and an empty window is
+    // background on both decision paths - plain tiles have u = 0, border tiles dd0 > -1e-4 (the host has checked the bound
+    // in float64 for every window cut of this frame size before it set the bit: ncc_trim_guard).  So the wave reads the bits
+    // its horizontal products would read - one lane per row, the loads of four 64-row chunks in flight together - and runs
+    // its 16-row steps only over the tiles whose windows reach an occupied row.  The rest of its segment is stored as zeros
+    // here (the workspace keeps the previous pass's masks), and a wave that finds nothing skips the ring, the fragments and
+    // the loop.  Only Y0 / ntiles change: the step loop below is the one it was.
+    if (dbg_arg & NCC_TRIM_BIT) {
+        const int seg_y0 = Y0, seg_y1 = min(Y0 + 16 * ntiles, H);                       // the segment's rows [seg_y0, seg_y1)
+        const int r0 = max(Y0 + LO, 0), r1 = min(Y0 + 16 * ntiles - 1 + HI, H - 1);     // rows the horizontal tiles read
+        const int pws = xw + LO, pb0 = pws >> 3;
+        const bool pwide = (pb0 >= 0) && ((pb0 & ~3) + 16 <= 8 * WW);                   // (uniform; as `wide` below)
+        constexpr int NB = 16 + L - 1;                                                  // columns of the strip's windows
+        int first = 0x7FFFFFFF, last = -1;
+        for (int base = r0; base <= r1; base += 256) {
+            u64 w0[4], w1[4];
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-        uint4 a = wfrag[(0 * NKS + s) * 64 + lane], b = wfrag[(1 * NKS + s) * 64 + lane], c = wfrag[(2 * NKS + s) * 64 + lane];
-        whi[s] = __builtin_bit_cast(h8, a);
-        wlo[s] = __builtin_bit_cast(h8, b);
-        one[s] = __builtin_bit_cast(h8, c);
+            for (int k = 0; k < 4; ++k) {
+                const int row = min(base + 64 * k + lane, r1);                          // (lanes past the end repeat row r1)
+                if (pwide) {
+                    const uint4 rr = *reinterpret_cast<const uint4*>(reinterpret_cast<const u8*>(fbits) + (pb0 & ~3) + (int64_t)row * (8 * WW));
+                    const u64 lo64 = (u64)rr.x | ((u64)rr.y << 32), hi64 = (u64)rr.z | ((u64)rr.w << 32);
+                    const int sh = 8 * (pb0 & 3);
+                    w0[k] = sh ? (lo64 >> sh) | (hi64 << (64 - sh)) : lo64;
+                    w1[k] = hi64 >> sh;
+                } else {
+                    const u64* prow = fbits + (int64_t)row * WW;
+                    w0[k] = load_bits(prow, WW, pws);
+                    w1[k] = NB > 64 ? load_bits(prow, WW, pws + 64) : 0ull;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const u64 v0 = NB >= 64 ? w0[k] : w0[k] & ((1ull << (NB & 63)) - 1ull);
+                const u64 v1 = NB > 64 ? w1[k] & ((1ull << ((NB - 64) & 63)) - 1ull) : 0ull;
+                const u64 occ = __ballot((v0 | v1) != 0ull);                            // bit = lane = row base + 64 k + lane
+                if (occ) {
+                    first = min(first, min(base + 64 * k + (int)__builtin_ctzll(occ), r1));
+                    last = max(last, min(base + 64 * k + 63 - (int)__builtin_clzll(occ), r1));
+                }
+            }
+        }
+        int ta = tile0;
+        if (last >= 0) {                                 // output rows first - HI .. last - LO, cut to the segment, as whole tiles
+            const int tb = min(Y0 + 16 * ntiles - 1, last - LO) >> 4;
+            ta = max(Y0, first - HI) >> 4;
+            ntiles = tb - ta + 1;
+        } else {
+            ntiles = 0;
+        }
+        Y0 = 16 * __builtin_amdgcn_readfirstlane(ta);    // (uniform, and a multiple of 16 the compiler can see)
+        ntiles = __builtin_amdgcn_readfirstlane(ntiles);
+        u8* zb = reinterpret_cast<u8*>(reinterpret_cast<unsigned short*>(mbits) + ((int64_t)n * H * WW + blockIdx.x) * 4 + wave);
+        for (int y = seg_y0 + lane; y < seg_y1; y += 64)
+            if (y < Y0 || y >= Y0 + 16 * ntiles) *reinterpret_cast<unsigned short*>(zb + (int64_t)y * (8 * WW)) = 0;
+        if (U8OUT) {
+            for (int y = seg_y0 + g; y < seg_y1; y += 4)
+                if ((y < Y0 || y >= Y0 + 16 * ntiles) && xw + q < W) mask_u8[((int64_t)n * H + y) * W + xw + q] = 0;
+        }
     }
-    // int8 Toeplitz of ones (A operand of the vertical count product): lane (g, row q), byte j <-> k = 64 s + 16 g + j
-    // (from the fragment table as well: built here it cost 250 vector instructions per wave)
+    const int nsteps = ntiles > 0 ? ntiles + NT - 1 : 0;
+    h8 whi[NKS], wlo[NKS], one[NKS];
     i4 one8[NK8];
+    if (nsteps) {                                        // (uniform)
+        for (int i = lane; i < 2 * 16 * RSTR / 8; i += 64) reinterpret_cast<uint4*>(&sm.ring[wave][0][0])[i] = make_uint4(0, 0, 0, 0);
+        for (int i = lane; i < 16 * CSTR / 16; i += 64) reinterpret_cast<uint4*>(&sm.ringc[wave][0])[i] = make_uint4(0, 0, 0, 0);
 #pragma unroll
-    for (int s = 0; s < NK8; ++s) {
-        const uint4 a = wfrag[(3 * NKS + s) * 64 + lane];
-        one8[s] = i4{(int)a.x, (int)a.y, (int)a.z, (int)a.w};
+        for (int s = 0; s < NKS; ++s) {
+            uint4 a = wfrag[(0 * NKS + s) * 64 + lane], b = wfrag[(1 * NKS + s) * 64 + lane], c = wfrag[(2 * NKS + s) * 64 + lane];
+            whi[s] = __builtin_bit_cast(h8, a);
+            wlo[s] = __builtin_bit_cast(h8, b);
+            one[s] = __builtin_bit_cast(h8, c);
+        }
+        // int8 Toeplitz of ones (A operand of the vertical count product): lane (g, row q), byte j <-> k = 64 s + 16 g + j
+        // (from the fragment table as well: built here it cost 250 vector instructions per wave)
+#pragma unroll
+        for (int s = 0; s < NK8; ++s) {
+            const uint4 a = wfrag[(3 * NKS + s) * 64 + lane];
+            one8[s] = i4{(int)a.x, (int)a.y, (int)a.z, (int)a.w};
+        }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                 // operand fragments landed (see k_blur_mfma)
     __syncthreads();
@@ -376,8 +443,10 @@ __global__ __launch_bounds__(256, 4) void k_ncc_mfma(const u64* __restrict__ bit
 #pragma unroll
         for (int s = 0; s < NKS; ++s) a_op[s] = __builtin_bit_cast(h8, sm.lut[by[s]]);
     };
-    load_rows(0);
-    fetch_ops(0);
+    if (nsteps) {                                        // (uniform: a wave with no occupied row has no loop to prime)
+        load_rows(0);
+        fetch_ops(0);
+    }
     for (int t0 = 0; t0 < nsteps; t0 += NT) {
 #pragma unroll
         for (int u = 0; u < NT; ++u) {                   // u = ring slot of step t: a constant of this copy of the body
@@ -673,11 +742,14 @@ void launch_ncc_mfma(vbs_handle* h, Workspace& w, int nb, u8* mask_u8, hipStream
     const int tps = (tilesY + nseg - 1) / nseg;
     nseg = (tilesY + tps - 1) / tps;
     dim3 grid(h->WW, nseg, nb);
+    // the pre-scan (NCC_TRIM_BIT) where vbs_create found an empty window background for every cut of this frame size; the
+    // tools' library keeps the untrimmed kernel under its phase knobs, and VBS_NCC_TRIM_OFF gives the tests the same to compare with
+    const int trim = (h->ncc_trim_ok && !VBS_KNOB("VBS_NCC_DBG") && !VBS_KNOB("VBS_NCC_TRIM_OFF")) ? NCC_TRIM_BIT : 0;
 #define NCC_GO(L_, LO_, U8)                                                                                      \
     VBS_LAUNCH(h, s, "k_ncc_mfma", (k_ncc_mfma<L_, LO_, U8>), grid, dim3(256), 0, s, w.area_bits, h->ncc_rx,     \
                h->ncc_ry, h->ncc_frags, h->ncc_tab, h->ncc_rowf, w.mask_bits, mask_u8, w.fstat, w.ncc_tot,       \
                h->H, h->W, h->WW, tps,                                                                           \
-               VBS_KNOB("VBS_NCC_DBG"), std::max(NCC_REL, 1e-6f * (float)h->ncc_margin_ppm), h->ncc)
+               VBS_KNOB("VBS_NCC_DBG") | trim, std::max(NCC_REL, 1e-6f * (float)h->ncc_margin_ppm), h->ncc)
     if (!h->bp.small) { if (mask_u8) NCC_GO(80, -40, true); else NCC_GO(80, -40, false); }
     else { if (mask_u8) NCC_GO(33, -16, true); else NCC_GO(33, -16, false); }
 #undef NCC_GO

@@ -52,6 +52,7 @@ __device__ __attribute__((noinline)) double ncc_exact_G(const u64* fbits, int H,
 #define NCC_WSCALE 1024.0                               // weights are scaled so that every wlo is a normal float16
 #define NCC_REL 2e-5f
 #define NCC_NEVER 3e38                                  // "no G reaches this" (finite, so G - theta stays ordered)
+#define NCC_TRIM_BIT 0x100                              // of k_ncc_mfma's dbg_arg: skip strips and rows whose windows are empty
 #define NCC_ABS 1e-3f                                   // in units of G * 2^20: far below any theta with c >= 1
 
 // theta on 2^20 G for a window with c foreground and nn in-image samples (+inf where var <= 0)
