@@ -1012,6 +1012,81 @@ int vbs_window_moments_f64(int device, const double* rec, int n, int s, int cols
 int vbs_window_fit_f64(int device, const double* mom, int F, int s, int n_values, double sw, double min_coverage, double det_min,
                        double* fit, void* stream);
 
+/* ---- Marker velocity, acceleration and gap filling along a recording (slip, approach speed, first contact and the direction
+ * reversal of Figure 11(b) are statements about rates; the reference ships no code for this) ----
+ * A gap-aware weighted local polynomial fit along time - Savitzky-Golay with the gaps selected out, one-sided at the ends of the
+ * recording - in two entries without a handle: the moments of every window, then a small kernel that turns them into the fit of
+ * every frame.  Its constant term is the smoothed position (the gap filler), its linear term the velocity, its quadratic term the
+ * acceleration.  Operator, scaling, fallback rule and every default are this project's.
+ *
+ * The taps.  h = n_half - 1 in 0 .. VBS_KIN_MAX_HALF, degree d in 0 .. VBS_KIN_MAX_DEGREE, H = the smallest power of two >=
+ * max(h, 1), u = delta / H (an exact scaling), w[delta] = half[|delta|] as for vbs_window_moments_f64 (finite, >= 0, centre > 0):
+ *     taps[k][delta] = w[delta] * u^k        k = 0 .. 2d, delta = -h .. h
+ * u^k by repeated multiplication, every product exact (|delta|^k < 2^42), so a tap is rounded ONCE (`filters.poly_taps`).
+ *
+ * vbs_poly_moments_f64 - rec [dev] float64 [n, s, cols], the record layout of vbs_fir_series_f64: col 0 the flag (nonzero =
+ * valid), cols 1 .. n_values the values, 1 <= n_values <= 3, n_values < cols <= 8; the values of VALID entries are finite with
+ * finite squares.  For every frame f of [frame_begin, frame_end) and every slot the sums run over the VALID frames j of
+ * [f - h, f + h] n [0, n), delta = j - f: M = (2d + 1) + (d + 2) n_values sums, in this column order:
+ *     S_k = sum taps[k][delta]                      k = 0 .. 2d
+ *     per value:   X_k = sum taps[k][delta] x_j     k = 0 .. d,     XX = sum taps[0][delta] (x_j x_j)
+ * the square rounded once when it is staged, no contraction.  mom [dev] float64 [frame_end - frame_begin, s, M].  Invalid entries
+ * and frames outside [0, n) are selected out before anything is computed from them, never multiplied by zero: they may hold NaN
+ * or 1e300, and so may every column beyond n_values.  A window with no valid frame gives exact zeros.  The call allocates nothing.
+ * The kernel is a banded float64 matrix product on v_mfma_f64_16x16x4_f64 with SEVERAL bands over ONE staged operand: B, staged
+ * once per input frame, is (valid, x1, x2, x3) of 4 slots a tile, their squares, and a tile of 16 slots' flags for the orders
+ * k > d; each tap row is its own Toeplitz A, A_k[r][j] = taps[k][j - r - h] inside the band and 0.0 outside (which is why a valid
+ * value must be finite with a finite square: 0.0 times it must be 0.0), each product into its own accumulator.  Frame tiles are
+ * aligned to multiples of VBS_KIN_TILE of the GLOBAL frame index, never to frame_begin.  No atomics.
+ * THE ORDER OF SUMMATION IS NOT PART OF THIS INTERFACE, as for vbs_window_moments_f64.  What is promised:
+ *   - exact where the inputs make every order exact: if every product and every partial sum is representable, every sum is exact;
+ *   - otherwise, with u = 2^-53, gamma_k = k u / (1 - k u), K = 2h + 1, every sum satisfies
+ *         |sum^ - sum| <= gamma_(K+8) sum |taps[k][delta] term|      (term = 1, x, x x; derived in DESIGN 4.20)
+ *     against the sum of the ROUNDED taps in exact arithmetic, for any order of summation, with or without fused multiply-add;
+ *   - bit-identical run to run, range by range (any frame_begin, frame_end) against the full call, a series alone against the same
+ *     series among s, with dead (invalid) slots appended and with dead frames appended at the end.
+ * A null pointer, n or s < 1, bad cols / n_values, n_half < 1 or h > VBS_KIN_MAX_HALF, degree outside 0 .. VBS_KIN_MAX_DEGREE, a
+ * negative or non-finite weight, a centre <= 0, a range outside 0 <= fb <= fe <= n: VBS_EINVAL; n > VBS_PROJ_MAX_FRAMES or s >
+ * VBS_PROJ_MAX_SLOTS: VBS_ECAPACITY; a bad argument comes before a capacity; all decided before the device is touched.  fb == fe
+ * emits nothing.
+ *
+ * vbs_poly_fit_f64 - mom [dev] float64 [F, s, M] as above for the frames [frame_begin, frame_end) of rec [dev] [n, s, cols] (read
+ * for the flag of the centre frame and, with `filled`, for the rows of valid entries); half_window = the h of the moments (it
+ * fixes H), thr HOST [d + 1], >= 0 and not NaN (+inf switches an order off: the caller's for k >= 2h + 1, which no window of 2h + 1
+ * frames determines): thr[0] = min_coverage * sw (sw the ascending sum of w), thr[k] = piv_rel *
+ * piv_full[k] (the pivots of the gap-free full window), each ONE IEEE product formed by the caller.  Per (frame, slot) the normal
+ * equations are the Hankel matrix G[a][b] = S_(a+b), factored G = L diag(D) L^T without a square root, column by column:
+ *     for j = 0 .. d:
+ *         t = S_(2j);        for m = 0 .. j-1 ascending:  t = t - V[j][m] * L[j][m];        D_j = t
+ *         for a = j+1 .. d:  t = S_(a+j);  for m = 0 .. j-1 ascending:  t = t - V[a][m] * L[j][m];   V[a][j] = t;  L[a][j] = t / D_j
+ * THE DEGREE USED q is the largest q <= d with D_k > thr[k] for ALL k <= q, -1 when there is none; a comparison with a NaN is
+ * false.  The leading block of the factorisation is the factorisation of the lower-degree problem, so the fallback is a shorter
+ * back substitution: a window across a gap degrades from cubic to line to mean instead of returning a wild curvature.  Per value:
+ *     for k = 0 .. d:        t = X_k;  for m = 0 .. k-1 ascending:  t = t - L[k][m] * z_m;    z_k = t;   g_k = z_k / D_k
+ *     for k = q down to 0:   t = g_k;  for m = k+1 .. q ascending:  t = t - L[m][k] * c_m;    c_k = t
+ *     y0 = c_0     y1 = c_1 / H     y2 = (2 * c_2) / (H * H)     y3 = (6 * c_3) / (H * H * H)       (0 for the orders above q)
+ *     rss = XX;    for k = 0 .. q ascending:  rss = rss - z_k * g_k
+ * y_k is the k-th derivative of the fitted polynomial at the window's centre in units of frames; g_k = z_k / D_k is the solution of
+ * the diagonal system (the "y" of L z = X, D y = z, L^T c = y), so rss is the weighted residual sum of squares of the degree-q
+ * fit, reported as computed: it may be a rounding below zero; with q = -1 it is XX.  EVERY EXPRESSION IS EVALUATED AS WRITTEN,
+ * FLOAT64 WITHOUT CONTRACTION, AND THAT IS PART OF THIS INTERFACE (a division by H is an exact scaling).
+ * fit [dev] float64 [F, s, 2 + (d + 2) n_values] = flag, q, then (y_0 .. y_d, rss) per value;
+ *     flag = (centre entry valid) + 2 (q >= 0) + 4 (q == d).
+ * filled [dev] float64 [F, s, cols] or NULL, as vbs_hampel_series_f64 writes `clean`: where the centre entry is valid the row of
+ * rec bit for bit; where it is missing and q >= fill_degree (0 <= fill_degree <= VBS_KIN_MAX_DEGREE; above d nothing is filled) flag 2.0, the values y0, 0.0 in the columns
+ * beyond n_values; otherwise all zeros.  Any flag != 0 is what every other entry reads as valid.  One thread per (frame, slot).
+ * A null pointer (filled excepted), n or s < 1, bad cols / n_values / degree / half_window / fill_degree, a thr that is negative
+ * or NaN, a range outside 0 <= fb <= fe <= n: VBS_EINVAL; n > VBS_PROJ_MAX_FRAMES or s > VBS_PROJ_MAX_SLOTS:
+ * VBS_ECAPACITY, after the arguments; before the device is touched. */
+#define VBS_KIN_TILE       64    /* frames a workgroup emits (no result depends on it)           */
+#define VBS_KIN_MAX_HALF   127   /* h at most: a window of 2h + 1 <= VBS_FIR_MAX_TAPS frames      */
+#define VBS_KIN_MAX_DEGREE 3     /* d at most                                                     */
+int vbs_poly_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half,
+                         int degree, int frame_begin, int frame_end, double* mom, void* stream);
+int vbs_poly_fit_f64(int device, const double* mom, const double* rec, int n, int s, int cols, int n_values, int degree,
+                     int half_window, const double* thr, int fill_degree, int frame_begin, int frame_end, double* fit,
+                     double* filled, void* stream);
+
 /* ---- Principal modes of the displacement field along a recording (the reference ships no code for this; every other analysis
  * here reduces the recording with a model chosen in advance) ----
  * Which spatial patterns of marker displacement a recording consists of, how much of the variance each carries and how each

@@ -18,6 +18,7 @@ FIELD_FRAMES, FIELD_MAX_SLOTS, FIELD_MAX_POINTS, PATCH_COLS, PATCH_GROUP = 4, 10
 PROJ_SLOTS, PROJ_CHUNK, PROJ_ROWS, PROJ_WG_SLOTS, PROJ_MAX_ROWS, PROJ_MAX_FRAMES, PROJ_MAX_SLOTS = 4, 64, 64, 16, 8192, 1048576, 1024
 FIT_GROUP, PEAK_COLS = 4, 7
 ENV_TILE, ENV_MAX_HALF = 64, 127
+KIN_TILE, KIN_MAX_HALF, KIN_MAX_DEGREE = 64, 127, 3
 MOM_CHUNK, MOM_WG_SLOTS, MOM_MAX_SLOTS = 32, 16, 1024
 MODES_MAX, MODES_MAX_DIM, MODES_SWEEPS, MODES_MAX_ITERS, SCORE_GROUP = 16, 3072, 10, 4096, 8
 STRAIN_COLS, LSTRAIN_COLS, MOTION_GROUP, LSTRAIN_GROUP, STRAIN_MAX_NBR = 16, 8, 8, 8, 12
@@ -44,6 +45,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_axis_displacement", "vbs_fir_series_f64",
            "vbs_step_response_f64", "vbs_find_steps_f64", "vbs_dwell_stats_f64", "vbs_pose_series",
            "vbs_field_map_f64", "vbs_patch_stats_f64", "vbs_project_series_f64", "vbs_harmonic_fit_f64", "vbs_window_moments_f64", "vbs_window_fit_f64",
+           "vbs_poly_moments_f64", "vbs_poly_fit_f64",
            "vbs_motion_series_f64", "vbs_local_strain_f64", "vbs_hampel_series_f64",
            "vbs_cross_moments_f64", "vbs_covariance_f64", "vbs_leading_modes_f64", "vbs_mode_scores_f64")
 
@@ -154,6 +156,8 @@ def lib():
         "vbs_harmonic_fit_f64": (i32, [i32, vp, i32, i32, i32, i32, i32, f64, vp, vp, vp]),
         "vbs_window_moments_f64": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]),
         "vbs_window_fit_f64": (i32, [i32, vp, i32, i32, i32, f64, f64, f64, vp, vp]),
+        "vbs_poly_moments_f64": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]),
+        "vbs_poly_fit_f64": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp]),
         "vbs_motion_series_f64": (i32, [i32, vp, i32, i32, i32, vp, vp, f64, i32, i32, vp, vp, vp, vp]),
         "vbs_local_strain_f64": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, f64, i32, i32, vp, vp]),
         "vbs_hampel_series_f64": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, f64, f64, i32, i32, vp, vp, vp]),

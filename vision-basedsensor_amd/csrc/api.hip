@@ -1112,6 +1112,40 @@ extern "C" int vbs_window_fit_f64(int device, const double* mom, int F, int s, i
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+// ---- marker velocity, acceleration and gap filling (k_kinematics.hip) ------------------------------------------------------------
+extern "C" int vbs_poly_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half,
+                                    int n_half, int degree, int frame_begin, int frame_end, double* mom, void* stream) {
+    if (!rec || !half || !mom || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 || n_values >= cols ||
+        n_half < 1 || n_half - 1 > VBS_KIN_MAX_HALF || degree < 0 || degree > VBS_KIN_MAX_DEGREE || frame_begin < 0 ||
+        frame_end > n || frame_begin > frame_end)
+        return VBS_EINVAL;
+    for (int i = 0; i < n_half; ++i)
+        if (!std::isfinite(half[i]) || !(half[i] >= 0.0)) return VBS_EINVAL;
+    if (!(half[0] > 0.0)) return VBS_EINVAL;
+    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_poly_moments(rec, n, s, cols, n_values, half, n_half, degree, frame_begin, frame_end, mom, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
+extern "C" int vbs_poly_fit_f64(int device, const double* mom, const double* rec, int n, int s, int cols, int n_values, int degree,
+                                int half_window, const double* thr, int fill_degree, int frame_begin, int frame_end, double* fit,
+                                double* filled, void* stream) {
+    if (!mom || !rec || !thr || !fit || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
+        n_values >= cols || degree < 0 || degree > VBS_KIN_MAX_DEGREE || half_window < 0 || half_window > VBS_KIN_MAX_HALF ||
+        fill_degree < 0 || fill_degree > VBS_KIN_MAX_DEGREE || frame_begin < 0 || frame_end > n || frame_begin > frame_end)
+        return VBS_EINVAL;
+    for (int k = 0; k <= degree; ++k)
+        if (!(thr[k] >= 0.0)) return VBS_EINVAL;                     // (a NaN fails it; +inf switches the order off)
+    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_poly_fit(mom, rec, s, cols, n_values, degree, half_window, thr, fill_degree, frame_begin, frame_end, fit, filled,
+                        (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 // ---- principal modes of the displacement field (k_modes.hip) ----------------------------------------------------------------------
 extern "C" int vbs_cross_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* shift,
                                      double* mom, void* stream) {

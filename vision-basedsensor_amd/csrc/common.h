@@ -270,6 +270,13 @@ void launch_hampel_series(const double* rec, int n, int s, int cols, int n_value
 void launch_window_moments(const double* rec, int n, int s, int cols, int n_values, const double* carrier, const double* half,
                            int n_half, int frame_begin, int frame_end, double* mom, hipStream_t st);
 void launch_window_fit(const double* mom, int F, int s, int n_values, double need, double det_min, double* fit, hipStream_t st);
+// k_kinematics.hip (f19): the moments of a gap-aware weighted local polynomial fit along time as several banded products over one
+// staged operand on the float64 matrix instruction, and the fit of every window with its fallback in degree
+void launch_poly_moments(const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half, int degree,
+                         int frame_begin, int frame_end, double* mom, hipStream_t st);
+void launch_poly_fit(const double* mom, const double* rec, int s, int cols, int n_values, int degree, int half_window,
+                     const double* thr, int fill_degree, int frame_begin, int frame_end, double* fit, double* filled,
+                     hipStream_t st);
 // k_modes.hip (f18): the cross moments of all pairs of series on the float64 matrix instruction, the covariance they give, its
 // leading eigenpairs by orthogonal iteration (apply, orthogonalise, Ritz step), and the score of every mode in every frame
 void launch_cross_moments(const double* rec, int n, int s, int cols, int n_values, const double* shift, double* mom, hipStream_t st);

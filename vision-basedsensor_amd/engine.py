@@ -1566,6 +1566,143 @@ def mode_scores_f64(rec, center, modes, n_values=None, min_coverage=0.5, frame_r
     return scores, energy
 
 
+# ---- marker velocity, acceleration and gap filling (k_kinematics.hip): the moments of a local polynomial fit, the fit -------------
+KIN_PIV_REL = 5e-3             # the default `piv_rel`: a gap-free one-sided window keeps its full degree (DESIGN 4.20's table)
+
+
+def n_kin_sums(degree, n_values):
+    """M of `poly_moments_f64`: (2d + 1) + (d + 2) n_values."""
+    return 2 * int(degree) + 1 + (int(degree) + 2) * int(n_values)
+
+
+def _kin_args(n, s, cols, half_window, degree, window, n_values, frame_range):
+    """`poly_moments_f64`'s argument checks (no device needed): -> (h, d, n_values, a, b) or ValueError."""
+    if n < 1 or s < 1 or not (2 <= cols <= 8):
+        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
+    nv = min(cols - 1, 3) if n_values is None else int(n_values)
+    if not (1 <= nv <= 3 and nv < cols):
+        raise ValueError("n_values must be 1 .. 3 and below cols")
+    h, d = int(half_window), int(degree)
+    if h != half_window or not (0 <= h <= L.KIN_MAX_HALF):
+        raise ValueError(f"half_window must be an integer in 0 .. VBS_KIN_MAX_HALF = {L.KIN_MAX_HALF}")
+    if d != degree or not (0 <= d <= L.KIN_MAX_DEGREE):
+        raise ValueError(f"degree must be an integer in 0 .. VBS_KIN_MAX_DEGREE = {L.KIN_MAX_DEGREE}")
+    if isinstance(window, str) and window not in ("hann", "rect"):
+        raise ValueError('window must be "hann", "rect" or 2 half_window + 1 weights')
+    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not (0 <= a <= b <= n):
+        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
+    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS)):
+        if got > cap:
+            raise L.VbsError(f"vbs_poly_moments_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
+    return h, d, nv, a, b
+
+
+def poly_moments_f64(rec, half_window, degree, window="hann", n_values=None, frame_range=None, device=None):
+    """The moments of a gap-aware weighted local polynomial fit along time for every frame and series (`vbs_poly_moments_f64`,
+    DESIGN 4.20): several banded float64 matrix products over one staged operand.  rec float64 [n, s, cols] (host or device): col
+    0 the flag (nonzero = valid), cols 1 .. n_values the values (default min(cols - 1, 3)).  The window is
+    `filters.poly_window(half_window, window)` ("hann", "rect" or 2h + 1 symmetric weights), the tap rows `filters.poly_taps(half_window, degree, window)`.  Returns float64
+    [b-a, s, (2d + 1) + (d + 2) n_values] = S_0 .. S_2d, then X_0 .. X_d, XX per value, over the valid frames of [f - h, f + h], for
+    the frames [a, b) of `frame_range` (default all); an output does not depend on the range it was asked in."""
+    from .filters import half_taps, poly_window
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    if r.dim() != 3:
+        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
+    n, s, cols = r.shape
+    h, d, nv, a, b = _kin_args(n, s, cols, half_window, degree, window, n_values, frame_range)
+    half = np.ascontiguousarray(half_taps(poly_window(h, window)), dtype=np.float64)
+    out = torch.empty((b - a, s, n_kin_sums(d, nv)), dtype=torch.float64, device=dev)
+    if a == b:
+        return out
+    with torch.cuda.device(dev):
+        rc = L.lib().vbs_poly_moments_f64(dev.index, _ptr(r), n, s, cols, nv, half.ctypes.data_as(C.c_void_p), half.size, d, a, b,
+                                          _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_poly_moments_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8, 0 <= degree <= 3)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_poly_moments_f64 failed ({rc})")
+    return out
+
+
+def kin_thresholds(sw, piv_full, min_coverage=0.5, piv_rel=KIN_PIV_REL, half_window=None):
+    """thr [d + 1] of `vbs_poly_fit_f64`: thr[0] = min_coverage * sw, thr[k] = piv_rel * piv_full[k], one IEEE product each; with
+    `half_window`, +inf for the orders k >= 2h + 1, which a window of 2h + 1 frames cannot determine (their full pivot is zero up
+    to rounding, and a rounding is not a pivot)."""
+    piv = np.asarray(piv_full, dtype=np.float64)
+    thr = np.float64(piv_rel) * piv
+    thr[0] = np.float64(min_coverage) * np.float64(sw)
+    if half_window is not None:
+        thr[2 * int(half_window) + 1:] = np.inf
+    return thr
+
+
+_KIN_PIVOTS = {}               # (h, d, window name) -> (sw, piv_full) of `filters.poly_taps`
+
+
+def _kin_fit_args(F, s, M, n, cols, half_window, degree, window, n_values, min_coverage, piv_rel, fill_degree, frame_range):
+    """`poly_fit_f64`'s argument checks (no device needed): -> (h, d, n_values, thr [d + 1], fill_degree, a, b) or ValueError."""
+    from .filters import poly_taps
+    h, d, nv, a, b = _kin_args(n, s, cols, half_window, degree, window, n_values, frame_range)
+    if (int(F), int(M)) != (b - a, n_kin_sums(d, nv)):
+        raise ValueError(f"mom must be [{b - a}, {s}, {n_kin_sums(d, nv)}]: the moments of the frames {a}:{b} at degree {d} "
+                         f"and {nv} values")
+    mc, pr = float(min_coverage), float(piv_rel)
+    if not (0.0 < mc <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    if not (0.0 <= pr < 1.0):
+        raise ValueError("piv_rel must lie in [0, 1)")
+    fd = int(fill_degree)
+    if fd != fill_degree or not (0 <= fd <= L.KIN_MAX_DEGREE):
+        raise ValueError(f"fill_degree must be an integer in 0 .. {L.KIN_MAX_DEGREE} (above `degree` nothing is filled)")
+    if isinstance(window, str):
+        if (h, d, window) not in _KIN_PIVOTS:                    # (host loops over the window: formed once per design)
+            _KIN_PIVOTS[(h, d, window)] = poly_taps(h, d, window)[1:]
+        sw, piv = _KIN_PIVOTS[(h, d, window)]
+    else:
+        _, sw, piv = poly_taps(h, d, window)
+    return h, d, nv, kin_thresholds(sw, piv, mc, pr, h), fd, a, b
+
+
+def poly_fit_f64(mom, rec, half_window, degree, window="hann", n_values=None, min_coverage=0.5, piv_rel=KIN_PIV_REL,
+                 fill_degree=1, want_filled=False, frame_range=None, device=None):
+    """The local polynomial fit of every window with its fallback in degree (`vbs_poly_fit_f64`).  mom float64
+    [b-a, s, M] as `poly_moments_f64(rec, half_window, degree, window, n_values, frame_range)` returns it, rec the record itself.
+    A window keeps the largest degree q <= d whose pivots D_0 .. D_q all exceed their thresholds: D_0 = S_0 > `min_coverage` x the
+    window's sum, D_k > `piv_rel` x the pivot of the gap-free full window.  Returns `fit` float64 [b-a, s, 2 + (d + 2) n_values] =
+    flag (centre valid + 2 (q >= 0) + 4 (q == d)), q, then per value the derivatives y_0 .. y_d at the centre in units of frames
+    (0 above q) and the weighted residual sum of squares; with `want_filled` (fit, filled): `filled` float64 [b-a, s, cols], the
+    valid rows of rec bit for bit, flag 2.0 and y_0 where the entry is missing and q >= `fill_degree`, zeros otherwise -
+    a record every other entry of this module takes as it is."""
+    if not torch.cuda.is_available():
+        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    m = torch.as_tensor(mom, dtype=torch.float64, device=dev).contiguous()
+    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
+    if m.dim() != 3 or r.dim() != 3 or m.shape[1] != r.shape[1]:
+        raise ValueError("mom must be [F, s, M] and rec [n, s, cols] with the same s")
+    F, s, M = m.shape
+    n, _, cols = r.shape
+    h, d, nv, thr, fd, a, b = _kin_fit_args(F, s, M, n, cols, half_window, degree, window, n_values, min_coverage, piv_rel,
+                                            fill_degree, frame_range)
+    fit = torch.empty((F, s, 2 + (d + 2) * nv), dtype=torch.float64, device=dev)
+    filled = torch.empty((F, s, cols), dtype=torch.float64, device=dev) if want_filled else None
+    if F:
+        thr = np.ascontiguousarray(thr, dtype=np.float64)
+        with torch.cuda.device(dev):
+            rc = L.lib().vbs_poly_fit_f64(dev.index, _ptr(m), _ptr(r), n, s, cols, nv, d, h, thr.ctypes.data_as(C.c_void_p), fd, a, b,
+                                          _ptr(fit), _ptr(filled) if want_filled else None,
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc == L.VBS_EINVAL:
+            raise ValueError("vbs_poly_fit_f64: bad argument (thresholds >= 0, 0 <= fill_degree <= 3)")
+        if rc != L.VBS_OK:
+            raise L.VbsError(f"vbs_poly_fit_f64 failed ({rc})")
+    return (fit, filled) if want_filled else fit
+
+
 # ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
 def _steps_call(name, what, fn):
     rc = fn()

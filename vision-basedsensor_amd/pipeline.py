@@ -996,6 +996,193 @@ def to_mode_frame(result, frame_offset=0, path=None):
     return df
 
 
+# ---- marker velocity, acceleration and gap filling (k_kinematics.hip): a gap-aware local polynomial fit along time -----------------
+KINEMATIC_FRAME_COLUMNS = ("frameno", "marker_id", "axis", "displacement", "velocity", "acceleration", "noise", "degree")
+
+
+def _kinematic_args(n, m, half_window, degree, window, ref_frame, min_coverage, piv_rel, onset_frac, axis="z"):
+    """`kinematic_analysis`'s argument checks (no device needed): -> (h, d, axis index) or ValueError."""
+    from .engine import _kin_args
+    h, d, _, _, _ = _kin_args(max(n, 1), max(m, 1), 4, half_window, degree, window, 3, None)
+    if n < 1 or m < 1:
+        raise ValueError("the table must have at least one frame and one slot")
+    if not (0 <= int(ref_frame) < n):
+        raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+    if not (0.0 < float(min_coverage) <= 1.0):
+        raise ValueError("min_coverage must lie in (0, 1]")
+    if not (0.0 <= float(piv_rel) < 1.0):
+        raise ValueError("piv_rel must lie in [0, 1)")
+    if not (0.0 < float(onset_frac) <= 1.0):
+        raise ValueError("onset_frac must lie in (0, 1]")
+    if axis not in _SPECTRUM_AXES:
+        raise ValueError(f"axis must be one of {_SPECTRUM_AXES}")
+    return h, d, _SPECTRUM_AXES.index(axis)
+
+
+def _kinematic_rows(fit, mom, degree, fps=None, onset_frac=0.1):
+    """The host arithmetic of `kinematic_analysis`: fit [F, k, 2 + 3 (d + 2)] and mom [F, k, M] (host, three values) -> a dict of
+    `displacement`, `velocity`, `acceleration` [F, k, 3] (the derivatives y_0, y_1, y_2 of the fit, times fps and fps^2 with `fps`;
+    NaN where no degree was reached, velocity NaN below degree 1 of the request, acceleration below 2), `speed` [F, k] = |v|,
+    `noise` [F, k, 3] = sqrt(max(rss, 0) / S_0), `degree` int64 [F, k] (the degree used, -1 without one); per frame `mean_speed`,
+    `max_speed` [F] over the slots that have a speed (NaN without one) and `fastest` int64 [F], the slot that has the largest speed,
+    ties to the smaller slot, -1 without one; per slot `peak_speed` [k] and `peak_frame` int64 [k] (the first of equal ones, NaN / -1
+    without a speed); `onset`: the first frame whose mean speed exceeds `onset_frac` x the largest mean speed (-1 without one)."""
+    fit, mom = np.asarray(fit, dtype=np.float64), np.asarray(mom, dtype=np.float64)
+    d = int(degree)
+    F, k = fit.shape[:2]
+    q = fit[..., 1].astype(np.int64)
+    have = q >= 0
+    per = fit[..., 2:].reshape(F, k, 3, d + 2)
+    nan = lambda v: np.where(have[..., None], v, np.nan)                                          # noqa: E731
+    scale = 1.0 if fps is None else float(fps)
+    out = {"degree": q, "displacement": nan(per[..., 0])}
+    out["velocity"] = nan(per[..., 1] * scale) if d >= 1 else np.full((F, k, 3), np.nan)
+    out["acceleration"] = nan(per[..., 2] * (scale * scale)) if d >= 2 else np.full((F, k, 3), np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["noise"] = nan(np.sqrt(np.maximum(per[..., d + 1], 0.0) / mom[..., :1]))
+    speed = np.sqrt((out["velocity"] ** 2).sum(axis=2))
+    out["speed"] = speed
+    seen = ~np.isnan(speed)
+    cnt = seen.sum(axis=1)
+    filled = np.where(seen, speed, -np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["mean_speed"] = np.where(cnt > 0, np.where(seen, speed, 0.0).sum(axis=1) / cnt, np.nan)
+    out["max_speed"] = np.where(cnt > 0, filled.max(axis=1, initial=-np.inf), np.nan)
+    out["fastest"] = np.where(cnt > 0, np.argmax(filled, axis=1), -1).astype(np.int64)               # argmax: the first of equal ones
+    any_f = seen.any(axis=0)
+    out["peak_speed"] = np.where(any_f, filled.max(axis=0, initial=-np.inf), np.nan)
+    out["peak_frame"] = np.where(any_f, np.argmax(filled, axis=0), -1).astype(np.int64)
+    ms = out["mean_speed"]
+    onset = -1
+    if np.isfinite(ms).any() and np.nanmax(ms) > 0.0:
+        over = np.nonzero(np.nan_to_num(ms, nan=0.0) > float(onset_frac) * np.nanmax(ms))[0]
+        onset = int(over[0]) if over.size else -1
+    out["onset"] = onset
+    return out
+
+
+def kinematic_analysis(eng: Engine, table: torch.Tensor, half_window=7, degree=2, window="hann", ref_frame=0, slots=None, fps=None,
+                       min_coverage=0.5, piv_rel=None, grid=None, onset_frac=0.1, axis="z"):
+    """Smoothed displacement, velocity and acceleration of every marker along a recording (slip, approach speed,
+    first contact and the direction reversal of the reference's Figure 11(b) are statements about rates, and it ships no code for
+    them) from a table [N, M, 10]: `Engine.axis_displacement` against `ref_frame` (`slots`: indices), fitted by a polynomial of
+    `degree` <= 3 in a sliding window of 2 `half_window` + 1 frames weighted by `window`, gaps selected out, one-sided at the ends:
+    `poly_moments_f64` then `poly_fit_f64` for the markers, and the same pair for the per-frame `total` as a record of one series.
+    A window that a gap or an end leaves badly determined falls back in degree (`piv_rel`, default `engine.KIN_PIV_REL`).  Returns
+    a dict.  Device tensors (float64): `series` [N, M, 4], `moments`, `fit` [N, M, 2 + 3 (d + 2)], `total_series` [N, 1, 5],
+    `total_fit`.  Host arrays (`_kinematic_rows`): `displacement`, `velocity`, `acceleration`, `noise` [N, M, 3] (per frame, times
+    `fps` and `fps`^2 when given; NaN where the window reached no degree), `speed` [N, M], `degree` [N, M], `mean_speed`,
+    `max_speed`, `fastest` [N], `peak_speed`, `peak_frame` [M], `onset`, and `total_displacement`, `total_velocity`,
+    `total_acceleration` [N, 3].  With `grid` = (weights [P, M], wsum [P]) from `fields.gaussian_weights` / `fields.row_sums`:
+    `speed_map` [N, P, 2] = `field_map_f64` of the record (has a speed, speed): where on the bonnet the skin moves fastest, frame
+    by frame; with a third element grid_xy [P, 2] also `speed_patch` [N, 8] = `patch_stats_f64` of that map."""
+    from .engine import KIN_PIV_REL, field_map_f64, patch_stats_f64, poly_fit_f64, poly_moments_f64
+    n, m = int(table.shape[0]), int(table.shape[1])
+    pr = KIN_PIV_REL if piv_rel is None else piv_rel
+    h, d, ax = _kinematic_args(n, m, half_window, degree, window, ref_frame, min_coverage, pr, onset_frac, axis)
+    dev = eng.device.index
+    ax_rec, tot = eng.axis_displacement(table, ref_frame, slots)
+    out = {"half_window": h, "degree_asked": d, "fps": fps}
+    for name, rec in (("", ax_rec), ("total_", tot[:, None, :].contiguous())):
+        mom = poly_moments_f64(rec, h, d, window, 3, device=dev)
+        fit = poly_fit_f64(mom, rec, h, d, window, 3, min_coverage, pr, device=dev)
+        out.update({name + "series": rec, name + "moments": mom, name + "fit": fit})
+        rows = _kinematic_rows(fit.cpu().numpy(), mom.cpu().numpy(), d, fps, onset_frac)
+        if not name:
+            out.update(rows)
+        else:
+            for key in ("displacement", "velocity", "acceleration"):
+                out[name + key] = rows[key][:, 0]
+    if grid is not None:
+        Wg, wsum = grid[0], grid[1]
+        sp = out["speed"]
+        rec = torch.from_numpy(np.stack([(~np.isnan(sp)).astype(np.float64), np.nan_to_num(sp, nan=0.0)], axis=2)).to(eng.device)
+        out["speed_map"] = field_map_f64(rec, torch.as_tensor(Wg, dtype=torch.float64, device=eng.device),
+                                         torch.as_tensor(wsum, dtype=torch.float64, device=eng.device), min_coverage, 1, device=dev)
+        if len(grid) > 2:
+            out["speed_patch"] = patch_stats_f64(out["speed_map"], grid[2], component=0, device=dev)
+    return out
+
+
+def to_kinematic_frame(result, ids=None, fps=None, path=None):
+    """The long sheet of `kinematic_analysis`: one row `KINEMATIC_FRAME_COLUMNS` per frame, slot and axis (frame-major, then slot,
+    then axis "x", "y", "z"); `frameno` counts from 1, `marker_id` = `ids.marker_ids` (slot number + 1 without `ids`); with `fps` also
+    `time_s` = (frameno - 1) / fps.  displacement .. noise are NaN (empty cells) where the window reached no degree.  `path`: also
+    written, as .csv or as .xlsx."""
+    import pandas as pd
+    dis, vel, acc, noi = (np.asarray(result[k], dtype=np.float64) for k in ("displacement", "velocity", "acceleration", "noise"))
+    deg = np.asarray(result["degree"])
+    if dis.ndim != 3 or dis.shape[2] != 3 or any(v.shape != dis.shape for v in (vel, acc, noi)) or deg.shape != dis.shape[:2]:
+        raise ValueError("displacement, velocity, acceleration and noise must be [N, M, 3], degree [N, M]")
+    N, M = dis.shape[:2]
+    mid = _ids.marker_ids(ids) if ids is not None else np.arange(1, M + 1, dtype=np.int64)
+    if len(mid) != M:
+        raise ValueError(f"the result has {M} slots, ids {len(mid)}")
+    cols = {"frameno": np.repeat(np.arange(1, N + 1, dtype=np.int64), 3 * M),
+            "marker_id": np.tile(np.repeat(np.asarray(mid), 3), N),
+            "axis": np.tile(np.array(_SPECTRUM_AXES, dtype=object), N * M),
+            "displacement": dis.reshape(-1), "velocity": vel.reshape(-1), "acceleration": acc.reshape(-1), "noise": noi.reshape(-1),
+            "degree": np.repeat(deg.reshape(-1).astype(np.int64), 3)}
+    if fps is not None:
+        fps = float(fps)
+        if not (np.isfinite(fps) and fps > 0.0):
+            raise ValueError("fps must be finite and > 0")
+        cols["time_s"] = (cols["frameno"] - 1) / fps
+    df = pd.DataFrame(cols)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
+def fill_table(eng: Engine, table: torch.Tensor, half_window=7, degree=2, *, source="xyz", fill_degree=1, slots=None, window="hann",
+               min_coverage=0.5, piv_rel=None):
+    """The gaps of a table [N, M, 10] filled along time by the constant term of the gap-aware local polynomial fit
+    (`engine.poly_moments_f64`, `engine.poly_fit_f64`), in `despike_table`'s conventions.  `source` "xyz": the rows
+    with VBS_FLAG_XYZ, values X, Y, Z (cols 6-8); "pixel": the rows with VBS_FLAG_TRACKED, values Cx, Cy.  `slots` (indices)
+    restricts the filling to those markers.  Returns (filled_table, report): filled_table is a copy of the table in which a MISSING
+    row whose window reaches `fill_degree` has its values replaced by y_0, rounded to the table's dtype once; its flag bits are
+    untouched - whether to set VBS_FLAG_XYZ (or VBS_FLAG_TRACKED) on an interpolated row is the caller's decision, and
+    `report["filled"]` bool [N, M] is what they would OR in.  report, a dict of tensors on the table's device: `filled`; `degree`
+    int64 [N, M] (the degree used, -1 without one); `per_marker` [M] and `per_frame` [N] int64 counts of filled rows; `values`
+    float64 [N, M, nv] (y_0 where filled, else 0); `source`."""
+    from . import engine as _engine
+    if source not in _SPIKE_SOURCES:
+        raise ValueError(f"source must be one of {sorted(_SPIKE_SOURCES)}")
+    bit, _, cols, _ = _SPIKE_SOURCES[source]
+    t = table if isinstance(table, torch.Tensor) else torch.as_tensor(np.asarray(table), device=eng.device)
+    if t.dim() != 3 or t.shape[2] != L.TABLE_COLS:
+        raise ValueError(f"table must be [N, M, {L.TABLE_COLS}]")
+    flags = t[..., 0].to(torch.int64)
+    valid = (flags & bit) != 0
+    pick = torch.ones(t.shape[1], dtype=torch.bool, device=t.device)
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= t.shape[1]):
+            raise ValueError(f"slots outside the table's {t.shape[1]} slots")
+        pick = torch.zeros(t.shape[1], dtype=torch.bool, device=t.device)
+        pick[torch.as_tensor(idx, device=t.device)] = True
+    nv = len(cols)
+    rec = torch.cat([valid.to(torch.float64)[..., None], t[..., list(cols)].to(torch.float64)], dim=2).contiguous()
+    pr = _engine.KIN_PIV_REL if piv_rel is None else piv_rel
+    dev = eng.device.index
+    mom = _engine.poly_moments_f64(rec, half_window, degree, window, nv, device=dev)
+    fit, filled_rec = _engine.poly_fit_f64(mom, rec, half_window, degree, window, nv, min_coverage, pr, fill_degree, want_filled=True,
+                                           device=dev)
+    fit, filled_rec = torch.as_tensor(fit, device=t.device), torch.as_tensor(filled_rec, device=t.device)
+    did = (filled_rec[..., 0] == 2.0) & pick[None, :]
+    out = t.clone()
+    vals = filled_rec[..., 1:1 + nv]
+    for k, c in enumerate(cols):
+        out[..., c] = torch.where(did, vals[..., k].to(t.dtype), t[..., c])
+    report = {"filled": did, "degree": fit[..., 1].to(torch.int64), "per_marker": did.sum(dim=0), "per_frame": did.sum(dim=1),
+              "values": torch.where(did[..., None], vals, torch.zeros_like(vals)), "source": source}
+    return out, report
+
+
 # ---- the probe-indentation validation (k_steps.hip): the reference's Figure 6(b) from a tracked table -------------------------
 @dataclass
 class IndentationResult:
