@@ -1052,148 +1052,6 @@ extern "C" int vbs_axis_displacement(vbs_handle* h, const float* table, int n, i
     return check_launch(h);
 }
 
-extern "C" int vbs_fir_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half,
-                                  int n_half, double min_coverage, int frame_begin, int frame_end, double* out, void* stream) {
-    if (!rec || !half || !out || !series_shape_ok(n, s, 0) || cols < 2 || cols > 8 || n_values < 1 || n_values >= cols ||
-        n_half < 1 || 2 * (int64_t)n_half - 1 > VBS_FIR_MAX_TAPS || !(min_coverage > 0.0 && min_coverage <= 1.0) ||
-        frame_begin < 0 || frame_end > n || frame_begin > frame_end)
-        return VBS_EINVAL;
-    double sw = 0.0;                                     // ascending over k = -h .. h, as the kernel adds den
-    for (int k = -(n_half - 1); k <= n_half - 1; ++k) sw = sw + half[k < 0 ? -k : k];
-    if (!(sw > 0.0)) return VBS_EINVAL;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_fir_series(rec, n, s, cols, n_values, half, n_half, min_coverage * sw, frame_begin, frame_end, out,
-                          (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- despiking a tracked series (k_robust.hip) ----------------------------------------------------------------------------------
-extern "C" int vbs_hampel_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, int half_window,
-                                     int min_count, double k_sigma, double min_scale, int frame_begin, int frame_end, double* out,
-                                     double* clean, void* stream) {
-    if (!rec || !out || !series_shape_ok(n, s, 0) || cols < 2 || cols > 8 || n_values < 1 || n_values >= cols || half_window < 0 ||
-        half_window > VBS_ROBUST_MAX_HALF || min_count < 1 || min_count > 2 * half_window + 1 || !std::isfinite(k_sigma) ||
-        !(k_sigma > 0.0) || !std::isfinite(min_scale) || !(min_scale >= 0.0) || frame_begin < 0 || frame_end > n ||
-        frame_begin > frame_end)
-        return VBS_EINVAL;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_hampel_series(rec, n, s, cols, n_values, half_window, min_count, k_sigma * 1.4826, min_scale, frame_begin, frame_end,
-                             out, clean, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- time-resolved amplitude and phase along a recording (k_envelope.hip) -------------------------------------------------------
-extern "C" int vbs_window_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* carrier,
-                                      const double* half, int n_half, int frame_begin, int frame_end, double* mom, void* stream) {
-    if (!rec || !carrier || !half || !mom || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
-        n_values >= cols || n_half < 1 || n_half - 1 > VBS_ENV_MAX_HALF || frame_begin < 0 || frame_end > n ||
-        frame_begin > frame_end)
-        return VBS_EINVAL;
-    for (int i = 0; i < n_half; ++i)
-        if (!std::isfinite(half[i]) || !(half[i] >= 0.0)) return VBS_EINVAL;
-    if (!(half[0] > 0.0)) return VBS_EINVAL;
-    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_window_moments(rec, n, s, cols, n_values, carrier, half, n_half, frame_begin, frame_end, mom, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_window_fit_f64(int device, const double* mom, int F, int s, int n_values, double sw, double min_coverage,
-                                  double det_min, double* fit, void* stream) {
-    if (!mom || !fit || F < 1 || s < 1 || n_values < 1 || n_values > 3 || !std::isfinite(sw) || !(sw > 0.0) ||
-        !(min_coverage > 0.0 && min_coverage <= 1.0) || !(det_min >= 0.0 && det_min < 0.25))
-        return VBS_EINVAL;
-    if (F > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_window_fit(mom, F, s, n_values, min_coverage * sw, det_min, fit, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- marker velocity, acceleration and gap filling (k_kinematics.hip) ------------------------------------------------------------
-extern "C" int vbs_poly_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* half,
-                                    int n_half, int degree, int frame_begin, int frame_end, double* mom, void* stream) {
-    if (!rec || !half || !mom || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 || n_values >= cols ||
-        n_half < 1 || n_half - 1 > VBS_KIN_MAX_HALF || degree < 0 || degree > VBS_KIN_MAX_DEGREE || frame_begin < 0 ||
-        frame_end > n || frame_begin > frame_end)
-        return VBS_EINVAL;
-    for (int i = 0; i < n_half; ++i)
-        if (!std::isfinite(half[i]) || !(half[i] >= 0.0)) return VBS_EINVAL;
-    if (!(half[0] > 0.0)) return VBS_EINVAL;
-    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_poly_moments(rec, n, s, cols, n_values, half, n_half, degree, frame_begin, frame_end, mom, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_poly_fit_f64(int device, const double* mom, const double* rec, int n, int s, int cols, int n_values, int degree,
-                                int half_window, const double* thr, int fill_degree, int frame_begin, int frame_end, double* fit,
-                                double* filled, void* stream) {
-    if (!mom || !rec || !thr || !fit || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
-        n_values >= cols || degree < 0 || degree > VBS_KIN_MAX_DEGREE || half_window < 0 || half_window > VBS_KIN_MAX_HALF ||
-        fill_degree < 0 || fill_degree > VBS_KIN_MAX_DEGREE || frame_begin < 0 || frame_end > n || frame_begin > frame_end)
-        return VBS_EINVAL;
-    for (int k = 0; k <= degree; ++k)
-        if (!(thr[k] >= 0.0)) return VBS_EINVAL;                     // (a NaN fails it; +inf switches the order off)
-    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_poly_fit(mom, rec, s, cols, n_values, degree, half_window, thr, fill_degree, frame_begin, frame_end, fit, filled,
-                        (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- principal modes of the displacement field (k_modes.hip) ----------------------------------------------------------------------
-extern "C" int vbs_cross_moments_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* shift,
-                                     double* mom, void* stream) {
-    if (!rec || !mom || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 || n_values >= cols) return VBS_EINVAL;
-    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_MOM_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_cross_moments(rec, n, s, cols, n_values, shift, mom, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_covariance_f64(int device, const double* mom, int s, int n_values, int mode, int min_count, double denom,
-                                  const uint8_t* slot_mask, double* cov, uint8_t* ok, void* stream) {
-    if (!mom || !cov || s < 1 || n_values < 1 || n_values > 3 || (mode != 0 && mode != 1) || min_count < 2 ||
-        (mode == 1 && (!std::isfinite(denom) || !(denom > 0.0))))
-        return VBS_EINVAL;
-    if (s > VBS_MOM_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_covariance(mom, s, n_values, mode, min_count, denom, slot_mask, cov, ok, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_leading_modes_f64(int device, const double* A, int C, int r, int iters, double tiny, double* work, double* values,
-                                     double* modes, double* resid, int32_t* info, void* stream) {
-    if (!A || !work || !values || !modes || !resid || !info || C < 1 || r < 1 || r > VBS_MODES_MAX || iters < 0 ||
-        iters > VBS_MODES_MAX_ITERS || !(tiny >= 0.0 && tiny < 1.0))
-        return VBS_EINVAL;
-    if (r > C) return VBS_EINVAL;
-    if (C > VBS_MODES_MAX_DIM) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_leading_modes(A, C, r, iters, tiny, work, values, modes, resid, info, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_mode_scores_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* center,
-                                   const double* modes, int r, double min_coverage, int frame_begin, int frame_end, double* scores,
-                                   double* energy, void* stream) {
-    if (!rec || !center || !modes || !scores || n < 1 || s < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
-        n_values >= cols || r < 1 || r > VBS_MODES_MAX || !(min_coverage > 0.0 && min_coverage <= 1.0) || frame_begin < 0 ||
-        frame_end > n || frame_begin > frame_end)
-        return VBS_EINVAL;
-    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_MOM_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_mode_scores(rec, s, cols, n_values, center, modes, r, min_coverage, frame_begin, frame_end, scores, energy,
-                           (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
 // ---- pose misalignment along a recording (k_pose.hip) ---------------------------------------------------------------------------
 extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
                                const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k,
@@ -1211,124 +1069,6 @@ extern "C" int vbs_pose_series(vbs_handle* h, const float* table, int n, int m_r
         launch_pose_series(h, table, m_ref, start_frame, ref_disp, ref_xyz, slot_mask, shell_mode, scale, reject_k, frame_begin,
                            frame_end, deviation, field, pose, (hipStream_t)stream);
     return check_launch(h);
-}
-
-// ---- contact maps along a recording (k_field.hip) -------------------------------------------------------------------------------
-extern "C" int vbs_field_map_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* W,
-                                 const double* wsum, int P, double min_coverage, int frame_begin, int frame_end, double* map,
-                                 void* stream) {
-    if (!rec || !W || !wsum || !map || n < 1 || s < 1 || P < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
-        n_values >= cols || !(min_coverage > 0.0 && min_coverage <= 1.0) || frame_begin < 0 || frame_end > n ||
-        frame_begin > frame_end)
-        return VBS_EINVAL;
-    if (s > VBS_FIELD_MAX_SLOTS || P > VBS_FIELD_MAX_POINTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin) {
-        const int rc = launch_field_map(rec, s, cols, n_values, W, wsum, P, min_coverage, frame_begin, frame_end, map,
-                                        (hipStream_t)stream);
-        if (rc != VBS_OK) { (void)hipGetLastError(); return rc; }
-    }
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_patch_stats_f64(int device, const double* map, int F, int P, int n_values, const double* grid_xy, int component,
-                                   double sign, double thr, double* patch, void* stream) {
-    if (!map || !grid_xy || !patch || F < 1 || P < 1 || n_values < 1 || n_values > 3 || component < -1 || component >= n_values ||
-        !(sign == 1.0 || sign == -1.0) || !(thr >= 0.0))
-        return VBS_EINVAL;
-    if (P > VBS_FIELD_MAX_POINTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_patch_stats(map, F, P, n_values, grid_xy, component, sign, thr, patch, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- displacement spectra along a recording (k_spectrum.hip) --------------------------------------------------------------------
-extern "C" int vbs_project_series_f64(int device, const double* rec, int n, int s, int cols, int n_values, const double* basis,
-                                      int R, double* proj, void* stream) {
-    if (!rec || !basis || !proj || n < 1 || s < 1 || R < 1 || cols < 2 || cols > 8 || n_values < 1 || n_values > 3 ||
-        n_values >= cols)
-        return VBS_EINVAL;
-    if (n > VBS_PROJ_MAX_FRAMES || s > VBS_PROJ_MAX_SLOTS || R > VBS_PROJ_MAX_ROWS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_project_series(rec, n, s, cols, n_values, basis, R, proj, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_harmonic_fit_f64(int device, const double* proj, int s, int R, int n_values, int Q, int min_count,
-                                    double det_min, double* fit, double* peak, void* stream) {
-    if (!proj || (!fit && !peak) || s < 1 || Q < 1 || Q > (VBS_PROJ_MAX_ROWS - 1) / 4 || R != 1 + 4 * Q || n_values < 1 ||
-        n_values > 3 || min_count < 3 || !(det_min >= 0.0 && det_min < 0.25))
-        return VBS_EINVAL;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_harmonic_fit(proj, s, R, n_values, Q, min_count, det_min, fit, peak, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- shear, torsion and strain along a recording (k_motion.hip) ------------------------------------------------------------------
-static bool motion_shape_ok(const double* rec, const double* pos, int n, int s, int cols, int frame_begin, int frame_end) {
-    return rec && pos && n >= 1 && s >= 1 && cols >= 4 && cols <= 8 && frame_begin >= 0 && frame_end <= n && frame_begin <= frame_end;
-}
-
-extern "C" int vbs_motion_series_f64(int device, const double* rec, int n, int s, int cols, const double* pos,
-                                     const uint8_t* slot_mask, double reject_k, int frame_begin, int frame_end, double* grad,
-                                     double* strain, double* residual, void* stream) {
-    if (!motion_shape_ok(rec, pos, n, s, cols, frame_begin, frame_end) || (!grad && !strain && !residual) ||
-        !std::isfinite(reject_k) || reject_k < 0.0)
-        return VBS_EINVAL;
-    if (s > VBS_FIELD_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_motion_series(rec, s, cols, pos, slot_mask, reject_k, frame_begin, frame_end, grad, strain, residual,
-                             (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_local_strain_f64(int device, const double* rec, int n, int s, int cols, const double* pos, const int32_t* nbr,
-                                    int K, int min_count, double det_rel, int frame_begin, int frame_end, double* out,
-                                    void* stream) {
-    if (!motion_shape_ok(rec, pos, n, s, cols, frame_begin, frame_end) || !nbr || !out || K < 1 || K > VBS_STRAIN_MAX_NBR ||
-        min_count < 3 || min_count > K + 1 || !(det_rel >= 0.0 && det_rel < 1.0))
-        return VBS_EINVAL;
-    if (s > VBS_FIELD_MAX_SLOTS) return VBS_ECAPACITY;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    if (frame_end > frame_begin)
-        launch_local_strain(rec, s, cols, pos, nbr, K, min_count, det_rel, frame_begin, frame_end, out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-// ---- the probe-indentation validation (k_steps.hip) ---------------------------------------------------------------------------
-static bool record_shape_ok(int n, int s, int cols, int n_values) {
-    return series_shape_ok(n, s, 0) && cols >= 2 && cols <= 8 && n_values >= 1 && n_values < cols;
-}
-
-extern "C" int vbs_step_response_f64(int device, const double* rec, int n, int s, int cols, int n_values, int window,
-                                     int min_count, double* out, void* stream) {
-    if (!rec || !out || !record_shape_ok(n, s, cols, n_values) || window > VBS_STEP_MAX_WINDOW || min_count < 1 ||
-        min_count > window)
-        return VBS_EINVAL;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_step_response(rec, n, s, cols, n_values, window, min_count, out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_find_steps_f64(int device, const double* resp, int n, int s, int resp_cols, int window, double thr2,
-                                  int max_steps, int32_t* steps, void* stream) {
-    if (!resp || !steps || !series_shape_ok(n, s, 0) || resp_cols < 2 || resp_cols > 9 || window < 1 ||
-        window > VBS_STEP_MAX_WINDOW || !(thr2 >= 0.0) || max_steps < 1 || max_steps > VBS_STEP_MAX_STEPS)
-        return VBS_EINVAL;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_find_steps(resp, n, s, resp_cols, window, thr2, max_steps, steps, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
-}
-
-extern "C" int vbs_dwell_stats_f64(int device, const double* rec, int n, int s, int cols, int n_values, const int32_t* steps,
-                                   int steps_rows, int max_steps, int guard, double* out, void* stream) {
-    if (!rec || !steps || !out || !record_shape_ok(n, s, cols, n_values) || (steps_rows != s && steps_rows != 1) ||
-        max_steps < 1 || max_steps > VBS_STEP_MAX_STEPS || guard < 0)
-        return VBS_EINVAL;
-    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
-    launch_dwell_stats(rec, n, s, cols, n_values, steps, steps_rows, max_steps, guard, out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
 extern "C" int vbs_assign_ids(vbs_handle* h, const double* det, const int32_t* count, int num_layers, int id_mode,

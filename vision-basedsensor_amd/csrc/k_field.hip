@@ -15,6 +15,7 @@
 //   k_patch_stats   one wave per frame, VBS_PATCH_GROUP frames (waves) a workgroup, nothing shared; every sum follows the rule of
 //            k_axis_displacement (lane l adds points l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1), without contraction.
 #include "common.h"
+#include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define FIELD_WAVES   8
@@ -145,18 +146,6 @@ int launch_field_map(const double* rec, int s, int cols, int n_values, const dou
     return VBS_OK;
 }
 
-// a[i] (+) a[i + 32], then 16, 8, 4, 2, 1; every lane gets lane 0's result
-__device__ __forceinline__ double patch_fold(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
-    return __shfl(v, 0);
-}
-__device__ __forceinline__ int patch_fold(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return __shfl(v, 0);
-}
-
 __global__ __launch_bounds__(VBS_PATCH_GROUP * 64) void k_patch_stats(const double* __restrict__ map, int F, int P, int nv,
                                                                       const double* __restrict__ grid_xy, int component, double sign,
                                                                       double thr, double* __restrict__ patch) {
@@ -185,14 +174,16 @@ __global__ __launch_bounds__(VBS_PATCH_GROUP * 64) void k_patch_stats(const doub
         Sy = Sy + sc * grid_xy[2 * p + 1];
         if (pi < 0 || sc > pk) { pk = sc; pi = p; }                      // ascending p: the earliest of equal maxima stays
     }
+    // wave_argmax_down(pk, pi), written out: through the function's references this kernel compiles to other device code
+    // (profiles/analysis_fold_text_equal.txt)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const double ok = __shfl_down(pk, off);
         const int oi = __shfl_down(pi, off);
         if (oi >= 0 && (pi < 0 || ok > pk || (ok == pk && oi < pi))) { pk = ok; pi = oi; }
     }
-    covered = patch_fold(covered); count = patch_fold(count);
-    S = patch_fold(S); Sx = patch_fold(Sx); Sy = patch_fold(Sy);
+    covered = wave_sum(covered); count = wave_sum(count);
+    S = wave_sum(S); Sx = wave_sum(Sx); Sy = wave_sum(Sy);
     if (lane == 0) {
         double* o = patch + fi * VBS_PATCH_COLS;
         const bool centre = covered > 0 && count > 0 && S > 0.0;

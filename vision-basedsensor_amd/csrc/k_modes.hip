@@ -25,6 +25,7 @@
 //            is read and written by one thread and only the sums need a barrier (one each, the LDS slot alternates).
 //   k_mode_scores  one wave per frame, VBS_SCORE_GROUP frames a workgroup, no barrier, nothing shared.
 #include "common.h"
+#include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define MOM_WAVES   (VBS_MOM_WG_SLOTS / 4)              // one 16-row tile (4 slots) a wave
@@ -224,8 +225,7 @@ __global__ __launch_bounds__(MODES_THREADS) void k_modes_apply(const double* __r
 #pragma unroll
     for (int k = 0; k < MR; ++k) {
         if (k >= r) continue;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[k] = acc[k] + __shfl_down(acc[k], off);
+        acc[k] = wave_fold_down(acc[k]);
         if (lane == 0) Y[(int64_t)row * MR + k] = acc[k];
     }
 }
@@ -249,8 +249,7 @@ __device__ __forceinline__ void modes_sums(const double* X, int j, const double*
 #pragma unroll
     for (int k = 0; k < MR; ++k) {
         if (k < lo || k >= hi) continue;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[k] = acc[k] + __shfl_down(acc[k], off);
+        acc[k] = wave_fold_down(acc[k]);
         if (lane == 0) red[slot][wave][k] = acc[k];
     }
     __syncthreads();
@@ -455,6 +454,8 @@ __global__ __launch_bounds__(VBS_SCORE_GROUP * 64) void k_mode_scores(const doub
             den[k] = den[k] + u * u;
         }
     }
+    // the fold of wave_fold_down for two sums, a step of each in turn (written out here and below: one whole fold after the
+    // other is the same arithmetic but other device code, profiles/analysis_fold_text_equal.txt)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { e = e + __shfl_down(e, off); cnt = cnt + __shfl_down(cnt, off); }
     const int64_t o = f - frame_begin;

@@ -14,6 +14,7 @@
 //                   neighbourhoods are added up.  One thread adds its members in list order: no fold.
 #include "common.h"
 #include "strain_math.h"
+#include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define MOTION_WAVES VBS_MOTION_GROUP
@@ -26,18 +27,6 @@ struct MotionStage {                             // 17 KB
 };
 struct MotionPoint { double px, py, d[3]; };
 struct MotionFit { double mx, my, md[3], gx[3], gy[3]; };
-
-// a[i] + a[i + 32], then + 16, 8, 4, 2, 1 (lanes >= off are not read again); every lane gets lane 0's sum
-__device__ __forceinline__ double motion_fold(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
-    return __shfl(v, 0);
-}
-__device__ __forceinline__ int motion_fold(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return __shfl(v, 0);
-}
 
 // r_k = e_k - (g_kx x + g_ky y) on the fit's own centred coordinates; -> q = r_X r_X + r_Y r_Y + r_Z r_Z, left to right
 __device__ __forceinline__ double motion_resid(const MotionFit& F, const MotionPoint& p, double (&r)[3]) {
@@ -92,9 +81,9 @@ __global__ __launch_bounds__(MOTION_WAVES * 64) void k_motion(const double* __re
                 sm[0] = sm[0] + p.px; sm[1] = sm[1] + p.py;
                 sm[2] = sm[2] + p.d[0]; sm[3] = sm[3] + p.d[1]; sm[4] = sm[4] + p.d[2];
             }
-        c = motion_fold(c);
+        c = wave_sum(c);
 #pragma unroll
-        for (int q = 0; q < 5; ++q) sm[q] = motion_fold(sm[q]);
+        for (int q = 0; q < 5; ++q) sm[q] = wave_sum(sm[q]);
         count = c;
         const double n = (double)c;
         F.mx = c > 0 ? sm[0] / n : 0.0; F.my = c > 0 ? sm[1] / n : 0.0;
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(MOTION_WAVES * 64) void k_motion(const double* __re
                 }
             }
 #pragma unroll
-        for (int q = 0; q < 9; ++q) cs[q] = motion_fold(cs[q]);
+        for (int q = 0; q < 9; ++q) cs[q] = wave_sum(cs[q]);
         const double det = cs[0] * cs[2] - cs[1] * cs[1];
         const bool exists = enough && fabs(det) > 1e-300;
         if (exists) {
@@ -124,14 +113,9 @@ __global__ __launch_bounds__(MOTION_WAVES * 64) void k_motion(const double* __re
         }
         return exists;
     };
-    // the largest q with the smallest slot among equals, over the wave (a lane without a candidate holds -1)
+    // the largest q with the smallest slot among equals, over the wave; every lane gets the slot
     auto worst_fold = [&](double& wq, int& wi) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double oq = __shfl_down(wq, off);
-            const int oi = __shfl_down(wi, off);
-            if (oi >= 0 && (wi < 0 || oq > wq || (oq == wq && oi < wi))) { wq = oq; wi = oi; }
-        }
+        wave_argmax_down(wq, wi);
         wi = __shfl(wi, 0);
     };
 
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(MOTION_WAVES * 64) void k_motion(const double* __re
             }
         }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) ss[k] = motion_fold(ss[k]);
+    for (int k = 0; k < 3; ++k) ss[k] = wave_sum(ss[k]);
     worst_fold(wq, wi);
     const double n0 = (double)cnt;
     double n_used = n0, flag = fit1 ? 1.0 : 0.0;
@@ -195,7 +179,7 @@ __global__ __launch_bounds__(MOTION_WAVES * 64) void k_motion(const double* __re
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 3; ++k) ss[k] = motion_fold(s2[k]);
+            for (int k = 0; k < 3; ++k) ss[k] = wave_sum(s2[k]);
             worst_fold(wq2, wi2);
             wi = wi2;
             F = F2; n_used = (double)kc; flag = 2.0;

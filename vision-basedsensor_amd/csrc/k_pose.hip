@@ -10,6 +10,7 @@
 //            The sums are recomputed from the table in every sweep: means / field, centred sums, SSR, and the same three over
 //            the kept set when reject_k > 0.
 #include "common.h"
+#include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define POSE_WAVES VBS_POSE_GROUP
@@ -26,18 +27,6 @@ struct PoseStage {                               // 50.5 KB with the tiles at PO
 };
 
 struct PosePoint { double dx, dy, dz, sx, sy, sz, px, py, pz; };
-
-// a[i] + a[i + 32], then + 16, 8, 4, 2, 1 (lanes >= off are not read again); every lane gets lane 0's sum
-__device__ __forceinline__ double pose_fold(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
-    return __shfl(v, 0);
-}
-__device__ __forceinline__ int pose_fold(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return __shfl(v, 0);
-}
 
 // One sweep over the slots in the stated order: lane l meets slots l, l + 64, ... ascending.  body(slot, cs, row): cs = the
 // slot's place in the staged chunk, row = its 10 floats of this wave's frame (not valid for slot >= m_ref).  EVERY thread of
@@ -140,10 +129,10 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
             o[0] = ok ? 1.0 : 0.0; o[1] = ok ? p.dx : 0.0; o[2] = ok ? p.dy : 0.0; o[3] = ok ? p.dz : 0.0;
         }
     });
-    cnt = pose_fold(cnt); want = pose_fold(want);
+    cnt = wave_sum(cnt); want = wave_sum(want);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { sp[k] = pose_fold(sp[k]); sd[k] = pose_fold(sd[k]); }
-    smag = pose_fold(smag);
+    for (int k = 0; k < 3; ++k) { sp[k] = wave_sum(sp[k]); sd[k] = wave_sum(sd[k]); }
+    smag = wave_sum(smag);
     const double n0 = (double)cnt;
     if (field && live && lane == 0) {
         double* o = field + fi * VBS_POSEFIELD_COLS;
@@ -165,7 +154,7 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
         c[0] = c[0] + x * x; c[1] = c[1] + x * y; c[2] = c[2] + y * y; c[3] = c[3] + x * z; c[4] = c[4] + y * z;
     });
 #pragma unroll
-    for (int q = 0; q < 5; ++q) c[q] = pose_fold(c[q]);
+    for (int q = 0; q < 5; ++q) c[q] = wave_sum(c[q]);
     const double det1 = c[0] * c[2] - c[1] * c[1];
     const bool plane1 = live && cnt >= 3 && fabs(det1) > 1e-300;
     double a = 0.0, b = 0.0, cc = 0.0, ssr = 0.0;
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
         const double r = z - (a * x + b * y);
         ssr = ssr + r * r;
     });
-    ssr = pose_fold(ssr);
+    ssr = wave_sum(ssr);
     double n_used = n0, flag = plane1 ? 1.0 : 0.0;
 
     // ---- sweeps 3 - 5: one round of rejection; the kept set is decided by the FIRST plane in every one of them -------------------
@@ -201,9 +190,9 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
             ++kc;
             kp[0] = kp[0] + p.px; kp[1] = kp[1] + p.py; kp[2] = kp[2] + p.pz;
         });
-        kc = pose_fold(kc);
+        kc = wave_sum(kc);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) kp[k] = pose_fold(kp[k]);
+        for (int k = 0; k < 3; ++k) kp[k] = wave_sum(kp[k]);
         const bool redo = rej && kc < cnt && kc >= 3;
         const double n2 = (double)kc;
         double m2[3];
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
             e[0] = e[0] + x * x; e[1] = e[1] + x * y; e[2] = e[2] + y * y; e[3] = e[3] + x * z; e[4] = e[4] + y * z;
         });
 #pragma unroll
-        for (int q = 0; q < 5; ++q) e[q] = pose_fold(e[q]);
+        for (int q = 0; q < 5; ++q) e[q] = wave_sum(e[q]);
         const double det2 = e[0] * e[2] - e[1] * e[1];
         const bool plane2 = redo && fabs(det2) > 1e-300;
         double a2 = 0.0, b2 = 0.0, ssr2 = 0.0;
@@ -229,7 +218,7 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
             const double r = z - (a2 * x + b2 * y);
             ssr2 = ssr2 + r * r;
         });
-        ssr2 = pose_fold(ssr2);
+        ssr2 = wave_sum(ssr2);
         if (plane2) {
             a = a2; b = b2; cc = m2[2] - a2 * m2[0] - b2 * m2[1];
             ssr = ssr2; n_used = n2; flag = 2.0;

@@ -13,6 +13,7 @@
 //   k_dwell_stats<NV>     one wave per (series, dwell): lane sums in ascending order, the fold of k_axis_displacement, two passes.
 // The data is time-major, series on the fast axis: a wave's accesses to one frame row are contiguous.
 #include "common.h"
+#include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define STEP_WAVES 8
@@ -223,13 +224,6 @@ void launch_find_steps(const double* resp, int n, int s, int resp_cols, int w, d
                        max_steps, steps);
 }
 
-// the 64 lane values folded a[i] + a[i + 32], then + 16, 8, 4, 2, 1, and the result given to every lane
-__device__ __forceinline__ double fold64(double a) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) a = a + __shfl_down(a, off);   // lane i: a[i] + a[i + off]; lanes >= off are not read again
-    return __shfl(a, 0);
-}
-
 // out [s][max_steps + 1][3 + 2 NV] = begin, end, count, mean[NV], M2[NV].  Whatever `steps` holds, begin and end are clipped to
 // [0, n] before a frame is read.
 template <int NV>
@@ -272,13 +266,11 @@ __global__ __launch_bounds__(64) void k_dwell_stats(const double* __restrict__ r
             for (int v = 0; v < NV; ++v) sum[v] = sum[v] + in[1 + v];
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_down(cnt, off);
-    cnt = __shfl(cnt, 0);
+    cnt = wave_sum(cnt);
     double mean[NV], m2[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-        const double t = fold64(sum[v]);
+        const double t = wave_sum(sum[v]);
         mean[v] = cnt > 0 ? t / (double)cnt : nan;
         m2[v] = 0.0;
     }
@@ -293,7 +285,7 @@ __global__ __launch_bounds__(64) void k_dwell_stats(const double* __restrict__ r
         }
     }
 #pragma unroll
-    for (int v = 0; v < NV; ++v) m2[v] = fold64(m2[v]);
+    for (int v = 0; v < NV; ++v) m2[v] = wave_sum(m2[v]);
     if (lane == 0) {
         o[0] = (double)begin; o[1] = (double)end; o[2] = (double)cnt;
 #pragma unroll

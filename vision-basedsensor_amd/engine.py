@@ -12,10 +12,15 @@ import numpy as np
 import torch
 
 from . import _lib as L
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+from .analysis import _device, _frame_range, _ptr
+from .analysis import (KIN_PIV_REL, covariance_f64, cross_moments_f64, dwell_stats_f64, field_map_f64, find_steps_f64,  # noqa: F401
+                       fir_series_f64, hampel_series_f64, harmonic_fit_f64, kin_thresholds, leading_modes_f64, local_strain_f64,
+                       mode_scores_f64, motion_series_f64, n_kin_sums, patch_stats_f64, poly_fit_f64, poly_moments_f64,
+                       project_series_f64, step_response_f64, taps_sum, window_fit_f64, window_moments_f64)
+# the wrappers' argument checkers, under the names the host tests have held them to since before they moved
+from .analysis import (_covariance_args, _envelope_args, _envelope_fit_args, _field_args, _fit_args, _kin_args,  # noqa: F401
+                       _kin_fit_args, _lstrain_args, _modes_args, _moments_args, _motion_args, _patch_args, _project_args,
+                       _robust_args, _scores_args)
 
 
 class Engine:
@@ -607,9 +612,7 @@ def _dev_f64(x, dev, cols):
 
 def undistort_points(points, cam: L.Camera, device=None):
     """float64 [n,2] -> [n,2] on the GPU (`MarkerAnalysis._undistort_points`)."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dev = _device(device)
     p = _dev_f64(points, dev, 2)
     out = torch.empty_like(p)
     rc = L.lib().vbs_undistort_points(dev.index, _ptr(p), p.shape[0], C.byref(cam), _ptr(out),
@@ -640,9 +643,7 @@ def pnp_ransac(world, image_or_table, cam: L.Camera, iterations: int = 1000, rep
     rows with FLAG_TRACKED); valid: optional [B,N] mask.  Returns a dict of device tensors: status [B], R [B,3,3], T [B,3],
     inlier_count [B], inlier_mask [B,N] uint8, mean_error [B], inlier_rms [B], winner [B], and per hypothesis hyp_count [B,H],
     hyp_pose [B,H,12]; `samples` (int32 [H,6], default `pnp_samples(N, iterations, seed)`) is returned as given."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dev = _device(device)
     w = _dev_f64(world, dev, 3)
     n = w.shape[0]
     x = image_or_table if isinstance(image_or_table, torch.Tensor) else torch.as_tensor(np.asarray(image_or_table))
@@ -722,9 +723,7 @@ def calibrate_camera_points(obj_points, img_points, img_size, view_mask=None, ma
     view_mask: optional [B,V] (or [V]) - problem b uses the views with a non-zero entry; None = one problem over all views.
     Returns a dict of device tensors: status [B], K4 [B,4], dist [B,5], R [B,V,3,3], T [B,V,3], rms [B], view_rms [B,V],
     std_intrinsics [B,9], iterations [B], and per view homography [V,3,3], view_void [V]."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dev = _device(device)
     obj, img = _board_and_corners(obj_points, img_points, dev)
     nv, n = img.shape[0], img.shape[1]
     if nv > L.CALIB_MAX_VIEWS or n > L.CHESS_MAX_PATTERN:
@@ -755,12 +754,10 @@ def calibrate_camera_points(obj_points, img_points, img_size, view_mask=None, ma
 
 def normxcorr2_general(template, image, mode="same", device=None):
     """`_normxcorr2` for arbitrary operands: float64 map of the mode's size on the GPU (`vbs_normxcorr2_general`)."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
+    dev = _device(device)
     modes = {"full": 0, "same": 1, "valid": 2}
     if mode not in modes:
         raise ValueError("acceptable mode flags are 'valid', 'same', or 'full'")        # scipy's message
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     t = torch.as_tensor(np.asarray(template, dtype=np.float64), device=dev).contiguous()
     im = torch.as_tensor(np.asarray(image, dtype=np.float64), device=dev).contiguous()
     if t.dim() != 2 or im.dim() != 2:
@@ -781,9 +778,7 @@ def normxcorr2_general(template, image, mode="same", device=None):
 
 def calculate_3d(uvd, cam: L.Camera, device=None):
     """float64 [n,3] (u, v, diameter_px) -> (xyz float64 [n,3], ok int32 [n]) on the GPU."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dev = _device(device)
     p = _dev_f64(uvd, dev, 3)
     xyz = torch.empty_like(p)
     ok = torch.empty((p.shape[0],), dtype=torch.int32, device=dev)
@@ -798,9 +793,7 @@ def calculate_3d(uvd, cam: L.Camera, device=None):
 
 def displacement_f64(table64, warmup_frames=0, min_marker_size_px=0.0, max_displacement=50.0, device=None):
     """float64 table [n,m,10] (host or device) -> disp float64 [n,m,5] on the GPU (`vbs_displacement_f64`)."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dev = _device(device)
     t = torch.as_tensor(table64, dtype=torch.float64, device=dev).contiguous()
     n, m = t.shape[0], t.shape[1]
     disp = torch.empty((n, m, L.DISP_COLS), dtype=torch.float64, device=dev)
@@ -815,9 +808,7 @@ def displacement_f64(table64, warmup_frames=0, min_marker_size_px=0.0, max_displ
 def series_stats_f64(disp64, frame_begin=0, cumulative=False, device=None):
     """float64 disp [n,m,5] (host or device, as `displacement_f64` returns it) -> stats float64 [m,5] (and the running sum
     [n,m]) on the GPU (`vbs_series_stats_f64`)."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    dev = _device(device)
     d = torch.as_tensor(disp64, dtype=torch.float64, device=dev).contiguous()
     if d.dim() != 3 or d.shape[2] != L.DISP_COLS or d.shape[0] < 1 or d.shape[1] < 1:
         raise ValueError(f"disp must be [n >= 1, m >= 1, {L.DISP_COLS}]")
@@ -842,9 +833,7 @@ def _pose_args(n, m, start_frame, mode, scale, slots, reject_k, frame_range):
     """`Engine.pose_series`'s argument checks (no device needed): -> (a, b, shell_mode) or ValueError."""
     if mode not in ("plane", "shell"):
         raise ValueError("mode must be 'plane' or 'shell'")
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the table's {n} frames")
+    a, b = _frame_range(frame_range, n, "the table's")
     if not (0 <= int(start_frame) < n):
         raise ValueError(f"start_frame {start_frame} outside the table's {n} frames")
     if not np.isfinite(float(scale)):
@@ -856,931 +845,3 @@ def _pose_args(n, m, start_frame, mode, scale, slots, reject_k, frame_range):
         if idx.size and (idx.min() < 0 or idx.max() >= m):
             raise ValueError(f"slots outside the table's {m} slots")
     return a, b, 1 if mode == "shell" else 0
-
-
-def fir_series_f64(rec, taps, n_values=None, min_coverage=0.5, frame_range=None, device=None):
-    """A normalised zero-phase FIR along time with gaps (`vbs_fir_series_f64`).  rec float64 [n, s, cols] (host or device): col 0
-    the flag (nonzero = valid), cols 1 .. n_values the values (default cols - 1).  `taps`: the FULL odd-length array, refused
-    unless |w[k] - w[K-1-k]| <= 1e-12 max|w|; the means of its pairs are what is used (`filters.half_taps`), so the filter is
-    exactly symmetric.  Returns float64 [b-a, s, 1 + 2 n_values] = flag (0, 1 = valid, 3 = valid and filtered), filtered,
-    residual for the frames [a, b) of `frame_range` (default all); an output does not depend on the range it was asked in."""
-    from .filters import half_taps
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    half = np.ascontiguousarray(half_taps(taps), dtype=np.float64)
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    nv = cols - 1 if n_values is None else int(n_values)
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    if nv < 1:
-        raise ValueError("n_values must be >= 1")
-    out = torch.empty((b - a, s, 1 + 2 * nv), dtype=torch.float64, device=dev)
-    if a == b:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_fir_series_f64(dev.index, _ptr(r), n, s, cols, nv, half.ctypes.data_as(C.c_void_p), half.size,
-                                        float(min_coverage), a, b, _ptr(out),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError(f"vbs_fir_series_f64: bad argument (at most {L.FIR_MAX_TAPS} taps with a positive sum, min_coverage in "
-                         f"(0, 1], 1 <= n_values < cols <= 8)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_fir_series_f64 failed ({rc})")
-    return out
-
-
-# ---- despiking a tracked series (k_robust.hip): rolling median, MAD, the Hampel rule ---------------------------------------------
-def _robust_args(n, s, cols, half_window, k_sigma, min_scale, min_count, n_values, frame_range):
-    """`hampel_series_f64`'s argument checks (no device needed): -> (a, b, n_values, h, min_count) or ValueError."""
-    if n < 1 or s < 1 or not (2 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
-    nv = cols - 1 if n_values is None else int(n_values)
-    if not (1 <= nv < cols):
-        raise ValueError("n_values must be >= 1 and below cols")
-    h = int(half_window)
-    if h != half_window or not (0 <= h <= L.ROBUST_MAX_HALF):
-        raise ValueError(f"half_window must be an integer in [0, {L.ROBUST_MAX_HALF}] (VBS_ROBUST_MAX_HALF)")
-    mc = h + 1 if min_count is None else int(min_count)
-    if (min_count is not None and mc != min_count) or not (1 <= mc <= 2 * h + 1):
-        raise ValueError(f"min_count must be an integer in [1, 2 half_window + 1 = {2 * h + 1}]")
-    if not (np.isfinite(float(k_sigma)) and float(k_sigma) > 0.0):
-        raise ValueError(f"k_sigma {k_sigma} must be finite and > 0")
-    if not (np.isfinite(float(min_scale)) and float(min_scale) >= 0.0):
-        raise ValueError(f"min_scale {min_scale} must be finite and >= 0")
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    return a, b, nv, h, mc
-
-
-def hampel_series_f64(rec, half_window, k_sigma=3.0, min_scale=0.0, min_count=None, n_values=None, frame_range=None,
-                      want_clean=True, device=None):
-    """A gap-aware rolling median and median absolute deviation along time with the Hampel rule (`vbs_hampel_series_f64`).  rec
-    float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default cols - 1).  The
-    window of frame f is the valid frames of [f - h, f + h], h = `half_window` <= VBS_ROBUST_MAX_HALF; an entry is judged when the
-    window holds at least `min_count` (default h + 1) of them, and a valid judged entry is a spike when for any value
-    |x - med| > k_sigma * 1.4826 * mad and > `min_scale` (an absolute floor in the units of the data).  Returns (out, clean) for
-    the frames [a, b) of `frame_range` (default all): out float64 [b-a, s, 2 + 2 n_values] = flag (valid + 2 judged + 4 spike),
-    the population of the window, med, mad - flag 2 is a missing entry whose median is the value to fill the gap with; clean
-    float64 [b-a, s, cols] = those rows of rec bit for bit with the flag of every spike set to 0 (None when `want_clean` is
-    false).  An output does not depend on the range it was asked in."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    a, b, nv, h, mc = _robust_args(n, s, cols, half_window, k_sigma, min_scale, min_count, n_values, frame_range)
-    out = torch.empty((b - a, s, 2 + 2 * nv), dtype=torch.float64, device=dev)
-    clean = torch.empty((b - a, s, cols), dtype=torch.float64, device=dev) if want_clean else None
-    if a == b:
-        return out, clean
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_hampel_series_f64(dev.index, _ptr(r), n, s, cols, nv, h, mc, float(k_sigma), float(min_scale), a, b,
-                                           _ptr(out), _ptr(clean), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError(f"vbs_hampel_series_f64: bad argument (half_window in [0, {L.ROBUST_MAX_HALF}], min_count in "
-                         f"[1, 2 half_window + 1], k_sigma finite and > 0, min_scale finite and >= 0, 1 <= n_values < cols <= 8)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_hampel_series_f64 failed ({rc})")
-    return out, clean
-
-
-# ---- contact maps along a recording (k_field.hip): the smoother in space, the contact patch ------------------------------------
-def _field_args(n, s, cols, P, w_shape, wsum_shape, min_coverage, n_values, frame_range):
-    """`field_map_f64`'s argument checks (no device needed): -> (a, b, n_values) or ValueError."""
-    if n < 1 or s < 1 or not (2 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
-    if tuple(w_shape) != (P, s) or P < 1:
-        raise ValueError(f"W must be [P >= 1, {s}]: one weight per grid point and slot of rec")
-    if wsum_shape is not None and tuple(wsum_shape) != (P,):
-        raise ValueError(f"wsum must be [{P}]")
-    nv = min(cols - 1, 3) if n_values is None else int(n_values)
-    if not (1 <= nv <= 3 and nv < cols):
-        raise ValueError("n_values must be 1 .. 3 and below cols")
-    mc = float(min_coverage)
-    if not (mc > 0.0 and mc <= 1.0):
-        raise ValueError("min_coverage must lie in (0, 1]")
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    if s > L.FIELD_MAX_SLOTS:
-        raise L.VbsError(f"vbs_field_map_f64: {s} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
-    if P > L.FIELD_MAX_POINTS:
-        raise L.VbsError(f"vbs_field_map_f64: {P} grid points exceed VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} "
-                         f"(status {L.VBS_ECAPACITY})")
-    return a, b, nv
-
-
-def field_map_f64(rec, W, wsum=None, min_coverage=0.5, n_values=None, frame_range=None, device=None):
-    """A normalised kernel smoother in space with gaps (`vbs_field_map_f64`), every frame in one launch.  rec float64
-    [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default min(cols - 1, 3)).
-    W float64 [P, s]: non-negative weights of slot m at grid point p (`fields.gaussian_weights`); wsum [P] its full row sums
-    (default `fields.row_sums(W)`, on the host).  Returns float64 [b-a, P, 1 + n_values] = ok, the weighted mean of every value
-    over the valid slots, for the frames [a, b) of `frame_range` (default all): ok where the valid weight is positive and at
-    least min_coverage * wsum, zeros elsewhere.  An output does not depend on the range it was asked in."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    if wsum is None:
-        from .fields import row_sums
-        wsum = row_sums(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else W)
-    w = torch.as_tensor(W, dtype=torch.float64, device=dev).contiguous()
-    ws = torch.as_tensor(wsum, dtype=torch.float64, device=dev).contiguous()
-    n, s, cols = r.shape
-    P = w.shape[0] if w.dim() == 2 else 0
-    a, b, nv = _field_args(n, s, cols, P, w.shape, ws.shape, min_coverage, n_values, frame_range)
-    out = torch.empty((b - a, P, 1 + nv), dtype=torch.float64, device=dev)
-    if a == b:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_field_map_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(w), _ptr(ws), P, float(min_coverage), a, b,
-                                       _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_field_map_f64: bad argument (min_coverage in (0, 1], 1 <= n_values <= 3, n_values < cols <= 8)")
-    if rc == L.VBS_ECAPACITY:
-        raise L.VbsError(f"vbs_field_map_f64: more than VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} slots or VBS_FIELD_MAX_POINTS = "
-                         f"{L.FIELD_MAX_POINTS} grid points (status {rc})")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_field_map_f64 failed ({rc})")
-    return out
-
-
-def _patch_args(F, P, oc, grid_shape, component, sign, threshold):
-    """`patch_stats_f64`'s argument checks (no device needed): -> (n_values, component, sign, thr as the entry takes it)."""
-    nv = oc - 1
-    if F < 0 or P < 1 or not (1 <= nv <= 3):
-        raise ValueError("map must be [F, P >= 1, 2 .. 4]")
-    if tuple(grid_shape) != (P, 2):
-        raise ValueError(f"grid_xy must be [{P}, 2]")
-    c = int(component)
-    if not (-1 <= c < nv):
-        raise ValueError(f"component must be 0 .. {nv - 1}, or -1 for the squared norm")
-    if float(sign) not in (1.0, -1.0):
-        raise ValueError("sign must be +1 or -1")
-    thr = float(threshold)
-    if not (thr >= 0.0):
-        raise ValueError("threshold must be >= 0")
-    if P > L.FIELD_MAX_POINTS:
-        raise L.VbsError(f"vbs_patch_stats_f64: {P} grid points exceed VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} "
-                         f"(status {L.VBS_ECAPACITY})")
-    return nv, c, float(sign), thr * thr if c < 0 else thr
-
-
-def patch_stats_f64(map, grid_xy, component=2, sign=1.0, threshold=0.0, device=None):
-    """The contact patch of every frame of a map (`vbs_patch_stats_f64`).  map float64 [F, P, 1 + n_values] as `field_map_f64`
-    returns it, grid_xy float64 [P, 2].  The score of a covered point is sign * value[component], or for component -1 the squared
-    norm of its values; the patch is the covered points whose score reaches `threshold` (for component -1 `threshold` is a length:
-    its square is what is compared).  Returns float64 [F, 8] = flag (0 nothing covered, 1 no patch, 2 a patch with a centre),
-    covered, count, sum of the scores, score-weighted centre cx, cy, peak score, index of the peak (the first of equal ones)."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    m = torch.as_tensor(map, dtype=torch.float64, device=dev).contiguous()
-    g = torch.as_tensor(grid_xy, dtype=torch.float64, device=dev).contiguous()
-    if m.dim() != 3:
-        raise ValueError("map must be [F, P, 1 + n_values]")
-    F, P, oc = m.shape
-    nv, c, sg, thr = _patch_args(F, P, oc, g.shape, component, sign, threshold)
-    out = torch.empty((F, L.PATCH_COLS), dtype=torch.float64, device=dev)
-    if F == 0:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_patch_stats_f64(dev.index, _ptr(m), F, P, nv, _ptr(g), c, sg, thr, _ptr(out),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_patch_stats_f64: bad argument (component -1 .. n_values-1, sign +-1, threshold >= 0)")
-    if rc == L.VBS_ECAPACITY:
-        raise L.VbsError(f"vbs_patch_stats_f64: more than VBS_FIELD_MAX_POINTS = {L.FIELD_MAX_POINTS} grid points (status {rc})")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_patch_stats_f64 failed ({rc})")
-    return out
-
-
-# ---- displacement spectra along a recording (k_spectrum.hip): the projection onto a basis, the harmonic fit ------------------------
-def _project_args(n, s, cols, basis_shape, n_values):
-    """`project_series_f64`'s argument checks (no device needed): -> (R, n_values) or ValueError."""
-    if n < 1 or s < 1 or not (2 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
-    bs = tuple(basis_shape)
-    if len(bs) != 2 or bs[0] < 1 or bs[1] != n:
-        raise ValueError(f"basis must be [R >= 1, {n}]: one value per basis row and frame of rec")
-    nv = min(cols - 1, 3) if n_values is None else int(n_values)
-    if not (1 <= nv <= 3 and nv < cols):
-        raise ValueError("n_values must be 1 .. 3 and below cols")
-    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS),
-                                 ("basis rows", bs[0], "VBS_PROJ_MAX_ROWS", L.PROJ_MAX_ROWS)):
-        if got > cap:
-            raise L.VbsError(f"vbs_project_series_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
-    return int(bs[0]), nv
-
-
-def project_series_f64(rec, basis, n_values=None, device=None):
-    """The gap-aware projection of every series onto a basis (`vbs_project_series_f64`), a float64 matrix product over the time
-    axis.  rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default
-    min(cols - 1, 3)).  basis float64 [R, n], finite (`spectra.harmonic_basis`).  Returns float64 [s, R, 1 + n_values] = den, num
-    per value: the sums of basis[r, f] and of basis[r, f] * x_v[f, i] over the valid frames of slot i."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    b = torch.as_tensor(basis, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    R, nv = _project_args(n, s, cols, b.shape, n_values)
-    out = torch.empty((s, R, 1 + nv), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_project_series_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(b), R, _ptr(out),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_project_series_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_project_series_f64 failed ({rc})")
-    return out
-
-
-def _fit_args(s, R, oc, Q, min_count, det_min):
-    """`harmonic_fit_f64`'s argument checks (no device needed): -> (n_values, min_count, det_min) or ValueError."""
-    nv, Q, mc, dm = int(oc) - 1, int(Q), int(min_count), float(det_min)
-    if s < 1 or not (1 <= nv <= 3):
-        raise ValueError("proj must be [s >= 1, R, 2 .. 4]")
-    if Q < 1 or Q > (L.PROJ_MAX_ROWS - 1) // 4 or R != 1 + 4 * Q:
-        raise ValueError(f"proj has {R} basis rows: harmonic_fit_f64 needs 1 + 4 Q = {1 + 4 * Q} in the order of "
-                         f"spectra.harmonic_basis, 1 <= Q <= {(L.PROJ_MAX_ROWS - 1) // 4}")
-    if mc < 3:
-        raise ValueError("min_count must be >= 3 (a mean, a cosine and a sine)")
-    if not (0.0 <= dm < 0.25):
-        raise ValueError("det_min must lie in [0, 0.25)")
-    return nv, mc, dm
-
-
-def harmonic_fit_f64(proj, Q, min_count=8, det_min=1e-3, want_fit=True, want_peak=True, device=None):
-    """The floating-mean least-squares fit x ~ c0 + a cos + b sin at every frequency of a `spectra.harmonic_basis`
-    (`vbs_harmonic_fit_f64`).  proj float64 [s, 1 + 4 Q, 1 + n_values] as `project_series_f64` returns it for that basis.  A bin is
-    ok where the series has at least `min_count` valid frames and the determinant of its normal equations exceeds `det_min` N^2
-    (N^2 / 4 is what a whole number of periods without gaps gives).  Returns `(fit, peak)`: fit float64 [s, Q, 1 + 3 n_values] =
-    ok, then a, b and the power p (the drop in the sum of squares) per value, zeros where not ok; peak float64 [s, n_values, 7] =
-    flag (0 too few frames, 1 no ok bin, 2 a peak), N, mean, bin, a, b, p of the ok bin with the largest p (the first of equal
-    ones).  Amplitude and phase: `spectra.amplitude_phase(a, b)`.  `want_fit` / `want_peak` False: None in its place."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    p = torch.as_tensor(proj, dtype=torch.float64, device=dev).contiguous()
-    if p.dim() != 3:
-        raise ValueError("proj must be [s, 1 + 4 Q, 1 + n_values]")
-    if not (want_fit or want_peak):
-        raise ValueError("at least one of fit and peak")
-    s, R, oc = p.shape
-    nv, mc, dm = _fit_args(s, R, oc, Q, min_count, det_min)
-    fit = torch.empty((s, int(Q), 1 + 3 * nv), dtype=torch.float64, device=dev) if want_fit else None
-    peak = torch.empty((s, nv, L.PEAK_COLS), dtype=torch.float64, device=dev) if want_peak else None
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_harmonic_fit_f64(dev.index, _ptr(p), s, R, nv, int(Q), mc, dm, _ptr(fit), _ptr(peak),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_harmonic_fit_f64: bad argument (R == 1 + 4 Q, min_count >= 3, det_min in [0, 0.25))")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_harmonic_fit_f64 failed ({rc})")
-    return fit, peak
-
-
-# ---- shear, torsion and strain along a recording (k_motion.hip): the global affine fit, the fit around every marker -----------------
-_MOTION_WANT = ("grad", "strain", "residual")
-
-
-def _motion_shape(n, s, cols, pos_shape, frame_range):
-    if n < 1 or s < 1 or not (4 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 4 <= cols <= 8]: flag, dX, dY, dZ")
-    if tuple(pos_shape) != (s, 2):
-        raise ValueError(f"pos must be [{s}, 2]: the rest position of every slot of rec")
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    return a, b
-
-
-def _motion_args(n, s, cols, pos_shape, slots, reject_k, frame_range, want):
-    """`motion_series_f64`'s argument checks (no device needed): -> (a, b, want as a tuple) or ValueError / VbsError."""
-    a, b = _motion_shape(n, s, cols, pos_shape, frame_range)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in _MOTION_WANT for w in want):
-        raise ValueError(f"want must name at least one of {_MOTION_WANT}")
-    if not (np.isfinite(float(reject_k)) and float(reject_k) >= 0.0):
-        raise ValueError(f"reject_k {reject_k} must be finite and >= 0 (0 = no rejection)")
-    if slots is not None:
-        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
-        if idx.size and (idx.min() < 0 or idx.max() >= s):
-            raise ValueError(f"slots outside the record's {s} slots")
-    if s > L.FIELD_MAX_SLOTS:
-        raise L.VbsError(f"vbs_motion_series_f64: {s} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
-    return a, b, want
-
-
-def motion_series_f64(rec, pos, slots=None, reject_k=0.0, frame_range=None, want=_MOTION_WANT, device=None):
-    """The affine fit of the displacement field of every frame (`vbs_motion_series_f64`): d_k ~ t_k + g_kx x + g_ky y over the
-    used slots, its invariants and what it leaves.  rec float64 [n, s, cols >= 4] (host or device): col 0 the flag (nonzero =
-    valid), cols 1 .. 3 dX, dY, dZ (`Engine.axis_displacement`'s `axis` as it is); pos float64 [s, 2] the rest positions; `slots`
-    selects markers as `axis_displacement` does; `reject_k > 0`: one round of rejection at reject_k times the rms residual.
-    Returns a dict of float64 device tensors for the frames [a, b) of `frame_range`, with the keys of `want`: `grad` [b-a, 3, 4] =
-    flag (0 no fit, 1, 2 = refitted), t_k, g_kx, g_ky for k = X, Y, Z (a FIR record); `strain` [b-a, 16] = flag, count, n_used,
-    dilation, omega, e1, e2, max_shear, shear_deg, rot_deg, lambda1, lambda2, tilt_deg, rms_inplane, rms_z, worst; `residual`
-    [b-a, s, 4] = (1 kept | 2 rejected, r_X, r_Y, r_Z), zeros where not used: a record for every other series entry."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    p = torch.as_tensor(pos, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    a, b, want = _motion_args(n, s, cols, p.shape, slots, reject_k, frame_range, want)
-    mask = None
-    if slots is not None:
-        mask = torch.zeros((s,), dtype=torch.uint8, device=dev)
-        mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=dev)] = 1
-    shapes = {"grad": (b - a, 3, 4), "strain": (b - a, L.STRAIN_COLS), "residual": (b - a, s, 4)}
-    out = {w: torch.empty(shapes[w], dtype=torch.float64, device=dev) for w in want}
-    if a == b:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_motion_series_f64(dev.index, _ptr(r), n, s, cols, _ptr(p), _ptr(mask), float(reject_k), a, b,
-                                           _ptr(out.get("grad")), _ptr(out.get("strain")), _ptr(out.get("residual")),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_motion_series_f64: bad argument (4 <= cols <= 8, reject_k finite and >= 0, at least one output)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_motion_series_f64 failed ({rc})")
-    return out
-
-
-def _lstrain_args(n, s, cols, pos_shape, nbr_shape, min_count, det_rel, frame_range):
-    """`local_strain_f64`'s argument checks (no device needed): -> (a, b, K) or ValueError / VbsError."""
-    a, b = _motion_shape(n, s, cols, pos_shape, frame_range)
-    ns = tuple(nbr_shape)
-    if len(ns) != 2 or ns[0] != s or not (1 <= ns[1] <= L.STRAIN_MAX_NBR):
-        raise ValueError(f"nbr must be [{s}, 1 <= K <= {L.STRAIN_MAX_NBR}] (`strain.neighbour_lists`)")
-    K = int(ns[1])
-    if not (3 <= int(min_count) <= K + 1):
-        raise ValueError(f"min_count must lie in 3 .. K + 1 = {K + 1}")
-    if not (0.0 <= float(det_rel) < 1.0):
-        raise ValueError("det_rel must lie in [0, 1)")
-    if s > L.FIELD_MAX_SLOTS:
-        raise L.VbsError(f"vbs_local_strain_f64: {s} slots exceed VBS_FIELD_MAX_SLOTS = {L.FIELD_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
-    return a, b, K
-
-
-def local_strain_f64(rec, pos, nbr, min_count=4, det_rel=0.01, frame_range=None, device=None):
-    """The affine fit around every marker (`vbs_local_strain_f64`).  rec, pos as `motion_series_f64`; nbr int32 [s, K] from
-    `strain.neighbour_lists` (an entry outside [0, s) = no neighbour).  Slot i has a result in a frame where it is valid itself,
-    at least `min_count` of i and its neighbours are, and these do not lie close to a line (1 - rho^2 > det_rel).  Returns float64
-    [b-a, s, 8] = cnt, dilation, omega, max_shear, e1, e2, g_Zx, g_Zy (zeros where there is no result): with n_values = 3 a
-    record `field_map_f64` turns into maps of local dilation, torsion and shear."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    p = torch.as_tensor(pos, dtype=torch.float64, device=dev).contiguous()
-    nb = torch.as_tensor(nbr, device=dev).to(torch.int32).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    a, b, K = _lstrain_args(n, s, cols, p.shape, nb.shape, min_count, det_rel, frame_range)
-    out = torch.empty((b - a, s, L.LSTRAIN_COLS), dtype=torch.float64, device=dev)
-    if a == b:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_local_strain_f64(dev.index, _ptr(r), n, s, cols, _ptr(p), _ptr(nb), K, int(min_count), float(det_rel), a, b,
-                                          _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_local_strain_f64: bad argument (4 <= cols <= 8, 1 <= K <= 12, 3 <= min_count <= K + 1, 0 <= det_rel < 1)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_local_strain_f64 failed ({rc})")
-    return out
-
-
-# ---- time-resolved amplitude and phase (k_envelope.hip): the sums of a sliding window at one frequency, the fit of every window ----
-def taps_sum(half):
-    """The ascending sum of all 2h + 1 weights w[k] = half[|k|], k = -h .. h: `sw` of `vbs_window_fit_f64`, as the FIR adds its own."""
-    half = np.asarray(half, dtype=np.float64)
-    sw = np.float64(0.0)
-    for k in range(-(half.size - 1), half.size):
-        sw = sw + half[abs(k)]
-    return float(sw)
-
-
-def _envelope_args(n, s, cols, carrier_shape, half, n_values, frame_range):
-    """`window_moments_f64`'s argument checks (no device needed): -> (n_values, a, b) or ValueError."""
-    if n < 1 or s < 1 or not (2 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
-    if tuple(carrier_shape) != (4, n):
-        raise ValueError(f"carrier must be [4, {n}]: cos, sin of 2 pi nu f and of 2 pi (2 nu) f at every frame of rec (spectra.carrier)")
-    nv = min(cols - 1, 3) if n_values is None else int(n_values)
-    if not (1 <= nv <= 3 and nv < cols):
-        raise ValueError("n_values must be 1 .. 3 and below cols")
-    half = np.asarray(half, dtype=np.float64)
-    if half.ndim != 1 or half.size < 1 or half.size - 1 > L.ENV_MAX_HALF:
-        raise ValueError(f"the window must have 1 .. {2 * L.ENV_MAX_HALF + 1} taps (half_window <= VBS_ENV_MAX_HALF = {L.ENV_MAX_HALF})")
-    if not np.isfinite(half).all() or (half < 0.0).any() or not half[0] > 0.0:
-        raise ValueError("the window's weights must be finite and >= 0, the centre > 0")
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS)):
-        if got > cap:
-            raise L.VbsError(f"vbs_window_moments_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
-    return nv, a, b
-
-
-def window_moments_f64(rec, carrier, taps, n_values=None, frame_range=None, device=None):
-    """The weighted sums of a sliding window at one frequency for every frame and series (`vbs_window_moments_f64`), a banded
-    float64 matrix product over the time axis.  rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols
-    1 .. n_values the values (default min(cols - 1, 3)).  carrier float64 [4, n], finite (`spectra.carrier(n, nu)`).  `taps`: the
-    FULL odd-length symmetric window (`spectra.window_taps`), through `filters.half_taps` as `fir_series_f64` takes its own; at
-    most 2 * 127 + 1 weights, each >= 0, the centre > 0.  Returns float64 [b-a, s, 5 + 4 n_values] = W, C1, S1, C2, S2, then X, XC,
-    XS, XX per value, over the valid frames of [f - h, f + h], for the frames [a, b) of `frame_range` (default all); an output
-    does not depend on the range it was asked in."""
-    from .filters import half_taps
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    half = np.ascontiguousarray(half_taps(taps), dtype=np.float64)
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    c = torch.as_tensor(carrier, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    nv, a, b = _envelope_args(n, s, cols, c.shape, half, n_values, frame_range)
-    out = torch.empty((b - a, s, 5 + 4 * nv), dtype=torch.float64, device=dev)
-    if a == b:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_window_moments_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(c), half.ctypes.data_as(C.c_void_p), half.size,
-                                            a, b, _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_window_moments_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8, finite weights >= 0)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_window_moments_f64 failed ({rc})")
-    return out
-
-
-def _envelope_fit_args(F, s, M, taps_sum, min_coverage, det_min):
-    """`window_fit_f64`'s argument checks (no device needed): -> (n_values, sw, min_coverage, det_min) or ValueError."""
-    nv = (int(M) - 5) // 4
-    if F < 1 or s < 1 or int(M) != 5 + 4 * nv or not (1 <= nv <= 3):
-        raise ValueError("mom must be [F >= 1, s >= 1, 9 | 13 | 17]")
-    sw, mc, dm = float(taps_sum), float(min_coverage), float(det_min)
-    if not (np.isfinite(sw) and sw > 0.0):
-        raise ValueError("taps_sum must be finite and > 0 (engine.taps_sum of the window's half taps)")
-    if not (0.0 < mc <= 1.0):
-        raise ValueError("min_coverage must lie in (0, 1]")
-    if not (0.0 <= dm < 0.25):
-        raise ValueError("det_min must lie in [0, 0.25)")
-    for what, got, name, cap in (("frames", F, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS)):
-        if got > cap:
-            raise L.VbsError(f"vbs_window_fit_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
-    return nv, sw, mc, dm
-
-
-def window_fit_f64(mom, taps_sum, min_coverage=0.5, det_min=1e-3, device=None):
-    """The weighted floating-mean fit x ~ c0 + a cos + b sin of every window (`vbs_window_fit_f64`).  mom float64
-    [F, s, 5 + 4 n_values] as `window_moments_f64` returns it; `taps_sum` the ascending sum of the window's weights
-    (`engine.taps_sum(filters.half_taps(taps))`).  A window is ok where W > 0, W >= `min_coverage` x taps_sum and the determinant
-    of its normal equations exceeds `det_min` W^2 (W^2 / 4 is what a whole number of periods without gaps gives).  Returns float64
-    [F, s, 1 + 5 n_values] = ok, then a, b, the power p, c0 and the weighted sum of squared deviations M2 per value; zeros where
-    not ok.  Amplitude and phase: `spectra.amplitude_phase(a, b)`."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    m = torch.as_tensor(mom, dtype=torch.float64, device=dev).contiguous()
-    if m.dim() != 3:
-        raise ValueError("mom must be [F, s, 5 + 4 n_values]")
-    F, s, M = m.shape
-    nv, sw, mc, dm = _envelope_fit_args(F, s, M, taps_sum, min_coverage, det_min)
-    out = torch.empty((F, s, 1 + 5 * nv), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_window_fit_f64(dev.index, _ptr(m), F, s, nv, sw, mc, dm, _ptr(out),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_window_fit_f64: bad argument (taps_sum > 0, min_coverage in (0, 1], det_min in [0, 0.25))")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_window_fit_f64 failed ({rc})")
-    return out
-
-
-# ---- principal modes of the displacement field (k_modes.hip): cross moments, covariance, leading eigenpairs, scores -----------------
-def _moments_args(n, s, cols, shift_shape, n_values):
-    """`cross_moments_f64`'s argument checks (no device needed): -> n_values or ValueError / VbsError."""
-    if n < 1 or s < 1 or not (2 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
-    nv = min(cols - 1, 3) if n_values is None else int(n_values)
-    if not (1 <= nv <= 3 and nv < cols):
-        raise ValueError("n_values must be 1 .. 3 and below cols")
-    if shift_shape is not None and tuple(shift_shape) != (s, nv):
-        raise ValueError(f"shift must be [{s}, {nv}]: one value per slot and value column")
-    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_MOM_MAX_SLOTS", L.MOM_MAX_SLOTS)):
-        if got > cap:
-            raise L.VbsError(f"vbs_cross_moments_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
-    return nv
-
-
-def cross_moments_f64(rec, shift=None, n_values=None, device=None):
-    """The cross moments of all pairs of series (`vbs_cross_moments_f64`), a symmetric float64 matrix product over the time axis.
-    rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values the values (default
-    min(cols - 1, 3)).  `shift` float64 [s, n_values] (default none) is subtracted from every valid value first: pass the series'
-    means.  Returns float64 [s, s, 4, 4]: [i, j, v, w] the sum over the frames of col_v(i) col_w(j), the columns of a slot being its
-    shifted values (0 beyond n_values) and its flag as 1.0 / 0.0, all 0 where the slot is invalid - so [.., 3, 3] is the number
-    of frames where both slots are valid and row / column 3 the sums pairwise-complete centring needs."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    sh = None if shift is None else torch.as_tensor(shift, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    nv = _moments_args(n, s, cols, None if sh is None else sh.shape, n_values)
-    out = torch.empty((s, s, 4, 4), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_cross_moments_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(sh), _ptr(out),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_cross_moments_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_cross_moments_f64 failed ({rc})")
-    return out
-
-
-_COV_MODES = {"pairwise": 0, "filled": 1, 0: 0, 1: 1}
-
-
-def _covariance_args(mom_shape, n_values, mode, min_count, denom, mask_shape):
-    """`covariance_f64`'s argument checks (no device needed): -> (s, n_values, mode, min_count, denom) or ValueError / VbsError."""
-    ms = tuple(mom_shape)
-    if len(ms) != 4 or ms[0] < 1 or ms[0] != ms[1] or ms[2:] != (4, 4):
-        raise ValueError("mom must be [s >= 1, s, 4, 4] (`cross_moments_f64`)")
-    nv = int(n_values)
-    if not (1 <= nv <= 3):
-        raise ValueError("n_values must be 1 .. 3")
-    if mode not in _COV_MODES:
-        raise ValueError("mode must be 'pairwise' (0) or 'filled' (1)")
-    m, mc = _COV_MODES[mode], int(min_count)
-    if mc < 2:
-        raise ValueError("min_count must be >= 2")
-    d = 1.0 if denom is None else float(denom)
-    if m == 1 and (denom is None or not (np.isfinite(d) and d > 0.0)):
-        raise ValueError("mode 'filled' needs a finite denom > 0 (n - 1)")
-    if mask_shape is not None and tuple(mask_shape) != (ms[0],):
-        raise ValueError(f"slot_mask must be [{ms[0]}]")
-    if ms[0] > L.MOM_MAX_SLOTS:
-        raise L.VbsError(f"vbs_covariance_f64: {ms[0]} slots exceed VBS_MOM_MAX_SLOTS = {L.MOM_MAX_SLOTS} (status {L.VBS_ECAPACITY})")
-    return ms[0], nv, m, mc, d
-
-
-def covariance_f64(mom, n_values, mode="filled", min_count=2, denom=None, slot_mask=None, want_ok=False, device=None):
-    """The covariance of all pairs of value columns from their cross moments (`vbs_covariance_f64`).  mom float64 [s, s, 4, 4] as
-    `cross_moments_f64` returns it.  mode 'pairwise': every pair over the frames where both are valid, unbiased, possibly
-    indefinite; 'filled': the Gram matrix of the data with gaps filled by the series' means over `denom` (n - 1), positive
-    semidefinite while no pair falls below `min_count`.  A pair with fewer than `min_count` common frames, or with a slot whose `slot_mask` (uint8 [s]) is 0, gives exact
-    zeros.  Returns float64 [C, C], C = s n_values, column c = i n_values + v; with `want_ok` also the uint8 [s, s] pair flags."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    m = torch.as_tensor(mom, dtype=torch.float64, device=dev).contiguous()
-    mk = None if slot_mask is None else torch.as_tensor(slot_mask, device=dev).to(torch.uint8).contiguous()
-    s, nv, md, mc, d = _covariance_args(m.shape, n_values, mode, min_count, denom, None if mk is None else mk.shape)
-    cov = torch.empty((s * nv, s * nv), dtype=torch.float64, device=dev)
-    ok = torch.empty((s, s), dtype=torch.uint8, device=dev) if want_ok else None
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_covariance_f64(dev.index, _ptr(m), s, nv, md, mc, d, _ptr(mk), _ptr(cov), _ptr(ok),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_covariance_f64: bad argument (mode 0 or 1, min_count >= 2, denom > 0)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_covariance_f64 failed ({rc})")
-    return (cov, ok) if want_ok else cov
-
-
-def _modes_args(a_shape, r, iters, tiny):
-    """`leading_modes_f64`'s argument checks (no device needed): -> (C, r, iters, tiny) or ValueError / VbsError."""
-    sh = tuple(a_shape)
-    if len(sh) != 2 or sh[0] < 1 or sh[0] != sh[1]:
-        raise ValueError("A must be [C >= 1, C], symmetric")
-    Cn, r, it, tn = sh[0], int(r), int(iters), float(tiny)
-    if not (1 <= r <= min(Cn, L.MODES_MAX)):
-        raise ValueError(f"n_modes must lie in 1 .. min(C, VBS_MODES_MAX = {L.MODES_MAX})")
-    if not (0 <= it <= L.MODES_MAX_ITERS):
-        raise ValueError(f"iters must lie in 0 .. {L.MODES_MAX_ITERS}")
-    if not (0.0 <= tn < 1.0):
-        raise ValueError("tiny must lie in [0, 1)")
-    if Cn > L.MODES_MAX_DIM:
-        raise L.VbsError(f"vbs_leading_modes_f64: {Cn} columns exceed VBS_MODES_MAX_DIM = {L.MODES_MAX_DIM} (status {L.VBS_ECAPACITY})")
-    return Cn, r, it, tn
-
-
-def leading_modes_f64(A, n_modes, iters=48, tiny=1e-24, work=None, device=None):
-    """The `n_modes` <= 16 leading eigenpairs of a symmetric float64 [C, C] matrix (`vbs_leading_modes_f64`) by orthogonal
-    iteration from a fixed start block with a FIXED number of iterations: deterministic, nothing is tested for convergence, and
-    `resid` says what was reached.  The iteration finds the largest |lambda| (an indefinite A may give negative values); the
-    values come descending.  A column whose squared norm falls below `tiny` times the largest is dropped (a rank-deficient A).
-    `work`: an optional float64 device tensor of 2 * C * 16 elements to reuse.  Returns `(values [r], modes [r, C], resid [r],
-    info int32 [2] = rank found, columns dropped)`: every mode has unit norm and its entry of largest magnitude positive."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    a = torch.as_tensor(A, dtype=torch.float64, device=dev).contiguous()
-    Cn, r, it, tn = _modes_args(a.shape, n_modes, iters, tiny)
-    if work is None:
-        work = torch.empty((2 * Cn * L.MODES_MAX,), dtype=torch.float64, device=dev)
-    elif work.dtype != torch.float64 or work.device != dev or not work.is_contiguous() or work.numel() < 2 * Cn * L.MODES_MAX:
-        raise ValueError(f"work must be a contiguous float64 tensor of 2 * C * {L.MODES_MAX} elements on {dev}")
-    values = torch.empty((r,), dtype=torch.float64, device=dev)
-    modes = torch.empty((r, Cn), dtype=torch.float64, device=dev)
-    resid = torch.empty((r,), dtype=torch.float64, device=dev)
-    info = torch.empty((2,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_leading_modes_f64(dev.index, _ptr(a), Cn, r, it, tn, _ptr(work), _ptr(values), _ptr(modes), _ptr(resid),
-                                           _ptr(info), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_leading_modes_f64: bad argument (1 <= r <= min(C, 16), iters >= 0, 0 <= tiny < 1)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_leading_modes_f64 failed ({rc})")
-    return values, modes, resid, info
-
-
-def _scores_args(n, s, cols, center_shape, modes_shape, n_values, min_coverage, frame_range):
-    """`mode_scores_f64`'s argument checks (no device needed): -> (n_values, r, min_coverage, a, b) or ValueError / VbsError."""
-    nv = _moments_args(n, s, cols, None, n_values)
-    Cn = s * nv
-    ms = tuple(modes_shape)
-    if len(ms) != 2 or not (1 <= ms[0] <= L.MODES_MAX) or ms[1] != Cn:
-        raise ValueError(f"modes must be [1 .. {L.MODES_MAX}, {Cn}] (`leading_modes_f64`)")
-    if tuple(center_shape) != (Cn,):
-        raise ValueError(f"center must be [{Cn}]: one value per value column of rec")
-    mc = float(min_coverage)
-    if not (0.0 < mc <= 1.0):
-        raise ValueError("min_coverage must lie in (0, 1]")
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    return nv, int(ms[0]), mc, a, b
-
-
-def mode_scores_f64(rec, center, modes, n_values=None, min_coverage=0.5, frame_range=None, want_energy=True, device=None):
-    """The score of every mode in every frame (`vbs_mode_scores_f64`): the least-squares amplitude of the mode over the columns
-    that are valid in the frame.  rec float64 [n, s, cols]; center float64 [s n_values] (what the covariance was centred on);
-    modes float64 [r, s n_values], unit norm.  Returns `(scores, energy)` for the frames [a, b) of `frame_range`: scores float64
-    [b-a, r, 3] = flag, score, den - den the share of the mode that was seen, flag 1 where it reaches `min_coverage`, else
-    (0, 0, den) - a record every series entry takes (cols 3, n_values 1, s = r); energy float64 [b-a, 2] = the number of valid
-    columns and the sum of their squared centred values (None without `want_energy`)."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r_ = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    c = torch.as_tensor(center, dtype=torch.float64, device=dev).contiguous()
-    m = torch.as_tensor(modes, dtype=torch.float64, device=dev).contiguous()
-    if r_.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r_.shape
-    nv, r, mc, a, b = _scores_args(n, s, cols, c.shape, m.shape, n_values, min_coverage, frame_range)
-    scores = torch.empty((b - a, r, 3), dtype=torch.float64, device=dev)
-    energy = torch.empty((b - a, 2), dtype=torch.float64, device=dev) if want_energy else None
-    if a == b:
-        return scores, energy
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_mode_scores_f64(dev.index, _ptr(r_), n, s, cols, nv, _ptr(c), _ptr(m), r, mc, a, b, _ptr(scores), _ptr(energy),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_mode_scores_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8, min_coverage in (0, 1])")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_mode_scores_f64 failed ({rc})")
-    return scores, energy
-
-
-# ---- marker velocity, acceleration and gap filling (k_kinematics.hip): the moments of a local polynomial fit, the fit -------------
-KIN_PIV_REL = 5e-3             # the default `piv_rel`: a gap-free one-sided window keeps its full degree (DESIGN 4.20's table)
-
-
-def n_kin_sums(degree, n_values):
-    """M of `poly_moments_f64`: (2d + 1) + (d + 2) n_values."""
-    return 2 * int(degree) + 1 + (int(degree) + 2) * int(n_values)
-
-
-def _kin_args(n, s, cols, half_window, degree, window, n_values, frame_range):
-    """`poly_moments_f64`'s argument checks (no device needed): -> (h, d, n_values, a, b) or ValueError."""
-    if n < 1 or s < 1 or not (2 <= cols <= 8):
-        raise ValueError("rec must be [n >= 1, s >= 1, 2 <= cols <= 8]")
-    nv = min(cols - 1, 3) if n_values is None else int(n_values)
-    if not (1 <= nv <= 3 and nv < cols):
-        raise ValueError("n_values must be 1 .. 3 and below cols")
-    h, d = int(half_window), int(degree)
-    if h != half_window or not (0 <= h <= L.KIN_MAX_HALF):
-        raise ValueError(f"half_window must be an integer in 0 .. VBS_KIN_MAX_HALF = {L.KIN_MAX_HALF}")
-    if d != degree or not (0 <= d <= L.KIN_MAX_DEGREE):
-        raise ValueError(f"degree must be an integer in 0 .. VBS_KIN_MAX_DEGREE = {L.KIN_MAX_DEGREE}")
-    if isinstance(window, str) and window not in ("hann", "rect"):
-        raise ValueError('window must be "hann", "rect" or 2 half_window + 1 weights')
-    a, b = (0, n) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    if not (0 <= a <= b <= n):
-        raise ValueError(f"frame_range {frame_range} outside the {n} frames")
-    for what, got, name, cap in (("frames", n, "VBS_PROJ_MAX_FRAMES", L.PROJ_MAX_FRAMES), ("slots", s, "VBS_PROJ_MAX_SLOTS", L.PROJ_MAX_SLOTS)):
-        if got > cap:
-            raise L.VbsError(f"vbs_poly_moments_f64: {got} {what} exceed {name} = {cap} (status {L.VBS_ECAPACITY})")
-    return h, d, nv, a, b
-
-
-def poly_moments_f64(rec, half_window, degree, window="hann", n_values=None, frame_range=None, device=None):
-    """The moments of a gap-aware weighted local polynomial fit along time for every frame and series (`vbs_poly_moments_f64`,
-    DESIGN 4.20): several banded float64 matrix products over one staged operand.  rec float64 [n, s, cols] (host or device): col
-    0 the flag (nonzero = valid), cols 1 .. n_values the values (default min(cols - 1, 3)).  The window is
-    `filters.poly_window(half_window, window)` ("hann", "rect" or 2h + 1 symmetric weights), the tap rows `filters.poly_taps(half_window, degree, window)`.  Returns float64
-    [b-a, s, (2d + 1) + (d + 2) n_values] = S_0 .. S_2d, then X_0 .. X_d, XX per value, over the valid frames of [f - h, f + h], for
-    the frames [a, b) of `frame_range` (default all); an output does not depend on the range it was asked in."""
-    from .filters import half_taps, poly_window
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    n, s, cols = r.shape
-    h, d, nv, a, b = _kin_args(n, s, cols, half_window, degree, window, n_values, frame_range)
-    half = np.ascontiguousarray(half_taps(poly_window(h, window)), dtype=np.float64)
-    out = torch.empty((b - a, s, n_kin_sums(d, nv)), dtype=torch.float64, device=dev)
-    if a == b:
-        return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vbs_poly_moments_f64(dev.index, _ptr(r), n, s, cols, nv, half.ctypes.data_as(C.c_void_p), half.size, d, a, b,
-                                          _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == L.VBS_EINVAL:
-        raise ValueError("vbs_poly_moments_f64: bad argument (1 <= n_values <= 3, n_values < cols <= 8, 0 <= degree <= 3)")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"vbs_poly_moments_f64 failed ({rc})")
-    return out
-
-
-def kin_thresholds(sw, piv_full, min_coverage=0.5, piv_rel=KIN_PIV_REL, half_window=None):
-    """thr [d + 1] of `vbs_poly_fit_f64`: thr[0] = min_coverage * sw, thr[k] = piv_rel * piv_full[k], one IEEE product each; with
-    `half_window`, +inf for the orders k >= 2h + 1, which a window of 2h + 1 frames cannot determine (their full pivot is zero up
-    to rounding, and a rounding is not a pivot)."""
-    piv = np.asarray(piv_full, dtype=np.float64)
-    thr = np.float64(piv_rel) * piv
-    thr[0] = np.float64(min_coverage) * np.float64(sw)
-    if half_window is not None:
-        thr[2 * int(half_window) + 1:] = np.inf
-    return thr
-
-
-_KIN_PIVOTS = {}               # (h, d, window name) -> (sw, piv_full) of `filters.poly_taps`
-
-
-def _kin_fit_args(F, s, M, n, cols, half_window, degree, window, n_values, min_coverage, piv_rel, fill_degree, frame_range):
-    """`poly_fit_f64`'s argument checks (no device needed): -> (h, d, n_values, thr [d + 1], fill_degree, a, b) or ValueError."""
-    from .filters import poly_taps
-    h, d, nv, a, b = _kin_args(n, s, cols, half_window, degree, window, n_values, frame_range)
-    if (int(F), int(M)) != (b - a, n_kin_sums(d, nv)):
-        raise ValueError(f"mom must be [{b - a}, {s}, {n_kin_sums(d, nv)}]: the moments of the frames {a}:{b} at degree {d} "
-                         f"and {nv} values")
-    mc, pr = float(min_coverage), float(piv_rel)
-    if not (0.0 < mc <= 1.0):
-        raise ValueError("min_coverage must lie in (0, 1]")
-    if not (0.0 <= pr < 1.0):
-        raise ValueError("piv_rel must lie in [0, 1)")
-    fd = int(fill_degree)
-    if fd != fill_degree or not (0 <= fd <= L.KIN_MAX_DEGREE):
-        raise ValueError(f"fill_degree must be an integer in 0 .. {L.KIN_MAX_DEGREE} (above `degree` nothing is filled)")
-    if isinstance(window, str):
-        if (h, d, window) not in _KIN_PIVOTS:                    # (host loops over the window: formed once per design)
-            _KIN_PIVOTS[(h, d, window)] = poly_taps(h, d, window)[1:]
-        sw, piv = _KIN_PIVOTS[(h, d, window)]
-    else:
-        _, sw, piv = poly_taps(h, d, window)
-    return h, d, nv, kin_thresholds(sw, piv, mc, pr, h), fd, a, b
-
-
-def poly_fit_f64(mom, rec, half_window, degree, window="hann", n_values=None, min_coverage=0.5, piv_rel=KIN_PIV_REL,
-                 fill_degree=1, want_filled=False, frame_range=None, device=None):
-    """The local polynomial fit of every window with its fallback in degree (`vbs_poly_fit_f64`).  mom float64
-    [b-a, s, M] as `poly_moments_f64(rec, half_window, degree, window, n_values, frame_range)` returns it, rec the record itself.
-    A window keeps the largest degree q <= d whose pivots D_0 .. D_q all exceed their thresholds: D_0 = S_0 > `min_coverage` x the
-    window's sum, D_k > `piv_rel` x the pivot of the gap-free full window.  Returns `fit` float64 [b-a, s, 2 + (d + 2) n_values] =
-    flag (centre valid + 2 (q >= 0) + 4 (q == d)), q, then per value the derivatives y_0 .. y_d at the centre in units of frames
-    (0 above q) and the weighted residual sum of squares; with `want_filled` (fit, filled): `filled` float64 [b-a, s, cols], the
-    valid rows of rec bit for bit, flag 2.0 and y_0 where the entry is missing and q >= `fill_degree`, zeros otherwise -
-    a record every other entry of this module takes as it is."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    m = torch.as_tensor(mom, dtype=torch.float64, device=dev).contiguous()
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    if m.dim() != 3 or r.dim() != 3 or m.shape[1] != r.shape[1]:
-        raise ValueError("mom must be [F, s, M] and rec [n, s, cols] with the same s")
-    F, s, M = m.shape
-    n, _, cols = r.shape
-    h, d, nv, thr, fd, a, b = _kin_fit_args(F, s, M, n, cols, half_window, degree, window, n_values, min_coverage, piv_rel,
-                                            fill_degree, frame_range)
-    fit = torch.empty((F, s, 2 + (d + 2) * nv), dtype=torch.float64, device=dev)
-    filled = torch.empty((F, s, cols), dtype=torch.float64, device=dev) if want_filled else None
-    if F:
-        thr = np.ascontiguousarray(thr, dtype=np.float64)
-        with torch.cuda.device(dev):
-            rc = L.lib().vbs_poly_fit_f64(dev.index, _ptr(m), _ptr(r), n, s, cols, nv, d, h, thr.ctypes.data_as(C.c_void_p), fd, a, b,
-                                          _ptr(fit), _ptr(filled) if want_filled else None,
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc == L.VBS_EINVAL:
-            raise ValueError("vbs_poly_fit_f64: bad argument (thresholds >= 0, 0 <= fill_degree <= 3)")
-        if rc != L.VBS_OK:
-            raise L.VbsError(f"vbs_poly_fit_f64 failed ({rc})")
-    return (fit, filled) if want_filled else fit
-
-
-# ---- the probe-indentation validation (k_steps.hip): steps, dwells ---------------------------------------------------------------
-def _steps_call(name, what, fn):
-    rc = fn()
-    if rc == L.VBS_EINVAL:
-        raise ValueError(f"{name}: bad argument ({what})")
-    if rc != L.VBS_OK:
-        raise L.VbsError(f"{name} failed ({rc})")
-
-
-def _record(rec, n_values, device):
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(rec, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1:
-        raise ValueError("rec must be [n >= 1, s >= 1, cols]")
-    nv = r.shape[2] - 1 if n_values is None else int(n_values)
-    if nv < 1:
-        raise ValueError("n_values must be >= 1")
-    return dev, r, nv
-
-
-def step_response_f64(rec, window, n_values=None, min_count=None, device=None):
-    """A step detector along time with gaps (`vbs_step_response_f64`): per frame the mean of the valid frames of [f, f+window)
-    minus that of [f-window, f).  rec float64 [n, s, cols] (host or device): col 0 the flag (nonzero = valid), cols 1 .. n_values
-    the values (default cols - 1).  `min_count` (default (window + 1) // 2): the valid frames each side needs.  Returns float64
-    [n, s, 2 + n_values] = ok, score (the SQUARED norm of the difference), the difference per value; zero where not ok."""
-    dev, r, nv = _record(rec, n_values, device)
-    n, s, cols = r.shape
-    w = int(window)
-    mc = (w + 1) // 2 if min_count is None else int(min_count)
-    out = torch.empty((n, s, 2 + nv), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _steps_call("vbs_step_response_f64", f"1 <= min_count <= window <= {L.STEP_MAX_WINDOW}, 1 <= n_values < cols <= 8",
-                    lambda: L.lib().vbs_step_response_f64(dev.index, _ptr(r), n, s, cols, nv, w, mc, _ptr(out),
-                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    return out
-
-
-def find_steps_f64(resp, window, threshold, max_steps=L.STEP_MAX_STEPS, device=None):
-    """The peaks of a step response (`vbs_find_steps_f64`): frame f is a step where it is ok, its score reaches `threshold`
-    squared and no ok frame within `window` on either side has a larger score (of equal ones the earliest wins).  resp float64
-    [n, s, >= 2] as `step_response_f64` returns it.  Returns int32 [s, 1 + max_steps]: the number of steps found (more than
-    `max_steps` = an overflow of that series), the first `max_steps` of them in ascending order, then -1."""
-    if not torch.cuda.is_available():
-        raise L.VbsError("no GPU visible: vbs_amd has no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    r = torch.as_tensor(resp, dtype=torch.float64, device=dev).contiguous()
-    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1:
-        raise ValueError("resp must be [n >= 1, s >= 1, cols >= 2]")
-    n, s, cols = r.shape
-    ms = int(max_steps)
-    steps = torch.empty((s, 1 + max(ms, 0)), dtype=torch.int32, device=dev)
-    thr = float(threshold)
-    with torch.cuda.device(dev):
-        _steps_call("vbs_find_steps_f64", f"1 <= window <= {L.STEP_MAX_WINDOW}, threshold >= 0, 1 <= max_steps <= "
-                    f"{L.STEP_MAX_STEPS}, 2 <= cols <= 9",
-                    lambda: L.lib().vbs_find_steps_f64(dev.index, _ptr(r), n, s, cols, int(window), thr * thr, ms, _ptr(steps),
-                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    return steps
-
-
-def dwell_stats_f64(rec, steps, guard, n_values=None, device=None):
-    """The statistics of the dwells between steps (`vbs_dwell_stats_f64`).  rec float64 [n, s, cols] as `step_response_f64`
-    takes it; steps int32 [s or 1, 1 + max_steps] as `find_steps_f64` returns it (one row: the list is shared by all series);
-    `guard`: frames left out on either side of a step.  Returns float64 [s, max_steps + 1, 3 + 2 n_values] = begin, end, count,
-    mean per value, M2 per value (sum of squared deviations; std = sqrt(M2 / (count - 1))); rows past the last dwell are
-    (-1, -1, 0, NaN ...)."""
-    dev, r, nv = _record(rec, n_values, device)
-    n, s, cols = r.shape
-    st = torch.as_tensor(steps, dtype=torch.int32, device=dev).contiguous()
-    if st.dim() != 2 or st.shape[1] < 2:
-        raise ValueError("steps must be [s or 1, 1 + max_steps]")
-    ms = st.shape[1] - 1
-    out = torch.empty((s, ms + 1, 3 + 2 * nv), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _steps_call("vbs_dwell_stats_f64", f"steps rows = s or 1, 1 <= max_steps <= {L.STEP_MAX_STEPS}, guard >= 0, "
-                    "1 <= n_values < cols <= 8",
-                    lambda: L.lib().vbs_dwell_stats_f64(dev.index, _ptr(r), n, s, cols, nv, _ptr(st), st.shape[0], ms, int(guard),
-                                                        _ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    return out

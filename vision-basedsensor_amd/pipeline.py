@@ -892,7 +892,7 @@ MODE_FRAME_COLUMNS = ("frameno", "mode", "flag", "score", "coverage", "value", "
 
 def _modal_args(n, m, n_modes, iters, mode, ref_frame, slot_mask, min_coverage):
     """`modal_analysis`'s argument checks (no device needed): -> (n_modes, iters, slot indices or None)."""
-    from .engine import _COV_MODES
+    from .analysis import _COV_MODES
     r, it = int(n_modes), int(iters)
     if n < 2:
         raise ValueError("a covariance needs at least 2 frames")
@@ -1002,7 +1002,7 @@ KINEMATIC_FRAME_COLUMNS = ("frameno", "marker_id", "axis", "displacement", "velo
 
 def _kinematic_args(n, m, half_window, degree, window, ref_frame, min_coverage, piv_rel, onset_frac, axis="z"):
     """`kinematic_analysis`'s argument checks (no device needed): -> (h, d, axis index) or ValueError."""
-    from .engine import _kin_args
+    from .analysis import _kin_args
     h, d, _, _, _ = _kin_args(max(n, 1), max(m, 1), 4, half_window, degree, window, 3, None)
     if n < 1 or m < 1:
         raise ValueError("the table must have at least one frame and one slot")
