@@ -1194,6 +1194,50 @@ int vbs_mode_scores_f64(int device, const double* rec, int n, int s, int cols, i
                         const double* modes, int r, double min_coverage, int frame_begin, int frame_end, double* scores,
                         double* energy, void* stream);
 
+/* vbs_retrack - re-track a recording from its detections, ALONG TIME (ours: the reference tracks every frame alone, against
+ * the first-frame positions, and lets two IDs take one detection - vbs_track is that rule and stays what it is).  Handle-free.
+ *   det [dev] float64 [n,max_det,VBS_DET_COLS] and counts [dev] int32 [n] as vbs_track_to_3d writes them; ref_xy [dev] float64
+ *   [m_ref,2]; state_in [dev] float64 [m_ref,VBS_RETRACK_STATE_COLS] = px, py, vx, vy, age, seen per slot, or NULL for the
+ *   initial state p = ref_xy, v = 0, age = 0, seen = 0.
+ * THE RULE.  For frame f, in frame order, per slot j, all in float64 without contraction; every expression and tie-break
+ * below is part of the interface:
+ *   1. prediction   k = age + 1,  qx = px + vx*k,  qy = py + vy*k.
+ *   2. counts[f] < 0: the frame is unusable, every slot is unmatched and info[f].used = 0.  Else cnt = min(counts[f], max_det);
+ *      no row of det at or beyond cnt is used.
+ *   3. candidates   a detection with a non-finite x or y is never one.  dx = qx - x_i, dy = qy - y_i, d2 = dx*dx + dy*dy; the
+ *      pair (j, i) is a candidate iff d2 <= gate*gate and, when max_travel is finite, (x_i - ox)*(x_i - ox) + (y_i - oy)*(y_i -
+ *      oy) <= max_travel*max_travel with (ox, oy) = ref_xy[j].
+ *   4. one-to-one   sort the candidate pairs by the key (d2, j, i) ascending and walk them: a pair is taken iff neither its slot
+ *      nor its detection has been taken.  (The kernel runs the equivalent rounds: every free slot names its best free candidate
+ *      by (d2, i), every free detection its best free slot by (d2, j) among ALL free slots that hold it as a candidate, mutual
+ *      pairs are fixed, until no free slot has a free candidate.)
+ *   5. update       matched to i with seen == 1: ux = (x_i - px)/k, vx <- vx + vel_gain*(ux - vx), the same for y; with seen
+ *      == 0 the velocity stays as it is.  Either way p <- (x_i, y_i), age <- 0, seen <- 1.  Unmatched: age <- age + 1, and
+ *      v <- 0 once age > max_coast.
+ * Defaults of the shim: gate 10, max_travel +inf, vel_gain 0.5, max_coast 5.
+ * Outputs, each may be NULL (all of assign, table and state_out NULL: VBS_EINVAL):
+ *   assign [dev] int32 [n,m_ref]     the detection index, or -1
+ *   table [dev] float32 [n,m_ref,VBS_TABLE_COLS]  rows exactly as vbs_track writes them: VBS_FLAG_TRACKED, columns 1-5 the
+ *                                    detection cast once to float32, column 9 the index, X Y Z zero; vbs_solve3d fills it in place
+ *   dist2 [dev] float64 [n,m_ref]    d2 of the accepted pair, or -1
+ *   info [dev] int32 [n,VBS_RETRACK_INFO_COLS] = used, matched, with_candidate (slots with >= 1 candidate), contested (slots
+ *                                    with a candidate whose outcome is not their own best candidate by (d2, i); a slot left
+ *                                    unmatched counts)
+ *   state_out [dev] float64 [m_ref,VBS_RETRACK_STATE_COLS]: frames [0, k) and then [k, n) from that state give what [0, n) gives.
+ *   workspace [dev], 8-byte aligned, of vbs_retrack_workspace bytes for the same n, m_ref, max_det (the cell grid of every
+ *   frame, and the assignment when `assign` is NULL); the call allocates nothing.
+ * A null det, counts, ref_xy or workspace, n < 0, m_ref < 1, max_det < 1, a NaN or negative gate, vel_gain outside [0, 1] or
+ * max_coast < 0: VBS_EINVAL; m_ref or max_det above VBS_RETRACK_MAX: VBS_ECAPACITY, after the arguments; both before a device is
+ * selected.  Results do not depend on the path a frame takes: the cell lists need a gate <= 4095 and cell coordinates below
+ * 2^30, any other frame (or slot) scans every detection. */
+#define VBS_RETRACK_MAX        1024  /* m_ref and max_det at most                                             */
+#define VBS_RETRACK_STATE_COLS 6     /* px, py, vx, vy, age, seen                                             */
+#define VBS_RETRACK_INFO_COLS  4     /* used, matched, with_candidate, contested                              */
+int64_t vbs_retrack_workspace(int n, int m_ref, int max_det);
+int vbs_retrack(int device, const double* det, const int32_t* counts, int n, int max_det, const double* ref_xy, int m_ref,
+                const double* state_in, double gate, double max_travel, double vel_gain, int max_coast, int32_t* assign,
+                float* table, double* dist2, int32_t* info, double* state_out, void* workspace, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

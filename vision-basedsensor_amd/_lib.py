@@ -28,6 +28,7 @@ PNP_SAMPLE, PNP_MAX_POINTS, PNP_MAX_HYPOTHESES, PNP_FEW_POINTS, PNP_NO_HYPOTHESI
 CHESS_MAX_CANDIDATES, CHESS_MAX_PATTERN, CHESS_MAX_WIN = 256, 256, 15
 CALIB_MAX_VIEWS, CALIB_FEW_VIEWS, CALIB_DEGENERATE = 64, 1, 2
 IDS_MAX_MARKERS, IDS_MAX_LAYERS = 1024, 16
+RETRACK_MAX, RETRACK_STATE_COLS, RETRACK_INFO_COLS = 1024, 6, 4
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -42,6 +43,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_window_means", "vbs_displacement_from_frame", "vbs_mjpeg_scan_batch", "vbs_mjpeg_huffman_device",
            "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers", "vbs_pnp_ransac",
            "vbs_chess_workspace", "vbs_chess_corners", "vbs_corner_subpix", "vbs_calibrate_camera",
+           "vbs_retrack_workspace", "vbs_retrack",
            "vbs_axis_displacement", "vbs_fir_series_f64",
            "vbs_step_response_f64", "vbs_find_steps_f64", "vbs_dwell_stats_f64", "vbs_pose_series",
            "vbs_field_map_f64", "vbs_patch_stats_f64", "vbs_project_series_f64", "vbs_harmonic_fit_f64", "vbs_window_moments_f64", "vbs_window_fit_f64",
@@ -173,6 +175,8 @@ def lib():
         "vbs_chess_corners": (i32, [i32, vp, i32, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "vbs_corner_subpix": (i32, [i32, vp, i32, i32, i32, i64, i64, vp, i32, i32, i32, i32, i32, i32, f64, vp, vp]),
         "vbs_calibrate_camera": (i32, [i32, vp, i32, vp, i32, vp, i32, i32, i32, i32] + [vp] * 12),
+        "vbs_retrack_workspace": (i64, [i32, i32, i32]),
+        "vbs_retrack": (i32, [i32, vp, vp, i32, i32, vp, i32, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

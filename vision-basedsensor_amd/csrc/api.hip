@@ -601,6 +601,25 @@ extern "C" int vbs_pnp_ransac(int device, const double* world, int n_points, con
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
 
+extern "C" int64_t vbs_retrack_workspace(int n, int m_ref, int max_det) {
+    if (n < 0 || m_ref < 1 || max_det < 1) return VBS_EINVAL;
+    if (m_ref > VBS_RETRACK_MAX || max_det > VBS_RETRACK_MAX) return VBS_ECAPACITY;
+    return (int64_t)retrack_workspace_bytes(n, m_ref, max_det);
+}
+
+extern "C" int vbs_retrack(int device, const double* det, const int32_t* counts, int n, int max_det, const double* ref_xy, int m_ref,
+                           const double* state_in, double gate, double max_travel, double vel_gain, int max_coast, int32_t* assign,
+                           float* table, double* dist2, int32_t* info, double* state_out, void* workspace, void* stream) {
+    if (!det || !counts || !ref_xy || !workspace || ((uintptr_t)workspace & 7) || (!assign && !table && !state_out) || n < 0 ||
+        m_ref < 1 || max_det < 1 || !(gate >= 0.0) || !(vel_gain >= 0.0 && vel_gain <= 1.0) || max_coast < 0)
+        return VBS_EINVAL;
+    if (m_ref > VBS_RETRACK_MAX || max_det > VBS_RETRACK_MAX) return VBS_ECAPACITY;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_retrack(det, counts, n, max_det, ref_xy, m_ref, state_in, gate, max_travel, vel_gain, max_coast, assign, table, dist2, info,
+                   state_out, workspace, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
+}
+
 extern "C" int vbs_calibrate_camera(int device, const double* obj, int n_points, const double* img, int n_views,
                                     const uint8_t* view_mask, int n_problems, int w, int h, int max_iter, double* homography,
                                     int32_t* view_void, int32_t* status, double* K4, double* dist, double* R, double* T, double* rms,

@@ -297,6 +297,11 @@ void launch_dwell_stats(const double* rec, int n, int s, int cols, int n_values,
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,
                 int32_t* inlier_count, u8* inlier_mask, double* errors, int32_t* winner, hipStream_t s);
+// k_retrack.hip (f20): the grid of every frame, the walk along time, the table rows; `assign` null: the workspace holds it
+size_t retrack_workspace_bytes(int n, int m, int max_det);
+void launch_retrack(const double* det, const int32_t* counts, int n, int max_det, const double* ref_xy, int m, const double* state_in,
+                    double gate, double max_travel, double vel_gain, int max_coast, int32_t* assign, float* table, double* dist2,
+                    int32_t* info, double* state_out, void* workspace, hipStream_t st);
 // k_calib.hip (f9): homographies of nv views, then nb calibration problems over subsets of them
 void launch_calib(const double* obj, int n, const double* img, int nv, const u8* view_mask, int nb, int w, int h, int max_iter,
                   double* H, int32_t* view_void, int32_t* status, double* K4, double* dist, double* R, double* T, double* rms,

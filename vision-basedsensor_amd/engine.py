@@ -845,3 +845,77 @@ def _pose_args(n, m, start_frame, mode, scale, slots, reject_k, frame_range):
         if idx.size and (idx.min() < 0 or idx.max() >= m):
             raise ValueError(f"slots outside the table's {m} slots")
     return a, b, 1 if mode == "shell" else 0
+
+
+# ---- re-tracking a recording along time (k_retrack.hip) ---------------------------------------------------------------------------
+def _retrack_args(n, m, max_det, gate, max_travel, vel_gain, max_coast, want):
+    """`retrack`'s argument checks (no device needed): -> (gate, max_travel, vel_gain, max_coast, want) or ValueError."""
+    from .retrack import OUTPUTS
+    if n < 0 or m < 1 or max_det < 1:
+        raise ValueError("det must be [n >= 0, max_det >= 1, 6] and ref_xy [m >= 1, 2]")
+    if m > L.RETRACK_MAX or max_det > L.RETRACK_MAX:
+        raise ValueError(f"at most {L.RETRACK_MAX} slots and {L.RETRACK_MAX} detections per frame (VBS_RETRACK_MAX)")
+    g = float(gate)
+    if not g >= 0.0:
+        raise ValueError(f"gate {gate} must be >= 0")
+    mt = float(max_travel)
+    if np.isnan(mt):
+        raise ValueError("max_travel must not be NaN (inf = no limit)")
+    vg = float(vel_gain)
+    if not 0.0 <= vg <= 1.0:
+        raise ValueError(f"vel_gain {vel_gain} must lie in [0, 1]")
+    mc = int(max_coast)
+    if mc != max_coast or mc < 0:
+        raise ValueError(f"max_coast {max_coast} must be an integer >= 0")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in OUTPUTS]
+    if unknown:
+        raise ValueError(f"want: unknown outputs {unknown} (known: {', '.join(OUTPUTS)})")
+    return g, mt, vg, mc, want
+
+
+def retrack(det, counts, ref_xy, gate=10.0, max_travel=float("inf"), vel_gain=0.5, max_coast=5, state=None,
+            want=("assign", "table", "dist2", "info"), device=None):
+    """Re-track a recording from its detections along time (`vbs_retrack`; the rule: include/vbs.h): per slot a position and a
+    velocity, a gate of `gate` px around the prediction, every detection given to at most one slot.  det float64 [n, max_det, 6]
+    and counts int32 [n] as `Engine.track_to_3d(..., want_det=True)` returns them, ref_xy [m, 2] (arrays or tensors); `state`
+    [m, 6] as an earlier call returned it, None = `retrack.initial_state(ref_xy)`.  Returns a dict of device tensors: those of
+    `want` - assign int32 [n, m] (detection index or -1), table float32 [n, m, 10] (rows as `Engine.track` writes them, ready
+    for `Engine.solve3d`), dist2 float64 [n, m], info int32 [n, 4] = used, matched, with_candidate, contested - and always
+    `state` float64 [m, 6]: frames [0, k) and then [k, n) with that state give what [0, n) gives."""
+    if device is None and isinstance(det, torch.Tensor) and det.is_cuda:
+        device = det.device.index
+    dev = _device(device)
+    d = torch.as_tensor(det, dtype=torch.float64, device=dev).contiguous()
+    if d.dim() != 3 or d.shape[2] != L.DET_COLS:
+        raise ValueError(f"det must be [n, max_det, {L.DET_COLS}]")
+    c = torch.as_tensor(counts, device=dev).to(torch.int32).contiguous().reshape(-1)
+    if c.numel() != d.shape[0]:
+        raise ValueError(f"counts must be [n = {d.shape[0]}]")
+    ref = _dev_f64(ref_xy, dev, 2)
+    n, max_det, m = d.shape[0], d.shape[1], ref.shape[0]
+    g, mt, vg, mc, want = _retrack_args(n, m, max_det, gate, max_travel, vel_gain, max_coast, want)
+    st = None
+    if state is not None:
+        st = torch.as_tensor(state, dtype=torch.float64, device=dev).contiguous()
+        if tuple(st.shape) != (m, L.RETRACK_STATE_COLS):
+            raise ValueError(f"state must be [m = {m}, {L.RETRACK_STATE_COLS}]")
+    kinds = {"assign": ((n, m), torch.int32), "table": ((n, m, L.TABLE_COLS), torch.float32), "dist2": ((n, m), torch.float64),
+             "info": ((n, L.RETRACK_INFO_COLS), torch.int32)}
+    out = {k: torch.empty(kinds[k][0], dtype=kinds[k][1], device=dev) for k in want}
+    if n == 0:                                           # no frame: the state as it came (an empty tensor has no address to pass)
+        from .retrack import initial_state
+        out["state"] = st.clone() if st is not None else initial_state(ref)
+        return out
+    out["state"] = torch.empty((m, L.RETRACK_STATE_COLS), dtype=torch.float64, device=dev)
+    lib = L.lib()
+    ws = torch.empty((int(lib.vbs_retrack_workspace(n, m, max_det)) + 7) // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.vbs_retrack(dev.index, _ptr(d), _ptr(c), n, max_det, _ptr(ref), m, _ptr(st), g, mt, vg, mc, _ptr(out.get("assign")),
+                             _ptr(out.get("table")), _ptr(out.get("dist2")), _ptr(out.get("info")), _ptr(out["state"]), _ptr(ws),
+                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc == L.VBS_EINVAL:
+        raise ValueError("vbs_retrack: bad argument (gate >= 0, vel_gain in [0, 1], max_coast >= 0)")
+    if rc != L.VBS_OK:
+        raise L.VbsError(f"vbs_retrack failed ({rc})")
+    return out

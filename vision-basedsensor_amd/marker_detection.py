@@ -31,6 +31,7 @@ import os
 import numpy as np
 
 from . import ids as _ids
+from . import retrack as _retrack
 
 CSV_COLUMNS = ["frameno", "row", "col", "Ox", "Oy", "Cx", "Cy", "major_axis", "minor_axis", "angle"]
 
@@ -499,6 +500,19 @@ class MarkerTracker:
         ids, ref_xy = getattr(self, "_ref_arrays", None) or _ids.reference_arrays(self.first_frame_markers)
         table, det, counts = eng.track_to_3d(ft, ref_xy, self.config.get("min_marker_distance", 20),
                                              want_det=True)
+        rt = _retrack.params(self.config.get("retrack"))
+        if rt is not None:
+            # the table of the per-frame rule is replaced by the one tracked along time; the state goes from batch to batch on
+            # the object, so the batch size changes nothing (a frame with a device status raises below, as it always did)
+            from . import engine as _eng_mod
+            if self.frame_count == 0:
+                self._retrack_state, self.retrack_report = None, None
+            out = _eng_mod.retrack(det, counts, ref_xy, state=getattr(self, "_retrack_state", None), want=("table", "info"),
+                                   device=eng.device.index, **rt)
+            table, self._retrack_state = out["table"], out["state"]
+            info = out["info"].cpu().numpy()
+            prev = getattr(self, "retrack_report", None)
+            self.retrack_report = {"info": info if prev is None else np.concatenate([prev["info"], info]), "params": rt}
         table_d, det_d = table, det
         counts = counts.cpu().numpy()
         if (counts < 0).any():                  # the reference would have emitted rows: never drop a frame silently

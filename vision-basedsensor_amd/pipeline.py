@@ -1260,6 +1260,55 @@ def to_step_frame(result: IndentationResult, path=None):
     return df
 
 
+# ---- re-tracking a recording along time (k_retrack.hip) ---------------------------------------------------------------------------
+def retrack_table(eng: Engine, det, counts, ref_xy, cam=None, min_dist=20.0, min_marker_size_px=5.0, **params):
+    """The table of a recording re-tracked ALONG TIME (`engine.retrack`) from the detections
+    `eng.track_to_3d(..., want_det=True)` returned: every slot predicts where its marker is, takes only a detection inside
+    `gate` px of the prediction, and a detection goes to at most one slot - so a marker that drops out hands its ID to nobody,
+    and one dragged far from its first-frame position is followed.  `params`: gate, max_travel, vel_gain, max_coast, state.
+    Returns (table, report).  table float32 [n, m, 10] is `eng.track`'s format (with `cam`, `eng.solve3d` has run on it), so
+    `despike_table`, `fill_table` and every `*_analysis` take it as it is.  report: `info` int32 [n, 4] (used, matched,
+    with_candidate, contested) and `dist2` float64 [n, m] as `engine.retrack` returns them, `state` to continue from,
+    `comparison` = `retrack.compare_tables(table, eng.track(det, counts, ref_xy, min_dist))` - what changed against the
+    per-frame rule (a = this table, b = the per-frame one) - and `lost`, the slots never matched."""
+    from . import engine as _engine
+    from .retrack import compare_tables
+    out = _engine.retrack(det, counts, ref_xy, want=("table", "dist2", "info"), device=eng.device.index, **params)
+    table = out["table"]
+    d = torch.as_tensor(det, dtype=torch.float64, device=eng.device).contiguous()
+    c = torch.as_tensor(counts, device=eng.device).to(torch.int32).contiguous().reshape(-1)
+    legacy = eng.track(d, c, ref_xy, min_dist)
+    comparison = compare_tables(table, legacy)
+    if cam is not None:
+        eng.solve3d(table, cam, min_marker_size_px)
+    lost = torch.nonzero(~(out["dist2"] >= 0).any(dim=0)).reshape(-1) if table.shape[0] else torch.arange(table.shape[1], device=eng.device)
+    return table, {"info": out["info"], "dist2": out["dist2"], "state": out["state"], "comparison": comparison, "lost": lost}
+
+
+def to_retrack_frame(report, frame_offset=0, path=None):
+    """The sheet of `retrack_table`: one row per frame - `frameno, used, matched, with_candidate, contested` from the report's
+    `info`, then `same, only_retrack, only_per_frame, differ` from its comparison with the per-frame rule.  `path`: also written,
+    as .csv or as .xlsx."""
+    import pandas as pd
+    info = report["info"].detach().cpu().numpy() if isinstance(report["info"], torch.Tensor) else np.asarray(report["info"])
+    cmp_ = report["comparison"]
+    if info.ndim != 2 or info.shape[1] != L.RETRACK_INFO_COLS or len(cmp_["same"]) != info.shape[0]:
+        raise ValueError(f"report must hold info [n, {L.RETRACK_INFO_COLS}] and the comparison of the same n frames")
+    data = {"frameno": np.arange(info.shape[0], dtype=np.int64) + int(frame_offset)}
+    for k, name in enumerate(("used", "matched", "with_candidate", "contested")):
+        data[name] = info[:, k].astype(np.int64)
+    for key, name in (("same", "same"), ("only_a", "only_retrack"), ("only_b", "only_per_frame"), ("differ", "differ")):
+        data[name] = np.asarray(cmp_[key], dtype=np.int64)
+    df = pd.DataFrame(data)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 def to_marker_frame(table, ids, frame_offset=0, path=None):
     """The sheet the reference's L4 scripts read (`LocalAnalysis.py:47,58`, `MarkerDisplacement.py:72,80`): one row
     `frameno, marker_id, Xw, Yw, Zw` per table entry with a 3-D point, frame-major; `marker_id` = `ids.marker_ids`.
