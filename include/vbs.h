@@ -1238,6 +1238,69 @@ int vbs_retrack(int device, const double* det, const int32_t* counts, int n, int
                 const double* state_in, double gate, double max_travel, double vel_gain, int max_coast, int32_t* assign,
                 float* table, double* dist2, int32_t* info, double* state_out, void* workspace, void* stream);
 
+/* Uncertainty of the 3-D solve (ours: the reference states its precision as two figures).  Handle-free; float64 without
+ * contraction, + - * / sqrt only, every sum in a stated order: an output depends on its inputs only, never on the launch shape
+ * or on the range it was asked in, and tests/helpers/uncert_oracle.py restates every expression bit for bit.
+ * THE MODEL is what vbs_solve3d computes for a row: cv2.undistortPoints' five fixed-point iterations (skipped when every
+ * distortion coefficient is 0) followed by the closed-form solve, as a function of the observation o = (Cx, Cy, major) - table
+ * columns 1 .. 3 read as (double)float32 - and of the camera vector of VBS_UNCERT_CAM = 16 entries
+ *     fx, fy, cx, cy, k1, k2, p1, p2, k3, w0, w1, w2, T0, T1, T2, dmm
+ * where w is a small rotation on the camera side, R_wc' = exp([w]x) R_wc at w = 0: dX/dw_i = R_wc' (pc x e_i), pc = P_cam - T.
+ * It is differentiated by forward mode through the iterations AS EXECUTED (not the implicit-function derivative of the
+ * converged inverse); f_avg, dmm / f_avg and f_avg^2, float32 in the solve, are differentiated as the smooth float64 expressions
+ * while the primal values the tangents multiply are the solve's own.  First order only.
+ * A table row is USABLE where it carries VBS_FLAG_XYZ, major >= min_marker_size_px and the recomputed solve succeeds.
+ *
+ * vbs_uncert_points - uvd [dev] float64 [n,3] = (Cx, Cy, major) -> xyz [dev] float64 [n,3] and ok [dev] int32 [n], bit for bit
+ *   what vbs_calculate_3d gives for vbs_undistort_points of the same points; j_obs [dev] float64 [n,3,3] = dX_r / do_k and j_cam
+ *   [dev] float64 [n,3,VBS_UNCERT_CAM] = dX_r / dtheta_k, zeros where ok is 0.
+ * vbs_uncert_cov - table [dev] float32 [n,m_ref,VBS_TABLE_COLS].  obs_cov [HOST] float64 [obs_rows,6], obs_rows 1 or m_ref (one
+ *   per slot): the symmetric covariance of (Cx, Cy, major) as uu, uv, ud, vv, vd, dd.  cam_factor [HOST] float64 [16,q], 0 <= q
+ *   <= 16 (may be NULL at q = 0): Sigma_theta = L L'.  Column c of L is pushed through the model as ONE direction, g_c = J_cam
+ *   L[:,c], so a covariance is a sum of squares - positive semidefinite by construction - and J_cam is never formed for a table.
+ *   cov [dev] float64 [fe-fb,m_ref,VBS_UNCERT_COV_COLS] = flag (1 = usable), xx, xy, xz, yy, yz, zz of
+ *     Sigma_X = J_obs Sigma_o J_obs' + sum_c g_c g_c'           (M = J_obs Sigma_o, then M J_obs', every entry three products added
+ *   from the left; then c ascending), zeros where the row is not usable.  May be NULL.
+ *   dcov [dev] float64 [fe-fb,m_ref,VBS_UNCERT_DCOV_COLS], may be NULL; needs 0 <= ref_frame < n (with dcov NULL ref_frame must
+ *   be -1).  For a row usable in its frame AND in ref_frame: flag 1, the six entries of
+ *     Sigma_D = (J_obs,f Sigma_o J_obs,f' + J_obs,0 Sigma_o J_obs,0') + sum_c (g_c,f - g_c,0)(g_c,f - g_c,0)'
+ *   and t2 = D' Sigma_D^-1 D with D = table columns 6 .. 8 of the row minus the reference row's, as vbs_axis_displacement forms
+ *   it.  The inverse is an LDL' without square roots: d1 = xx, l21 = xy / d1, l31 = xz / d1, d2 = yy - l21 xy, w = yz - l21 xz,
+ *   l32 = w / d2, d3 = (zz - l31 xz) - l32 w; z1 = D0, z2 = D1 - l21 z1, z3 = (D2 - l31 z1) - l32 z2; t2 = (z1 z1 / d1 + z2 z2 /
+ *   d2) + z3 z3 / d3.  t2 is valid - flag 3 - only where d1, d2 and d3 each exceed piv_rel * ((xx + yy) + zz); else t2 = 0.  The
+ *   pixel noise of the two frames is taken as uncorrelated.  The reference row's parts are computed once per slot.
+ * vbs_uncert_total - the variance of vbs_axis_displacement's `total`.  A slot counts where slot_mask ([dev] uint8 [m_ref] or
+ *   NULL) selects it, the row of ref_frame is usable (want) and the frame's row is.  total [dev] float64
+ *   [fe-fb,VBS_UNCERT_TOTAL_COLS] = count, complete (want >= 1 and count == want), var_x, var_y, var_z, cam_x, cam_y, cam_z:
+ *     cam_k = sum_c (sum_r (g_c,f,r - g_c,0,r)_k)^2   the camera's share: coherent over the markers, it grows as count^2
+ *     var_k = sum_r (J_obs Sigma_o J_obs')_kk,f,r + (..)_kk,0,r  [each slot's pair added first]  + cam_k
+ *   Every sum over r: lane l of a wave adds slots l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1 (lane i takes i + off),
+ *   as vbs_axis_displacement.  One wave per frame, VBS_UNCERT_GROUP frames a workgroup (no result depends on it).
+ * vbs_pixel_noise - out [dev] float64 [m_ref,VBS_NOISE_COLS] = count, mean Cx, Cy, major, then uu, uv, ud, vv, vd, dd: the sample
+ *   covariance (ddof 1) of (Cx, Cy, major) over the rows of [frame_begin, frame_end) with VBS_FLAG_TRACKED, two passes (sums ->
+ *   means = sum / count; centred products / (count - 1)), frames in order.  count 0: zeros; count 1: the means and zeros.
+ * work [dev] float64 [m_ref * VBS_UNCERT_WORK_COLS]: the reference rows and the staged obs_cov; the calls allocate nothing.
+ * VBS_EINVAL, before a device is selected and with nothing written: a null pointer (but the optional ones), n or m_ref < 1,
+ * obs_rows neither 1 nor m_ref, q outside [0, 16], a non-finite obs_cov or cam_factor, a NaN min_marker_size_px, piv_rel not
+ * finite or < 0, ref_frame outside [0, n) where it is needed, frames outside 0 <= frame_begin <= frame_end <= n. */
+#define VBS_UNCERT_CAM        16    /* entries of the camera vector                                          */
+#define VBS_UNCERT_COV_COLS   7     /* flag, xx, xy, xz, yy, yz, zz                                          */
+#define VBS_UNCERT_DCOV_COLS  8     /* flag, xx, xy, xz, yy, yz, zz, t2                                      */
+#define VBS_UNCERT_TOTAL_COLS 8     /* count, complete, var_x, var_y, var_z, cam_x, cam_y, cam_z             */
+#define VBS_UNCERT_GROUP      4     /* frames a workgroup of the total takes, one wave each                  */
+#define VBS_UNCERT_REF_COLS   55    /* a reference row: usable, its six observation entries, g [16][3]       */
+#define VBS_UNCERT_WORK_COLS  61    /* VBS_UNCERT_REF_COLS + 6                                               */
+#define VBS_NOISE_COLS        10    /* count, three means, six covariance entries                            */
+int vbs_uncert_points(int device, const double* uvd, int n, const vbs_camera* cam, double* xyz, double* j_obs, double* j_cam,
+                      int32_t* ok, void* stream);
+int vbs_uncert_cov(int device, const float* table, int n, int m_ref, const vbs_camera* cam, const double* obs_cov, int obs_rows,
+                   const double* cam_factor, int q, int ref_frame, double min_marker_size_px, double piv_rel, int frame_begin,
+                   int frame_end, double* work, double* cov, double* dcov, void* stream);
+int vbs_uncert_total(int device, const float* table, int n, int m_ref, const vbs_camera* cam, const double* obs_cov, int obs_rows,
+                     const double* cam_factor, int q, int ref_frame, const uint8_t* slot_mask, double min_marker_size_px,
+                     int frame_begin, int frame_end, double* work, double* total, void* stream);
+int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

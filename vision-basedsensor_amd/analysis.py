@@ -776,3 +776,116 @@ def dwell_stats_f64(rec, steps, guard, n_values=None, device=None):
     _call("vbs_dwell_stats_f64", f"steps rows = s or 1, 1 <= max_steps <= {L.STEP_MAX_STEPS}, guard >= 0, 1 <= n_values < cols <= 8",
           dev, _ptr(r), n, s, cols, nv, _ptr(st), st.shape[0], ms, int(guard), _ptr(out))
     return out
+
+
+# ---- uncertainty of the 3-D solve (k_uncert.hip): Jacobians by forward mode, covariances, the pixel noise of a still segment -------
+_TABLE = "table must be float32 [n >= 1, m >= 1, 10]"
+
+
+def _f32_table(table, dev):
+    t = torch.as_tensor(table, dtype=torch.float32, device=dev).contiguous()
+    if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] < 1 or t.shape[2] != L.TABLE_COLS:
+        raise ValueError(_TABLE)
+    return t
+
+
+def solve3d_jacobian(uvd, cam, device=None):
+    """The 3-D solve of points with its Jacobians (`vbs_uncert_points`).  uvd float64 [n, 3] = (Cx, Cy, major) as a table row holds
+    them, BEFORE undistortion; cam an `_lib.Camera`.  Returns `(xyz [n, 3], J_obs [n, 3, 3], J_cam [n, 3, 16], ok int32 [n])`: xyz
+    and ok bit for bit `calculate_3d(undistort_points(..))`, J_obs = dX / d(Cx, Cy, major), J_cam = dX / d(fx, fy, cx, cy, k1, k2,
+    p1, p2, k3, w0, w1, w2, T0, T1, T2, dmm) by forward mode through the five undistortion iterations as executed; zeros where ok
+    is 0."""
+    dev = _device(device)
+    p = _f64(uvd, dev, 2, "uvd must be [n, 3]")
+    if p.shape[1] != 3:
+        raise ValueError("uvd must be [n, 3]")
+    n = p.shape[0]
+    xyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    jo = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
+    jc = torch.empty((n, 3, L.UNCERT_CAM), dtype=torch.float64, device=dev)
+    ok = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return xyz, jo, jc, ok
+    _call("vbs_uncert_points", "uvd [n, 3]", dev, _ptr(p), n, C.byref(cam), _ptr(xyz), _ptr(jo), _ptr(jc), _ptr(ok))
+    return xyz, jo, jc, ok
+
+
+def _uncert_args(n, m, obs_cov, cam_factor, ref_frame, slots, min_marker_size_px, piv_rel, frame_range):
+    """`solve3d_cov`'s argument checks (no device needed): -> (obs [1 or m, 6], L [16, q], ref_frame or -1, a, b) or ValueError."""
+    obs = np.ascontiguousarray(obs_cov, dtype=np.float64)
+    if obs.shape == (3, 3):
+        if not np.array_equal(obs, obs.T):
+            raise ValueError("obs_cov as a 3 x 3 matrix must be symmetric")
+        obs = obs[np.triu_indices(3)]
+    if obs.shape == (6,):
+        obs = obs.reshape(1, 6)
+    if obs.shape not in ((1, 6), (m, 6)):
+        raise ValueError(f"obs_cov must be [6] or [{m}, 6] = uu, uv, ud, vv, vd, dd of (Cx, Cy, major), or one symmetric 3 x 3")
+    if not np.isfinite(obs).all():
+        raise ValueError("obs_cov must be finite")
+    Lf = np.zeros((L.UNCERT_CAM, 0)) if cam_factor is None else np.ascontiguousarray(cam_factor, dtype=np.float64)
+    if Lf.ndim != 2 or Lf.shape[0] != L.UNCERT_CAM or Lf.shape[1] > L.UNCERT_CAM:
+        raise ValueError(f"cam_factor must be [{L.UNCERT_CAM}, q <= {L.UNCERT_CAM}] (`uncertainty.camera_factor`)")
+    if not np.isfinite(Lf).all():
+        raise ValueError("cam_factor must be finite")
+    rf = -1 if ref_frame is None else int(ref_frame)
+    if ref_frame is not None and not (0 <= rf < n):
+        raise ValueError(f"ref_frame {ref_frame} outside the table's {n} frames")
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= m):
+            raise ValueError(f"slots outside the table's {m} slots")
+    if np.isnan(float(min_marker_size_px)):
+        raise ValueError("min_marker_size_px must be a number")
+    if not (np.isfinite(float(piv_rel)) and float(piv_rel) >= 0.0):
+        raise ValueError("piv_rel must be finite and >= 0")
+    a, b = _frame_range(frame_range, n)
+    return np.ascontiguousarray(obs), np.ascontiguousarray(Lf), rf, a, b
+
+
+def solve3d_cov(table, cam, obs_cov, cam_factor=None, ref_frame=None, slots=None, min_marker_size_px=5.0, piv_rel=1e-12,
+                frame_range=None, device=None):
+    """The covariance of every 3-D point of a table, of its displacement from `ref_frame` and of the frame's total displacement
+    (`vbs_uncert_cov`, `vbs_uncert_total`).  table float32 [n, m, 10]; cam an `_lib.Camera`; obs_cov the covariance of
+    (Cx, Cy, major) as [6] = uu, uv, ud, vv, vd, dd, one per slot [m, 6], or a symmetric 3 x 3 (`uncertainty.obs_cov`); cam_factor
+    [16, q] with Sigma_theta = L L' (`uncertainty.camera_factor`; None = an exact camera).  Returns a dict of float64 device tensors
+    for the frames [a, b) of `frame_range`: `cov` [b-a, m, 7] = flag, xx, xy, xz, yy, yz, zz of Sigma_X; with a `ref_frame` also
+    `dcov` [b-a, m, 8] = flag (1 both rows usable, 3 = t2 valid), Sigma_D, t2 = D' Sigma_D^-1 D, and `total` [b-a, 8] = count,
+    complete, var_x, var_y, var_z of `axis_displacement`'s total over `slots`, then the coherent camera share of each variance;
+    without one both are None.  A row is usable where it carries the XYZ flag, major >= min_marker_size_px and the solve succeeds."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    obs, Lf, rf, a, b = _uncert_args(n, m, obs_cov, cam_factor, ref_frame, slots, min_marker_size_px, piv_rel, frame_range)
+    q = Lf.shape[1]
+    cov = torch.empty((b - a, m, L.UNCERT_COV_COLS), dtype=torch.float64, device=dev)
+    dcov = torch.empty((b - a, m, L.UNCERT_DCOV_COLS), dtype=torch.float64, device=dev) if rf >= 0 else None
+    total = torch.empty((b - a, L.UNCERT_TOTAL_COLS), dtype=torch.float64, device=dev) if rf >= 0 else None
+    out = {"cov": cov, "dcov": dcov, "total": total}
+    if a == b:
+        return out
+    work = torch.empty((m * L.UNCERT_WORK_COLS,), dtype=torch.float64, device=dev)
+    hint = "obs_cov finite [1 or m, 6], cam_factor finite [16, q <= 16], ref_frame inside the table, piv_rel >= 0"
+    _call("vbs_uncert_cov", hint, dev, _ptr(t), n, m, C.byref(cam), _host_ptr(obs), obs.shape[0], _host_ptr(Lf), q, rf,
+          float(min_marker_size_px), float(piv_rel), a, b, _ptr(work), _ptr(cov), _ptr(dcov))
+    if rf >= 0:
+        mask = None
+        if slots is not None:
+            mask = torch.zeros((m,), dtype=torch.uint8, device=dev)
+            mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=dev)] = 1
+        _call("vbs_uncert_total", hint, dev, _ptr(t), n, m, C.byref(cam), _host_ptr(obs), obs.shape[0], _host_ptr(Lf), q, rf,
+              _ptr(mask), float(min_marker_size_px), a, b, _ptr(work), _ptr(total))
+    return out
+
+
+def pixel_noise(table, frame_range=None, device=None):
+    """The scatter of the observation over a still segment (`vbs_pixel_noise`): table float32 [n, m, 10] -> float64 [m, 10] = count,
+    mean Cx, Cy, major, then uu, uv, ud, vv, vd, dd, the sample covariance (ddof 1) over the tracked rows of the frames [a, b) of
+    `frame_range` - columns 4 .. 9 are an `obs_cov` per slot for `solve3d_cov`.  count 0: zeros; count 1: the means and zeros."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    a, b = _frame_range(frame_range, n)
+    out = torch.empty((m, L.NOISE_COLS), dtype=torch.float64, device=dev)
+    _call("vbs_pixel_noise", "0 <= frame_begin <= frame_end <= n", dev, _ptr(t), n, m, a, b, _ptr(out))
+    return out

@@ -257,3 +257,72 @@ extern "C" int vbs_dwell_stats_f64(int device, const double* rec, int n, int s, 
     launch_dwell_stats(rec, n, s, cols, n_values, steps, steps_rows, max_steps, guard, out, (hipStream_t)stream);
     return launched();
 }
+
+// ---- uncertainty of the 3-D solve (k_uncert.hip) -------------------------------------------------------------------------------
+extern "C" int vbs_uncert_points(int device, const double* uvd, int n, const vbs_camera* cam, double* xyz, double* j_obs,
+                                 double* j_cam, int32_t* ok, void* stream) {
+    if (!uvd || !cam || !xyz || !j_obs || !j_cam || !ok || n < 0) return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (n) launch_uncert_points(uvd, n, *cam, xyz, j_obs, j_cam, ok, (hipStream_t)stream);
+    return launched();
+}
+
+// what vbs_uncert_cov and vbs_uncert_total share: the table, the two covariances (read on the host), the gate
+static inline bool uncert_ok(const float* table, int n, int m, const vbs_camera* cam, const double* obs_cov, int obs_rows,
+                             const double* cam_factor, int q, double min_size, int frame_begin, int frame_end, const double* work) {
+    if (!table || !cam || !obs_cov || !work || n < 1 || m < 1 || !slots_fit_grid(m) || (obs_rows != 1 && obs_rows != m) || q < 0 ||
+        q > VBS_UNCERT_CAM || (q > 0 && !cam_factor) || std::isnan(min_size) || !range_ok(frame_begin, frame_end, n))
+        return false;
+    for (int64_t i = 0; i < (int64_t)obs_rows * 6; ++i)
+        if (!std::isfinite(obs_cov[i])) return false;
+    for (int i = 0; i < VBS_UNCERT_CAM * q; ++i)
+        if (!std::isfinite(cam_factor[i])) return false;
+    return true;
+}
+// the observation covariance behind the reference rows of `work`; the copy has left the host array when this returns
+static inline double* uncert_stage_obs(const double* obs_cov, int obs_rows, int m, double* work, void* stream) {
+    double* obs = work + (int64_t)m * VBS_UNCERT_REF_COLS;
+    if (hipMemcpyAsync(obs, obs_cov, sizeof(double) * 6 * (size_t)obs_rows, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
+        return nullptr;
+    return obs;
+}
+
+extern "C" int vbs_uncert_cov(int device, const float* table, int n, int m_ref, const vbs_camera* cam, const double* obs_cov,
+                              int obs_rows, const double* cam_factor, int q, int ref_frame, double min_marker_size_px, double piv_rel,
+                              int frame_begin, int frame_end, double* work, double* cov, double* dcov, void* stream) {
+    if (!uncert_ok(table, n, m_ref, cam, obs_cov, obs_rows, cam_factor, q, min_marker_size_px, frame_begin, frame_end, work) ||
+        (!cov && !dcov) || (dcov ? (ref_frame < 0 || ref_frame >= n) : ref_frame != -1) || !std::isfinite(piv_rel) || piv_rel < 0.0)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin) {
+        double* obs = uncert_stage_obs(obs_cov, obs_rows, m_ref, work, stream);
+        if (!obs) { (void)hipGetLastError(); return VBS_EHIP; }
+        launch_uncert_cov(table, m_ref, *cam, obs, obs_rows, cam_factor, q, ref_frame, min_marker_size_px, piv_rel, frame_begin,
+                          frame_end, work, cov, dcov, (hipStream_t)stream);
+    }
+    return launched();
+}
+
+extern "C" int vbs_uncert_total(int device, const float* table, int n, int m_ref, const vbs_camera* cam, const double* obs_cov,
+                                int obs_rows, const double* cam_factor, int q, int ref_frame, const uint8_t* slot_mask,
+                                double min_marker_size_px, int frame_begin, int frame_end, double* work, double* total, void* stream) {
+    if (!uncert_ok(table, n, m_ref, cam, obs_cov, obs_rows, cam_factor, q, min_marker_size_px, frame_begin, frame_end, work) ||
+        !total || ref_frame < 0 || ref_frame >= n)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin) {
+        double* obs = uncert_stage_obs(obs_cov, obs_rows, m_ref, work, stream);
+        if (!obs) { (void)hipGetLastError(); return VBS_EHIP; }
+        launch_uncert_total(table, m_ref, *cam, obs, obs_rows, cam_factor, q, ref_frame, slot_mask, min_marker_size_px, frame_begin,
+                            frame_end, work, total, (hipStream_t)stream);
+    }
+    return launched();
+}
+
+extern "C" int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out,
+                               void* stream) {
+    if (!table || !out || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n)) return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    launch_pixel_noise(table, m_ref, frame_begin, frame_end, out, (hipStream_t)stream);
+    return launched();
+}

@@ -293,6 +293,17 @@ void launch_find_steps(const double* resp, int n, int s, int resp_cols, int w, d
                        hipStream_t st);
 void launch_dwell_stats(const double* rec, int n, int s, int cols, int n_values, const int32_t* steps, int steps_rows,
                         int max_steps, int guard, double* out, hipStream_t st);
+// k_uncert.hip (f21): Jacobians of the 3-D solve by forward mode, the covariances of positions, displacements and their total,
+// the pixel noise of a still segment.  obs [dev] [obs_rows (1 or m), 6]; cam_factor [host] [16, q]; ref [dev] [m, VBS_UNCERT_REF_COLS]
+void launch_uncert_points(const double* uvd, int n, const vbs_camera& cam, double* xyz, double* j_obs, double* j_cam, int32_t* ok,
+                          hipStream_t s);
+void launch_uncert_cov(const float* table, int m, const vbs_camera& cam, const double* obs, int obs_rows, const double* cam_factor,
+                       int q, int ref_frame, double min_size, double piv_rel, int frame_begin, int frame_end, double* ref, double* cov,
+                       double* dcov, hipStream_t s);
+void launch_uncert_total(const float* table, int m, const vbs_camera& cam, const double* obs, int obs_rows, const double* cam_factor,
+                         int q, int ref_frame, const u8* slot_mask, double min_size, int frame_begin, int frame_end, double* ref,
+                         double* total, hipStream_t s);
+void launch_pixel_noise(const float* table, int m, int frame_begin, int frame_end, double* out, hipStream_t s);
 // k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,

@@ -1138,6 +1138,98 @@ def to_kinematic_frame(result, ids=None, fps=None, path=None):
     return df
 
 
+def _uncertainty_args(n, m, ref_frame, k, grid):
+    """`uncertainty_analysis`'s own argument checks (no device needed); the entries' are `engine._uncert_args`."""
+    if ref_frame is None or int(ref_frame) != ref_frame or not (0 <= int(ref_frame) < n):
+        raise ValueError(f"ref_frame {ref_frame} must be a frame of the table's {n}")
+    if not (np.isfinite(float(k)) and float(k) > 0.0):
+        raise ValueError("k must be finite and > 0")
+    if grid is not None and (len(grid) < 2 or tuple(np.shape(grid[0]))[1:] != (m,)):
+        raise ValueError(f"grid must be (weights [P, {m}], wsum [P])")
+    return int(ref_frame), float(k)
+
+
+def uncertainty_analysis(eng, table, cam: L.Camera, obs_cov, cam_factor=None, ref_frame=0, k=3.0, grid=None, slots=None,
+                         min_marker_size_px=5.0):
+    """How good every 3-D point and displacement of a table [N, M, 10] is, to first order: `solve3d_cov` with
+    the observation covariance `obs_cov` (`uncertainty.obs_cov`, or columns 4 .. 9 of `pixel_noise` over a still segment) and the
+    camera's factor `cam_factor` (`uncertainty.camera_factor`), displacements against `ref_frame`.  `eng` may be None (the entries
+    take no handle; with an engine its device is used).  Returns a dict of host arrays: `usable`, `usable_d` [N, M]; `sigma_x`,
+    `sigma_d` [N, M, 3] the standard deviations of X, Y, Z and of dX, dY, dZ (NaN where not usable); `displacement` [N, M, 3];
+    `significant` [N, M, 3] = |D_axis| > k sigma_axis; `t2` [N, M] (NaN where its flag is not set) and `t2_valid`; `limit` [M, 3]
+    the detection limit of a marker, k times the median sigma_D per axis over its usable frames; `count`, `complete` [N],
+    `sigma_total` [N, 3] of `axis_displacement`'s total and `camera_share` [N, 3], the share of its variance that is the
+    camera's - coherent over the markers, it does not average out.  The device tensors are under `cov`, `dcov`, `total`.  With
+    `grid` = (weights [P, M], wsum [P]): `sigma_z_map` [N, P, 2] = `field_map_f64` of (usable, sigma_Z)."""
+    from .engine import field_map_f64, solve3d_cov
+    n, m = int(table.shape[0]), int(table.shape[1])
+    rf, kk = _uncertainty_args(n, m, ref_frame, k, grid)
+    dev = None if eng is None else eng.device.index
+    out = solve3d_cov(table, cam, obs_cov, cam_factor, ref_frame=rf, slots=slots, min_marker_size_px=min_marker_size_px, device=dev)
+    cov, dcov, tot = (out[w].cpu().numpy() for w in ("cov", "dcov", "total"))
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    usable, usable_d = cov[..., 0] == 1.0, dcov[..., 0] >= 1.0
+    with np.errstate(invalid="ignore"):
+        sx = np.where(usable[..., None], np.sqrt(cov[..., [1, 4, 6]]), np.nan)
+        sd = np.where(usable_d[..., None], np.sqrt(dcov[..., [1, 4, 6]]), np.nan)
+        D = np.where(usable_d[..., None], np.where(usable_d[..., None], t[..., 6:9], 0).astype(np.float64) -
+                     np.where(usable_d[..., None], t[rf][None, :, 6:9], 0).astype(np.float64), np.nan)
+        sig = usable_d[..., None] & (np.abs(D) > kk * sd)
+        limit = np.full((m, 3), np.nan)
+        for i in range(m):
+            if usable_d[:, i].any():
+                limit[i] = kk * np.median(sd[usable_d[:, i], i], axis=0)
+        var, camv = tot[:, 2:5], tot[:, 5:8]
+        share = np.where(var > 0.0, camv / np.where(var > 0.0, var, 1.0), 0.0)
+    res = dict(out, usable=usable, usable_d=usable_d, sigma_x=sx, sigma_d=sd, displacement=D, significant=sig,
+               t2=np.where(dcov[..., 0] == 3.0, dcov[..., 7], np.nan), t2_valid=dcov[..., 0] == 3.0, limit=limit, k=kk,
+               ref_frame=rf, count=tot[:, 0], complete=tot[:, 1] == 1.0, sigma_total=np.sqrt(var), camera_share=share)
+    if grid is not None:
+        d = out["cov"].device
+        rec = torch.stack([out["cov"][..., 0], torch.sqrt(out["cov"][..., 6])], dim=2).contiguous()
+        res["sigma_z_map"] = field_map_f64(rec, torch.as_tensor(grid[0], dtype=torch.float64, device=d),
+                                           torch.as_tensor(grid[1], dtype=torch.float64, device=d), 0.5, 1, device=d.index)
+    return res
+
+
+UNCERTAINTY_FRAME_COLUMNS = ("frameno", "slot", "usable", "sigma_X", "sigma_Y", "sigma_Z", "dX", "dY", "dZ", "sigma_dX", "sigma_dY",
+                             "sigma_dZ", "significant_X", "significant_Y", "significant_Z", "t2")
+
+
+def to_uncertainty_frame(result, ids=None, frame_offset=0, path=None):
+    """The long sheet of `uncertainty_analysis`: one row `UNCERTAINTY_FRAME_COLUMNS` per frame and slot (frame-major); `frameno`
+    counts from 1 + `frame_offset`, `slot` = `ids.marker_ids` (slot number + 1 without `ids`); cells are empty (NaN) where the row
+    or its reference row is not usable.  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    sx, sd, D = (np.asarray(result[w], dtype=np.float64) for w in ("sigma_x", "sigma_d", "displacement"))
+    sig, t2 = np.asarray(result["significant"]), np.asarray(result["t2"], dtype=np.float64)
+    if sx.ndim != 3 or sx.shape[2] != 3 or sd.shape != sx.shape or D.shape != sx.shape or sig.shape != sx.shape or t2.shape != sx.shape[:2]:
+        raise ValueError("sigma_x, sigma_d, displacement and significant must be [N, M, 3], t2 [N, M]")
+    N, M = sx.shape[:2]
+    mid = _ids.marker_ids(ids) if ids is not None else np.arange(1, M + 1, dtype=np.int64)
+    if len(mid) != M:
+        raise ValueError(f"the result has {M} slots, ids {len(mid)}")
+    cols = {"frameno": np.repeat(np.arange(1, N + 1, dtype=np.int64) + int(frame_offset), M), "slot": np.tile(np.asarray(mid), N),
+            "usable": np.asarray(result["usable"]).reshape(-1)}
+    for j, a in enumerate("XYZ"):
+        cols["sigma_" + a] = sx[..., j].reshape(-1)
+    for j, a in enumerate("XYZ"):
+        cols["d" + a] = D[..., j].reshape(-1)
+    for j, a in enumerate("XYZ"):
+        cols["sigma_d" + a] = sd[..., j].reshape(-1)
+    for j, a in enumerate("XYZ"):
+        cols["significant_" + a] = sig[..., j].reshape(-1)
+    cols["t2"] = t2.reshape(-1)
+    df = pd.DataFrame(cols, columns=list(UNCERTAINTY_FRAME_COLUMNS))
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 def fill_table(eng: Engine, table: torch.Tensor, half_window=7, degree=2, *, source="xyz", fill_degree=1, slots=None, window="hann",
                min_coverage=0.5, piv_rel=None):
     """The gaps of a table [N, M, 10] filled along time by the constant term of the gap-aware local polynomial fit

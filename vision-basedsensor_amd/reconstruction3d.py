@@ -256,6 +256,16 @@ class MarkerAnalysis:
             logger.info(f"Saved displacement statistics: {path}")
         return (stats, got[1]) if cumulative else stats
 
+    def uncertainty(self, table, obs_cov, cam_factor=None, ref_frame=0, k=3.0, ids=None, path=None, engine=None):
+        """The DataFrame-facing form of `pipeline.uncertainty_analysis` (ours): the standard deviations of every
+        3-D point and displacement of a table [N, M, 10] under this object's camera, the observation covariance `obs_cov` and the
+        camera's factor `cam_factor` (`uncertainty.obs_cov`, `uncertainty.camera_factor`), what is significant at `k` sigma, and
+        t2.  Returns `pipeline.to_uncertainty_frame`'s sheet (written to `path` when given)."""
+        from .pipeline import to_uncertainty_frame, uncertainty_analysis
+        res = uncertainty_analysis(engine, table, self._cam(), obs_cov, cam_factor, ref_frame=ref_frame, k=k,
+                                   min_marker_size_px=self.config.min_marker_size_px)
+        return to_uncertainty_frame(res, ids=ids, path=path)
+
     # ---- `:405-442` --------------------------------------------------------------------------------
     def run_analysis(self, input_csv: Path) -> None:
         try:
