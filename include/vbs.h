@@ -1301,6 +1301,60 @@ int vbs_uncert_total(int device, const float* table, int n, int m_ref, const vbs
                      int frame_begin, int frame_end, double* work, double* total, void* stream);
 int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out, void* stream);
 
+/* Uncertainty of the pose misalignment (ours): the first-order covariance of the plane vbs_pose_series fits, of its tilt and
+ * azimuth, and the test "is the plane tilted at all".  Handle-free; float64 without contraction, + - * / only in everything but
+ * the optional `pose` columns tilt_deg, azimuth_deg and rms; no atomics; every sum over slots follows the rule of
+ * vbs_axis_displacement (lane l of 64 adds slots l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1).  No result depends
+ * on the launch shape, on the frame range or on VBS_POSECOV_GROUP (the frames a workgroup takes, one wave each);
+ * tests/helpers/posecov_oracle.py restates every expression bit for bit.
+ * vbs_pose_cov - table, start_frame, ref_disp, ref_xyz, slot_mask, shell_mode, scale, reject_k and the frame range exactly as
+ *   vbs_pose_series takes them; cam, obs_cov [HOST] [obs_rows,6], cam_factor [HOST] [16,q], min_marker_size_px and piv_rel exactly
+ *   as vbs_uncert_total and vbs_uncert_cov take them.  ref_rows [dev] float32 [2,m_ref,VBS_TABLE_COLS] or NULL: the rows of the
+ *   reference session at the two frames whose difference ref_disp is, ref_start first and ref_end second; with NULL the reference
+ *   state is taken as exact.  work [dev] float64 [m_ref * VBS_UNCERT_WORK_COLS]; the call allocates nothing.
+ * THE MODEL.  The deviation of a slot is d = (X_f - X_start) - (X_re - X_rs): up to four solves with ONE camera.  Once per slot, with
+ *   p = J_obs Sigma_o J_obs' and g_c = J_cam L[:,c] of a row as vbs_uncert_cov forms them (Sigma_o is the slot's for every row):
+ *     fixed_usable = the row of start_frame is USABLE (the rule above) and, with ref_rows, both of its rows are
+ *     S_fix = p_start, with ref_rows (p_start + p_re) + p_rs                      six entries
+ *     g_fix,c = g_c,start, with ref_rows (g_c,start + g_c,re) - g_c,rs            (a shift of T cancels to exactly zero)
+ *   For frame f the covariance of a slot's end point from pixel noise is C = ss (p_f + S_fix) entry by entry, ss = scale scale, and
+ *   its direction for column c is u = scale (g_c,f - g_fix,c); the pixel noise of different rows is taken as uncorrelated.
+ * THE PLANE is recomputed exactly as vbs_pose_series states it: the common rule, means, centred sums, det, a, b, c, SSR, the one
+ *   round of rejection decided by the first plane.  pose [dev] float64 [fe-fb,VBS_POSE_COLS] (may be NULL) is that entry's `pose`:
+ *   flag, a, b, c and n_used bit for bit.  The USED set is the kept set where the pose flag is 2, the common set otherwise; the
+ *   selection is taken as given (not differentiated).  mx, my, mz, xx, xy, yy, det and n_used below are those of the used set.
+ * THE LINEARISATION.  A used slot has the centred coordinates x = Px - mx, y = Py - my, z = Pz - mz and r = z - (a x + b y).  Its
+ *   influence matrix K [3,3] has, for k = 0, 1, 2 and (dx, dy, dz) the unit vector e_k (as the constants 1.0 and 0.0), the column
+ *     e = (dz - a dx) - b dy;   h1 = x e + r dx;   h2 = y e + r dy
+ *     K[0][k] = (h1 yy - h2 xy) / det;   K[1][k] = (h2 xx - h1 xy) / det;   K[2][k] = (e / n_used - K[0][k] mx) - K[1][k] my
+ * THE SUMS, over the used slots that are fixed_usable and usable in f (n_unusable counts the used slots that are not):
+ *     Sigma_obs = sum_r K C K'     aa, ab, ac, bb, bc, cc: M = K C, then M K', every entry three products added from the left (the
+ *                                  product of vbs_uncert_cov with K for J_obs and C for Sigma_o); six sums
+ *     v_c = sum_r K u              row i = (K[i][0] u0 + K[i][1] u1) + K[i][2] u2; three sums per column
+ *     Sigma_cam = sum_c v_c v_c'   c ascending, each entry acc + v_i v_j;   Sigma = Sigma_obs + Sigma_cam entry by entry
+ *   With rho2 = a a + b b, w = 1.0 + rho2, k2 = 57.29577951308232 * 57.29577951308232, ab2 = (2.0 a) b:
+ *     var_tilt    = (k2 ((a a Saa + ab2 Sab) + b b Sbb)) / (rho2 (w w))             in degrees squared; both 0 unless rho2 > 0
+ *     var_azimuth = (k2 ((b b Saa - ab2 Sab) + a a Sbb)) / (rho2 rho2)
+ *   t2 = (a, b) Sigma_ab^-1 (a, b)' through an LDL' without square roots: d1 = Saa, l = Sab / d1, d2 = Sbb - l Sab, z1 = a,
+ *   z2 = b - l a, t2 = z1 z1 / d1 + z2 z2 / d2; valid only where d1 and d2 each exceed piv_rel (Saa + Sbb), else 0.  A tilt is
+ *   >= 0 and not Gaussian near 0: t2 (two degrees of freedom), not tilt / sigma_tilt, is the decision.
+ *   pcov [dev] float64 [fe-fb,VBS_POSECOV_COLS] (may be NULL, not both) = flag, n_unusable, the six entries of Sigma, the six of
+ *   Sigma_cam, var_tilt, var_azimuth, t2.  flag is a bit set: 1 = a plane exists and n_unusable = 0 - only then is any column
+ *   but n_unusable nonzero; 2 = t2 is valid; 4 = rho2 > 0, the angle variances are valid.  A nonzero flag keeps pcov readable as
+ *   a FIR record.  Nothing of a slot that is not common is read into a value, and of a row nothing but what its flag allows:
+ *   such cells may hold NaN.
+ * VBS_EINVAL, before a device is selected and with nothing written: what vbs_pose_series and vbs_uncert_total refuse (a null
+ *   table, ref_disp, ref_xyz, cam, obs_cov or work, n or m_ref < 1, start_frame outside [0, n), a shell_mode other than 0 / 1, a
+ *   scale or reject_k that is not finite, reject_k < 0, obs_rows neither 1 nor m_ref, q outside [0, 16], a non-finite obs_cov or
+ *   cam_factor, a NaN min_marker_size_px, piv_rel not finite or < 0, frames outside 0 <= frame_begin <= frame_end <= n), and pose
+ *   and pcov both NULL.  frame_begin == frame_end emits nothing. */
+#define VBS_POSECOV_COLS  17    /* flag, n_unusable, Sigma [6], Sigma_cam [6], var_tilt, var_azimuth, t2 */
+#define VBS_POSECOV_GROUP 4     /* frames a workgroup takes, one wave each (no result depends on it)     */
+int vbs_pose_cov(int device, const float* table, int n, int m_ref, int start_frame, const double* ref_disp, const double* ref_xyz,
+                 const uint8_t* slot_mask, int shell_mode, double scale, double reject_k, const vbs_camera* cam,
+                 const double* obs_cov, int obs_rows, const double* cam_factor, int q, double min_marker_size_px, double piv_rel,
+                 const float* ref_rows, int frame_begin, int frame_end, double* work, double* pose, double* pcov, void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

@@ -31,6 +31,7 @@ IDS_MAX_MARKERS, IDS_MAX_LAYERS = 1024, 16
 RETRACK_MAX, RETRACK_STATE_COLS, RETRACK_INFO_COLS = 1024, 6, 4
 UNCERT_CAM, UNCERT_COV_COLS, UNCERT_DCOV_COLS, UNCERT_TOTAL_COLS, UNCERT_GROUP = 16, 7, 8, 8, 4
 UNCERT_REF_COLS, UNCERT_WORK_COLS, NOISE_COLS = 55, 61, 10
+POSECOV_COLS, POSECOV_GROUP = 17, 4
 OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_IMPL, OPT_PASS_STREAMS, OPT_LATENCY_FRAMES = 1, 2, 4, 5, 6, 7, 8
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
@@ -46,7 +47,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers", "vbs_pnp_ransac",
            "vbs_chess_workspace", "vbs_chess_corners", "vbs_corner_subpix", "vbs_calibrate_camera",
            "vbs_retrack_workspace", "vbs_retrack",
-           "vbs_uncert_points", "vbs_uncert_cov", "vbs_uncert_total", "vbs_pixel_noise",
+           "vbs_uncert_points", "vbs_uncert_cov", "vbs_uncert_total", "vbs_pixel_noise", "vbs_pose_cov",
            "vbs_axis_displacement", "vbs_fir_series_f64",
            "vbs_step_response_f64", "vbs_find_steps_f64", "vbs_dwell_stats_f64", "vbs_pose_series",
            "vbs_field_map_f64", "vbs_patch_stats_f64", "vbs_project_series_f64", "vbs_harmonic_fit_f64", "vbs_window_moments_f64", "vbs_window_fit_f64",
@@ -184,6 +185,8 @@ def lib():
         "vbs_uncert_cov": (i32, [i32, vp, i32, i32, cam_p, vp, i32, vp, i32, i32, f64, f64, i32, i32, vp, vp, vp, vp]),
         "vbs_uncert_total": (i32, [i32, vp, i32, i32, cam_p, vp, i32, vp, i32, i32, vp, f64, i32, i32, vp, vp, vp]),
         "vbs_pixel_noise": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
+        "vbs_pose_cov": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, i32, f64, f64, cam_p, vp, i32, vp, i32, f64, f64, vp, i32, i32, vp, vp, vp,
+                               vp]),
     }
     for name in SYMBOLS:
         fn = getattr(L, name)            # AttributeError here = stale library

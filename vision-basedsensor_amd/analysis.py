@@ -878,6 +878,68 @@ def solve3d_cov(table, cam, obs_cov, cam_factor=None, ref_frame=None, slots=None
     return out
 
 
+# ---- uncertainty of the pose misalignment (k_posecov.hip): the covariance of the plane, of its angles, and t2 -------------------------
+def _posecov_args(n, m, obs_cov, cam_factor, start_frame, mode, scale, slots, reject_k, min_marker_size_px, piv_rel, frame_range,
+                  ref_disp_shape, ref_xyz_shape, ref_rows_shape=None, want=("pose", "pcov")):
+    """`pose_cov`'s argument checks (no device needed): what `vbs_pose_series` and `vbs_uncert_total` refuse, in the wrappers' words
+    -> (obs [1 or m, 6], L [16, q], a, b, shell_mode, want) or ValueError."""
+    if n < 1 or m < 1:
+        raise ValueError(_TABLE)
+    if mode not in ("plane", "shell"):
+        raise ValueError("mode must be 'plane' or 'shell'")
+    if int(start_frame) != start_frame or not (0 <= int(start_frame) < n):
+        raise ValueError(f"start_frame {start_frame} outside the table's {n} frames")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"scale {scale} is not finite")
+    if not (np.isfinite(float(reject_k)) and float(reject_k) >= 0.0):
+        raise ValueError(f"reject_k {reject_k} must be finite and >= 0 (0 = no rejection)")
+    if tuple(ref_disp_shape) != (m, L.AXIS_COLS) or tuple(ref_xyz_shape) != (m, 3):
+        raise ValueError(f"ref_disp must be [{m}, {L.AXIS_COLS}] and ref_xyz [{m}, 3]: one row per table slot")
+    if ref_rows_shape is not None and tuple(ref_rows_shape) != (2, m, L.TABLE_COLS):
+        raise ValueError(f"ref_rows must be [2, {m}, {L.TABLE_COLS}]: the reference session's rows at ref_start and at ref_end")
+    want = tuple(want)
+    if not want or any(w not in ("pose", "pcov") for w in want):
+        raise ValueError("want must name at least one of 'pose' and 'pcov'")
+    obs, Lf, _, a, b = _uncert_args(n, m, obs_cov, cam_factor, None, slots, min_marker_size_px, piv_rel, frame_range)
+    return obs, Lf, a, b, 1 if mode == "shell" else 0, want
+
+
+def pose_cov(table, ref_disp, ref_xyz, cam, obs_cov, cam_factor=None, ref_rows=None, start_frame=0, mode="plane", scale=1.0,
+             slots=None, reject_k=0.0, min_marker_size_px=5.0, piv_rel=1e-12, frame_range=None, want=("pose", "pcov"), device=None):
+    """The first-order covariance of the plane `Engine.pose_series` fits, of its tilt and azimuth, and the test "is the plane tilted
+    at all" (`vbs_pose_cov`).  table, ref_disp, ref_xyz, start_frame, mode, scale, slots, reject_k and frame_range as
+    `Engine.pose_series` takes them; cam, obs_cov, cam_factor, min_marker_size_px and piv_rel as `solve3d_cov` does.  ref_rows
+    float32 [2, m, 10]: the reference session's rows at the two frames whose difference `ref_disp` is (ref_start first); None takes
+    the reference state as exact.  Returns float64 device tensors `(pose, pcov)` for the frames [a, b) (None for one `want` leaves
+    out): pose [b-a, 8] as `Engine.pose_series`; pcov [b-a, 17] = flag (bit 1: a plane exists and every used slot is usable - only
+    then is any other column but n_unusable nonzero; bit 2: t2 valid; bit 4: the angle variances are valid), n_unusable, then aa,
+    ab, ac, bb, bc, cc of Sigma, the same six of the camera's share Sigma_cam, var_tilt and var_azimuth in degrees squared, and
+    t2 = (a, b) Sigma_ab^-1 (a, b)'."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    rd = torch.as_tensor(ref_disp, dtype=torch.float64, device=dev).contiguous()
+    rx = torch.as_tensor(ref_xyz, dtype=torch.float64, device=dev).contiguous()
+    rr = None if ref_rows is None else torch.as_tensor(ref_rows, dtype=torch.float32, device=dev).contiguous()
+    obs, Lf, a, b, shell, want = _posecov_args(n, m, obs_cov, cam_factor, start_frame, mode, scale, slots, reject_k, min_marker_size_px,
+                                               piv_rel, frame_range, rd.shape, rx.shape, None if rr is None else rr.shape, want)
+    pose = torch.empty((b - a, L.POSE_COLS), dtype=torch.float64, device=dev) if "pose" in want else None
+    pcov = torch.empty((b - a, L.POSECOV_COLS), dtype=torch.float64, device=dev) if "pcov" in want else None
+    if a == b:
+        return pose, pcov
+    mask = None
+    if slots is not None:
+        mask = torch.zeros((m,), dtype=torch.uint8, device=dev)
+        mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=dev)] = 1
+    work = torch.empty((m * L.UNCERT_WORK_COLS,), dtype=torch.float64, device=dev)
+    hint = ("start_frame inside the table, scale and reject_k finite, reject_k >= 0, obs_cov finite [1 or m, 6], cam_factor finite "
+            "[16, q <= 16], piv_rel >= 0")
+    _call("vbs_pose_cov", hint, dev, _ptr(t), n, m, int(start_frame), _ptr(rd), _ptr(rx), _ptr(mask), shell, float(scale),
+          float(reject_k), C.byref(cam), _host_ptr(obs), obs.shape[0], _host_ptr(Lf), Lf.shape[1], float(min_marker_size_px),
+          float(piv_rel), _ptr(rr), a, b, _ptr(work), _ptr(pose), _ptr(pcov))
+    return pose, pcov
+
+
 def pixel_noise(table, frame_range=None, device=None):
     """The scatter of the observation over a still segment (`vbs_pixel_noise`): table float32 [n, m, 10] -> float64 [m, 10] = count,
     mean Cx, Cy, major, then uu, uv, ud, vv, vd, dd, the sample covariance (ddof 1) over the tracked rows of the frames [a, b) of

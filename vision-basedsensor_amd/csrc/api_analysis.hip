@@ -319,6 +319,27 @@ extern "C" int vbs_uncert_total(int device, const float* table, int n, int m_ref
     return launched();
 }
 
+// ---- uncertainty of the pose misalignment (k_posecov.hip) ------------------------------------------------------------------------
+extern "C" int vbs_pose_cov(int device, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
+                            const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double reject_k,
+                            const vbs_camera* cam, const double* obs_cov, int obs_rows, const double* cam_factor, int q,
+                            double min_marker_size_px, double piv_rel, const float* ref_rows, int frame_begin, int frame_end,
+                            double* work, double* pose, double* pcov, void* stream) {
+    if (!uncert_ok(table, n, m_ref, cam, obs_cov, obs_rows, cam_factor, q, min_marker_size_px, frame_begin, frame_end, work) ||
+        !ref_disp || !ref_xyz || (!pose && !pcov) || start_frame < 0 || start_frame >= n || (shell_mode != 0 && shell_mode != 1) ||
+        !std::isfinite(scale) || !std::isfinite(reject_k) || reject_k < 0.0 || !std::isfinite(piv_rel) || piv_rel < 0.0)
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin) {
+        double* obs = uncert_stage_obs(obs_cov, obs_rows, m_ref, work, stream);
+        if (!obs) { (void)hipGetLastError(); return VBS_EHIP; }
+        launch_pose_cov(table, m_ref, start_frame, ref_disp, ref_xyz, slot_mask, shell_mode, scale, reject_k, *cam, obs, obs_rows,
+                        cam_factor, q, min_marker_size_px, piv_rel, ref_rows, frame_begin, frame_end, work, pose, pcov,
+                        (hipStream_t)stream);
+    }
+    return launched();
+}
+
 extern "C" int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out,
                                void* stream) {
     if (!table || !out || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n)) return VBS_EINVAL;

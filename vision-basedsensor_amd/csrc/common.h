@@ -304,6 +304,11 @@ void launch_uncert_total(const float* table, int m, const vbs_camera& cam, const
                          int q, int ref_frame, const u8* slot_mask, double min_size, int frame_begin, int frame_end, double* ref,
                          double* total, hipStream_t s);
 void launch_pixel_noise(const float* table, int m, int frame_begin, int frame_end, double* out, hipStream_t s);
+// k_posecov.hip (f22): the covariance of the pose plane, its angles and t2; fix [dev] [m, VBS_UNCERT_REF_COLS], obs as above
+void launch_pose_cov(const float* table, int m, int start_frame, const double* ref_disp, const double* ref_xyz, const u8* slot_mask,
+                     int shell, double scale, double reject_k, const vbs_camera& cam, const double* obs, int obs_rows,
+                     const double* cam_factor, int q, double min_size, double piv_rel, const float* ref_rows, int frame_begin,
+                     int frame_end, double* fix, double* pose, double* pcov, hipStream_t s);
 // k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,

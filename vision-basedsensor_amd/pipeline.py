@@ -380,6 +380,94 @@ def to_pose_frame(field, pose, pose_filtered=None, frame_offset=0, path=None):
     return df
 
 
+# ---- uncertainty of the pose misalignment (k_posecov.hip): is the tilt a misalignment or the noise of the markers? -----------------
+def _misalignment_uncertainty_args(n_ref, ref_start, ref_end, k):
+    """`misalignment_uncertainty`'s own argument checks (no device needed); the entry's are `engine._posecov_args`.  -> (ref_start,
+    ref_end counted from the front, k)."""
+    end = int(ref_end) + n_ref if int(ref_end) < 0 else int(ref_end)
+    if not (0 <= end < n_ref):
+        raise ValueError(f"ref_end {ref_end} outside the reference table's {n_ref} frames")
+    if int(ref_start) != ref_start or not (0 <= int(ref_start) < n_ref):
+        raise ValueError(f"ref_start {ref_start} outside the reference table's {n_ref} frames")
+    if not (np.isfinite(float(k)) and float(k) > 0.0):
+        raise ValueError("k must be finite and > 0")
+    return int(ref_start), end, float(k)
+
+
+def misalignment_uncertainty(eng: Engine, table, table_ref, ref_xyz, cam: L.Camera, obs_cov, cam_factor=None, start=0, ref_start=0,
+                             ref_end=-1, mode="plane", scale=1.0, slots=None, reject_k=0.0, k=3.0, min_marker_size_px=5.0,
+                             exact_reference=False):
+    """How good the plane of `misalignment_analysis` is, to first order: `pose_cov` on the same inputs, with the
+    observation covariance `obs_cov` and the camera's factor `cam_factor` of `uncertainty_analysis`.  `ref_disp` is formed as
+    `misalignment_analysis` forms it; the reference session's rows at `ref_start` and `ref_end` carry their own pixel noise and
+    camera directions into every frame unless `exact_reference`.  Returns a dict of host arrays over the N frames: `pose` [N, 8],
+    `pcov` [N, 17], `flag`; `sigma_abc` [N, 3] the standard deviations of a, b, c (NaN where flag bit 1 is clear: no plane, or a
+    used slot whose rows are not usable - `n_unusable` counts them); `sigma_tilt_deg`, `sigma_azimuth_deg` (NaN where bit 4 is
+    clear: a = b = 0); `camera_share` the camera's share of var_tilt - coherent over the markers, it does not average out; `t2` =
+    (a, b) Sigma_ab^-1 (a, b)' (NaN where bit 2 is clear) and `significant` = t2 > k^2; `tilt_limit_deg` = atan(k
+    sqrt(lambda_max(Sigma_ab))) in degrees, the tilt a frame could not tell from zero in its worst direction.
+    `significant` is a test with TWO degrees of freedom: for an untilted plane t2 is chi-squared with 2, so its false-alarm rate
+    is exp(-k^2 / 2) - 1.1 % at k = 3, not the 0.27 % of a one-dimensional 3 sigma.  A tilt is >= 0 and not Gaussian near 0, which
+    is why t2 and not tilt / sigma_tilt decides."""
+    from .engine import pose_cov
+    table_ref = eng._table32(table_ref)
+    rs, end, kk = _misalignment_uncertainty_args(int(table_ref.shape[0]), ref_start, ref_end, k)
+    ref_disp = eng.axis_displacement(table_ref, rs, slots, frame_range=(end, end + 1))[0][0]
+    ref_rows = None if exact_reference else torch.stack([table_ref[rs], table_ref[end]]).contiguous()
+    pose, pcov = pose_cov(table, ref_disp, ref_xyz, cam, obs_cov, cam_factor, ref_rows, start, mode, scale, slots, reject_k,
+                          min_marker_size_px, device=eng.device.index)
+    po, pc = pose.cpu().numpy(), pcov.cpu().numpy()
+    flag = pc[:, 0].astype(np.int64)
+    ok, t2ok, angok = (flag & 1) != 0, (flag & 2) != 0, (flag & 4) != 0
+    a, b = po[:, 1], po[:, 2]
+    S, Cm = pc[:, 2:8], pc[:, 8:14]
+    with np.errstate(all="ignore"):
+        sig = np.where(ok[:, None], np.sqrt(S[:, [0, 3, 5]]), np.nan)
+        quad = lambda M: a * a * M[:, 0] + 2.0 * a * b * M[:, 1] + b * b * M[:, 3]      # noqa: E731
+        qs, qc = quad(S), quad(Cm)
+        share = np.where(angok & (qs > 0.0), qc / np.where(qs > 0.0, qs, 1.0), np.where(angok, 0.0, np.nan))
+        lam = 0.5 * (S[:, 0] + S[:, 3]) + np.sqrt(0.25 * (S[:, 0] - S[:, 3]) ** 2 + S[:, 1] * S[:, 1])
+        t2 = np.where(t2ok, pc[:, 16], np.nan)
+        res = dict(pose=po, pcov=pc, flag=flag, n_unusable=pc[:, 1].astype(np.int64), sigma_abc=sig,
+                   sigma_tilt_deg=np.where(angok, np.sqrt(pc[:, 14]), np.nan),
+                   sigma_azimuth_deg=np.where(angok, np.sqrt(pc[:, 15]), np.nan), camera_share=share, t2=t2, significant=t2ok & (pc[:, 16] > kk * kk),
+                   tilt_limit_deg=np.where(ok, np.arctan(kk * np.sqrt(lam)) * _DEG, np.nan), k=kk)
+    return res
+
+
+POSE_UNCERTAINTY_COLUMNS = ("frameno", "flag", "n_used", "n_unusable", "a", "b", "c", "sigma_a", "sigma_b", "sigma_c", "tilt_deg",
+                            "sigma_tilt_deg", "azimuth_deg", "sigma_azimuth_deg", "camera_share", "t2", "significant", "tilt_limit_deg")
+
+
+def to_pose_uncertainty_frame(result, frame_offset=0, path=None):
+    """The sheet of `misalignment_uncertainty`: one row `POSE_UNCERTAINTY_COLUMNS` per frame; `flag` is the entry's bit set, a .. c
+    and the angles are empty (NaN) where the frame has no plane, every sigma where its flag bit is clear.  `path`: also written,
+    as .csv or as .xlsx."""
+    import pandas as pd
+    po, pc = np.asarray(result["pose"], dtype=np.float64), np.asarray(result["pcov"], dtype=np.float64)
+    if po.ndim != 2 or po.shape[1] != L.POSE_COLS or pc.shape != (po.shape[0], L.POSECOV_COLS):
+        raise ValueError(f"pose must be [N, {L.POSE_COLS}] and pcov [N, {L.POSECOV_COLS}]")
+    N = po.shape[0]
+    plane = np.where((po[:, 0] != 0)[:, None], po[:, 1:6], np.nan)
+    sig = np.asarray(result["sigma_abc"], dtype=np.float64)
+    cols = {"frameno": np.arange(N, dtype=np.int64) + int(frame_offset), "flag": pc[:, 0].astype(np.int64),
+            "n_used": po[:, 7].astype(np.int64), "n_unusable": pc[:, 1].astype(np.int64),
+            "a": plane[:, 0], "b": plane[:, 1], "c": plane[:, 2], "sigma_a": sig[:, 0], "sigma_b": sig[:, 1], "sigma_c": sig[:, 2],
+            "tilt_deg": plane[:, 3], "sigma_tilt_deg": np.asarray(result["sigma_tilt_deg"], dtype=np.float64),
+            "azimuth_deg": plane[:, 4], "sigma_azimuth_deg": np.asarray(result["sigma_azimuth_deg"], dtype=np.float64),
+            "camera_share": np.asarray(result["camera_share"], dtype=np.float64), "t2": np.asarray(result["t2"], dtype=np.float64),
+            "significant": np.asarray(result["significant"]).astype(bool),
+            "tilt_limit_deg": np.asarray(result["tilt_limit_deg"], dtype=np.float64)}
+    df = pd.DataFrame(cols, columns=list(POSE_UNCERTAINTY_COLUMNS))
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- shear, torsion and strain along a recording (k_motion.hip): the affine part of the field, globally and around every marker ----
 def motion_analysis(eng: Engine, table: torch.Tensor, ref_frame=0, slots=None, reject_k=0.0, neighbours=6, radius=None, min_count=4,
                     det_rel=0.01, taps=None, min_coverage=0.5):
