@@ -247,6 +247,12 @@ int vbs_ncc_template(int l, double sigma, double* g, double* stats);
  * (vbs_create then leaves the kernel as it was for that handle); the minimum goes to *min_d0 if given.  tbar_shift is
  * added to mean(t): 0 for the library's own use, anything else only shows the check failing. */
 int vbs_ncc_trim_guard(int l, double sigma, int height, int width, double tbar_shift, double* min_d0);
+/* host-only: the tiling the fused labelling kernel (k_stage) gives a height x width frame whose set bits (mask | area) have the
+ * bounding box [xlo, xhi] x [ylo, yhi] (xlo > xhi: an empty frame), for ns = 14 / 8 and 768 / 256 threads.  out[12] = the
+ * full-frame tiling {words per row, row blocks per wave, row blocks, rows per block}, the frame's own {first word column,
+ * words, row blocks per wave, row blocks, rows per block, first row}, the horizontal guard in pixels, and whether the frame's
+ * own tiling differs from the full-frame one.  VBS_EINVAL for a geometry the kernel does not take. */
+int vbs_stage_box_geom(int height, int width, int ns, int threads, int xlo, int xhi, int ylo, int yhi, int* out);
 
 /* MarkerTracker._undistort_frame (marker_detection.py:93-109), optional (`calibration_params` in the config):
  * getOptimalNewCameraMatrix(K, D, (w,h), 0) + initUndistortRectifyMap(CV_16SC2) are evaluated ONCE here (the

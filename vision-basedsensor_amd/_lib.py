@@ -36,7 +36,7 @@ OPT_GRAY_COEFFS, OPT_FORCE_SEQ_MATCH, OPT_NCC_MARGIN, OPT_STAGE_IMPL, OPT_BLUR_I
 
 # every symbol include/vbs.h declares (tests check the export list against the header)
 SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_contour_lut",
-           "vbs_gaussian_taps_q8", "vbs_ncc_template", "vbs_ncc_trim_guard", "vbs_set_undistort", "vbs_undistort_frames", "vbs_find_markers", "vbs_ncc_map", "vbs_normxcorr2",
+           "vbs_gaussian_taps_q8", "vbs_ncc_template", "vbs_ncc_trim_guard", "vbs_stage_box_geom", "vbs_set_undistort", "vbs_undistort_frames", "vbs_find_markers", "vbs_ncc_map", "vbs_normxcorr2",
            "vbs_profile", "vbs_profile_read", "vbs_frame_stats", "vbs_undistort_points", "vbs_calculate_3d", "vbs_marker_center",
            "vbs_track", "vbs_solve3d", "vbs_track_to_3d", "vbs_displacement", "vbs_displacement_range", "vbs_displacement_f64",
            "vbs_plane_fit", "vbs_assign_ids", "vbs_set_option", "vbs_bgr2gray", "vbs_ncc_counters", "vbs_normxcorr2_general",
@@ -108,6 +108,7 @@ def lib():
         "vbs_gaussian_taps_q8": (i32, [i32, f64, vp]),
         "vbs_ncc_template": (i32, [i32, f64, vp, vp]),
         "vbs_ncc_trim_guard": (i32, [i32, f64, i32, i32, f64, vp]),
+        "vbs_stage_box_geom": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "vbs_set_undistort": (i32, [vp, vp, vp, i32, vp, vp]),
         "vbs_undistort_frames": (i32, [vp, vp, i32, i32, i64, i64, vp, vp]),
         "vbs_find_markers": (i32, [vp, vp, i32, i32, i64, i64, vp, vp, vp]),

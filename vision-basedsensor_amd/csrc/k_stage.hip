@@ -44,6 +44,7 @@ struct StageGeom {
     u32 rec_cap, pq_cap, mom_comps; // LDS table sizes: band records, queued pairs, components per moment pass
     int stop;                       // debug builds: leave after phase `stop`
     int retry;                      // 1: the second chance of the frames the 256-thread instance could not hold (launch_stage)
+    int bbox;                       // 1: every frame is tiled over the bounding box of its own bits (stage_box_geom)
 };
 
 // exclusive prefix sum over the NT threads; tmp holds >= 17 words
@@ -141,19 +142,13 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
     u32* tmp = reinterpret_cast<u32*>(smem + geo.off_tmp);                                // [32]
     int* misc = reinterpret_cast<int*>(tmp + 32);                                         // [16]
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int H = geo.H, W = geo.W, WW = geo.WW, G = geo.G, R = geo.R, maxm = geo.maxm;
-    const int g = lane / WW, j = lane - g * WW;
-    const bool act = g < G;
-    const int blk = wave * G + g, y0 = blk * R;
-    const bool hasl = j > 0, hasr = act && j + 1 < WW;
-    const u64 vm = act ? valid_mask(j, W) : 0ull;
-    const int NBW = geo.NB * WW, bj = act ? blk * WW + j : 0;
-    const bool hasu = act && blk > 0;
+    const int H = geo.H, W = geo.W, WWF = geo.WW, maxm = geo.maxm;   // WWF: words of a frame row (addresses)
     const u32 sbase = (u32)tid * SG_SEGMAX;
     Q.n = &misc[5];
-    if (tid < 16) misc[tid] = 0;     // [0] Euler sum, [4] records, [5] queued pairs, [6] hand the frame on (why), [7] moment records
+    // [0] Euler sum, [4] records, [5] queued pairs, [6] hand the frame on (why), [7] moment records, [8 .. 11] the box of the set bits
+    if (tid < 16) misc[tid] = (tid == 8 || tid == 10) ? 0x7FFFFFFF : (tid == 9 || tid == 11) ? -1 : 0;
     mb_cnt[tid] = 0;
-    const int64_t fo = (int64_t)n * H * WW;
+    const int64_t fo = (int64_t)n * H * WWF;
     const u32 rec_cap = geo.rec_cap;
     unsigned short* rec_sid = reinterpret_cast<unsigned short*>(recb);                   // [rec_cap] records, by column
     u32* rec_pos = reinterpret_cast<u32*>(recb + 2 * rec_cap);
@@ -163,7 +158,6 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
     u32* seg_pos = reinterpret_cast<u32*>(recb);                                          // [8 NT] opened mask: first pixel by segment id
     // last-row slots of every tile; the component tables take their place once the tiles are linked
     u64* bot_mask = reinterpret_cast<u64*>(botb);                                         // [K][NBW]
-    unsigned short* bot_sid = reinterpret_cast<unsigned short*>(botb + (size_t)8 * SG_KB * NBW);   // [K][NBW]
     u32* comp_pos = reinterpret_cast<u32*>(botb);                                         // [1024] first pixel of a component
     unsigned short* cidmap = reinterpret_cast<unsigned short*>(botb + 4096);              // [1024] its rank = component id
     unsigned char* accb = botb + 4096 + 2048;                                            // band sums | anchors + moments
@@ -181,7 +175,63 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
         __syncthreads();                                 // (every thread has read the flag)
         if (tid == 0) { slow_flag[n] = 0u; atomicSub(slow_total, 1u); }
     }
+    // ---- the frame's own tiling.  A marker field leaves margins empty (at 1280x1024, 13x13 dots: 4 of 20 word columns and
+    //      ~100 rows), and a wave that spans the full width and G row blocks R rows apart hardly ever finds a row step with
+    //      nothing in it.  So, on the full-frame tiling first, every thread ORs the words of its column segment in BOTH
+    //      planes and notes the first and the last row that holds a bit (2 R independent loads, sixteen in flight, against
+    //      ~200 row steps of ~450 instructions); four LDS atomics per thread give the exact box of mask | area, and
+    //      stage_box_geom the window of word columns and the rows the workgroup is spread over instead: at 1280x1024,
+    //      16 words, G = 4 (all 64 lanes), 58 rows per tile instead of 86.  Everything below follows the per-frame values
+    //      (wave-uniform: scalar registers); word indices stay global, so image borders are what they were.
+    StageBox tb = {0, WWF, geo.G, geo.NB, geo.R, 0};
+    u64 sacc = 0;
+    int sfirst = 0x7FFFFFFF, slast = -1, sj = 0;
+    if (geo.bbox) {
+        const int g0 = lane / WWF;
+        sj = lane - g0 * WWF;
+        const int yb = (wave * geo.G + g0) * geo.R, ylast = min(yb + geo.R - 1, H - 1);   // (rows past the segment: its last row again)
+        const u64* Mp = mask_all + fo + sj;
+        const u64* Ap = area_all + fo + sj;
+#pragma unroll 1
+        for (int r = 0; r < geo.R; r += 8) {
+            u64 m[8], a[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int64_t o = (int64_t)min(yb + r + i, ylast) * WWF;
+                m[i] = Mp[o]; a[i] = Ap[o];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const u64 v = m[i] | a[i];
+                const int y = min(yb + r + i, ylast);
+                sacc |= v;
+                if (v) { sfirst = min(sfirst, y); slast = max(slast, y); }
+            }
+        }
+        if (g0 >= geo.G) sacc = 0;                       // (the lanes past the last row block)
+    }
     __syncthreads();
+    if (geo.bbox) {
+        if (sacc) {
+            atomicMin(&misc[8], 64 * sj + __ffsll((long long)sacc) - 1);
+            atomicMax(&misc[9], 64 * sj + 63 - __clzll((long long)sacc));
+            atomicMin(&misc[10], sfirst);
+            atomicMax(&misc[11], slast);
+        }
+        __syncthreads();
+        const int xlo = __builtin_amdgcn_readfirstlane(misc[8]), xhi = __builtin_amdgcn_readfirstlane(misc[9]);
+        const int ylo = __builtin_amdgcn_readfirstlane(misc[10]), yhi = __builtin_amdgcn_readfirstlane(misc[11]);
+        tb = stage_box_geom(W, WWF, geo.G, geo.NB, geo.R, NT, NS / 2, xlo, xhi, ylo, yhi);
+    }
+    const int WW = tb.WW, G = tb.G, NB = tb.NB, R = tb.R, ja = tb.ja, ylo = tb.ylo;
+    const int g = lane / WW, jl = lane - g * WW, j = ja + jl;       // j: the GLOBAL word column (addresses, pixel positions, borders)
+    const bool act = g < G;
+    const int blk = wave * G + g, y0 = ylo + blk * R;
+    const bool hasl = jl > 0, hasr = act && jl + 1 < WW;
+    const u64 vm = act ? valid_mask(j, W) : 0ull;
+    const int NBW = NB * WW, bj = act ? blk * WW + jl : 0;
+    const bool hasu = act && blk > 0;
+    unsigned short* bot_sid = reinterpret_cast<unsigned short*>(botb + (size_t)8 * SG_KB * NBW);   // [K][NBW]
 
     // ================================ band plane ====================================================================
     {
@@ -191,7 +241,7 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
         // steps after the load was issued); rows outside the image are loaded from a clamped address and replaced at use
         auto ldraw = [&](int r) -> u64 {
             const int y = min(max(y0 + r, 0), H - 1);
-            return M[(int64_t)y * WW + (act ? j : 0)];
+            return M[(int64_t)y * WWF + (act ? j : 0)];
         };
         auto rowval = [&](u64 raw, int r) -> u64 {       // source row y0 + r; outside the image: ones (ignored by the erosion)
             const int y = y0 + r;
@@ -349,8 +399,14 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
                 // one request per row and word: the pixel (ix + 1, py) rides along when it lies in the same word
                 const bool pair = (q & 1) == 0 && px + 1 < W && (px & 63) != 63;
                 if ((q & 1) && px > 0 && (px & 63) != 0) continue;                   // rode along with (ix, py)
-                const int ob = py / R, oi = py - ob * R, ow = ob / G, og = ob - ow * G;
-                const int owner = ow * 64 + og * WW + (px >> 6);
+                const int ry = py - ylo, wj = (px >> 6) - ja;
+                if (ry < 0 || ry >= NB * R || wj < 0 || wj >= WW) {           // outside the frame's tiling: background
+                    pr[c * 4 + q] = (unsigned short)NONE16;
+                    if (pair) pr[c * 4 + q + 1] = (unsigned short)NONE16;
+                    continue;
+                }
+                const int ob = ry / R, oi = ry - ob * R, ow = ob / G, og = ob - ow * G;
+                const int owner = ow * 64 + og * WW + wj;
                 const u32 slot = atomicAdd(&mb_cnt[owner], 1u);
                 if (slot < ST_MB_CAP)
                     mb_req[owner * ST_MB_CAP + slot] = c | ((u32)q << 10) | ((u32)oi << 12) | ((u32)(px & 63) << 19) | ((u32)pair << 25);
@@ -372,7 +428,7 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
         const u64* A = area_all + fo;
         auto ldraw = [&](int r) -> u64 {
             const int y = min(max(y0 + r, 0), H - 1);
-            return A[(int64_t)y * WW + (act ? j : 0)];
+            return A[(int64_t)y * WWF + (act ? j : 0)];
         };
         auto rowval = [&](u64 raw, int r) -> u64 {
             const int y = y0 + r;
@@ -453,7 +509,7 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
             // ---- Euler number by bit quads (8-connected foreground): E = (Q1 - Q3 - 2 QD) / 4 over all 2x2 windows of the
             //      zero-padded image; a word counts the windows whose top row is its row (image row 0 also the padding row)
             if (c >= 0) {
-                const bool top = (y0 + c) == 0;
+                const bool top = (y0 + c) == ylo;           // (the rows above the tiling are as empty as the padding row)
 #pragma unroll
                 for (int qq = 0; qq < 2; ++qq) {
                     if (qq == 1 && !top) continue;
@@ -623,7 +679,7 @@ __global__ __launch_bounds__(NT, 3) void k_stage(const u64* __restrict__ mask_al
             const u32 s = w0.x, cid = (u32)cidmap[P[s] & 0x7FFFu] - c0;
             if (cid >= nc) continue;                     // another pass's component
             const u32 ot = s / SG_SEGMAX, ol = ot & 63u, og = ol / (u32)WW;             // the thread that wrote it: its tile
-            const int ox = 64 * (int)(ol - og * (u32)WW) + 32, oy = (int)((ot >> 6) * (u32)G + og) * R + (R >> 1);
+            const int ox = 64 * (ja + (int)(ol - og * (u32)WW)) + 32, oy = ylo + (int)((ot >> 6) * (u32)G + og) * R + (R >> 1);
             const u32 fp = anchor[cid + c0];
             const i64 m[NMOM] = {(int)w0.y, (int)w0.z, (int)w0.w, (int)w1.x, (int)w1.y, (int)w1.z, (int)w1.w, (int)w2.x,
                                  (int)w2.y, (int)w2.z, (int)w2.w, (int)w3.x, (int)w3.y, (int)w3.z, (int)w3.w};
@@ -691,8 +747,17 @@ static bool stage_geom(const vbs_handle* h, const Workspace& w, StageGeom* g, si
     const size_t acc_band = up16((size_t)(8 * ((h->maxm + 1) / 2)) + 16 * (size_t)h->maxm);
     const size_t acc_open = up16((size_t)4 * CCL_OPEN_COMPS + (size_t)g->mom_comps * NMOM * 8);
     const size_t comp = 4096 + 2048 + (acc_band > acc_open ? acc_band : acc_open);
-    const size_t botc = bot > comp ? bot : comp;
     const size_t pq = (size_t)g->pq_cap * 4, mb = (size_t)nt * 4 * (1 + ST_MB_CAP), misc = 32 * 4 + 16 * 4;
+    // A frame's own tiling (stage_box_geom) has other row blocks and words, never more than nt tiles: the last-row tables are
+    // sized for nt then.  Where that would cost a handle its LDS budget (three 256-thread workgroups per CU), the handle
+    // keeps the full-frame tiling and its tables.  (VBS_STAGE_BBOX_OFF: the tools' library only, what the tests compare with.)
+    // The small branch (ns = 8: at most 480 rows, tiles of 15 - 20 rows under 17 rows of halo) keeps the full-frame tiling too:
+    // on its workloads the box gave 0.7 % (inside the noise) and 1.9 %, and which of its frames fill a tile's segment table
+    // is pinned to the full-frame tile rows (tests/test_gpu_labelling_oracle.py, `open_segs` at 480x640).
+    const size_t limit = (size_t)(half ? 160 * 1024 / 3 - 256 : 160 * 1024);
+    const size_t botn = up16((size_t)SG_KB * nt * 10);
+    g->bbox = h->bp.ns == 14 && !VBS_KNOB("VBS_STAGE_BBOX_OFF") && par + rec + (botn > comp ? botn : comp) + pq + mb + misc <= limit;
+    const size_t botu = g->bbox ? botn : bot, botc = botu > comp ? botu : comp;
     g->off_rec = (u32)par;
     g->off_bot = (u32)(par + rec);
     g->off_pq = (u32)(par + rec + botc);
@@ -704,7 +769,20 @@ static bool stage_geom(const vbs_handle* h, const Workspace& w, StageGeom* g, si
     // tiles of 5 rows, ~650 records against the 437 its slice holds) have their own buffer (alloc_workspace: stage_mrec)
     g->mrec_stride = w.stage_mrec ? 16u * (u32)SG_REC : 2u * (u32)h->H * (u32)h->WW;
     g->mrec_cap = g->mrec_stride / 16u < (u32)SG_REC ? g->mrec_stride / 16u : (u32)SG_REC;
-    return *lds_bytes <= (size_t)(half ? 160 * 1024 / 3 - 256 : 160 * 1024);
+    return *lds_bytes <= limit;
+}
+
+// host-only (include/vbs.h): the tilings k_stage gives a height x width frame whose set bits lie in [xlo, xhi] x [ylo, yhi]
+extern "C" int vbs_stage_box_geom(int height, int width, int ns, int threads, int xlo, int xhi, int ylo, int yhi, int* out) {
+    if (!out || height < 1 || width < 1 || (ns != 14 && ns != 8) || (threads != ST_NT && threads != ST_NT_SMALL)) return VBS_EINVAL;
+    const int WW = (width + 63) / 64;
+    if (WW > 64 || width > 4096 || height > 2048) return VBS_EINVAL;
+    const int G = 64 / WW, NB = (threads / 64) * G, R = (height + NB - 1) / NB;
+    if (R > 128) return VBS_EINVAL;
+    const StageBox b = stage_box_geom(width, WW, G, NB, R, threads, ns / 2, xlo, xhi, ylo, yhi);
+    const int v[12] = {WW, G, NB, R, b.ja, b.WW, b.G, b.NB, b.R, b.ylo, ns / 2, b.R != R};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return VBS_OK;
 }
 
 template <int NS, int NT>
@@ -736,6 +814,7 @@ bool launch_stage(vbs_handle* h, Workspace& w, int nb, int nt, hipStream_t s) {
         // there; a launch of workgroups that leave at once otherwise).
         if (stage_geom(h, w, &g, &lds, ST_NT)) {
             g.retry = 1;
+            g.bbox = 0;
             (void)(h->bp.ns == 14 ? stage_launch_t<14, ST_NT>(h, w, nb, g, lds, s) : stage_launch_t<8, ST_NT>(h, w, nb, g, lds, s));
         }
         return true;

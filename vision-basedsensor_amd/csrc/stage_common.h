@@ -20,6 +20,32 @@
 #define SLOW_RECS 7                // more segment / moment records than the frame's tables hold
 #define SLOW_PAIRS 8               // more queued unions than the queue holds
 
+// ---- k_stage's tiling of one frame: the window of word columns ja .. ja + WW - 1 and the rows from ylo on, cut into NB row
+//      blocks of R rows, G of them side by side in a wave --------------------------------------------------------------
+struct StageBox { int ja, WW, G, NB, R, ylo; };
+// The tiling of the frame whose set bits (mask | area) lie in [xlo, xhi] x [ylo, yhi], for a workgroup of nt threads whose
+// full-frame tiling is {0, WW, G, NB, R, 0}.  `guard` = the horizontal reach of the widest stencil: every set pixel then has
+// its whole horizontal window inside the word window (or cut by a TRUE image border, where the full-frame semantics hold:
+// the word indices stay global), so what is shifted in at an interior window edge never meets a set pixel.  Rows need no
+// guard: halo rows come from memory, rows outside the box are real zeros.
+// R never falls below half the full-frame R: a component of height h then meets ceil(h / R') + 1 <= 2 ceil(h / R) + 1 row
+// blocks: at most twice the records and queued pairs it had (a frame that fills a table all the same is handed on like
+// any other), and shorter tiles gain little: a tile of R rows costs
+// 2 R + NS + 9 row steps.  The full-frame tiling comes back for an empty frame (xlo > xhi) and whenever the box's is no shorter.
+__host__ __device__ inline StageBox stage_box_geom(int W, int WW, int G, int NB, int R, int nt, int guard, int xlo, int xhi, int ylo,
+                                                   int yhi) {
+    const StageBox full = {0, WW, G, NB, R, 0};
+    if (xlo > xhi || ylo > yhi) return full;
+    const int xa = xlo - guard > 0 ? xlo - guard : 0, xb = xhi + guard < W - 1 ? xhi + guard : W - 1;
+    const int ja = xa >> 6, WWe = (xb >> 6) - ja + 1;
+    const int Ge = 64 / WWe, NBe = (nt / 64) * Ge, Rmin = (R + 1) >> 1;
+    int Re = (yhi - ylo + NBe) / NBe;                    // ceil(rows / NB')
+    if (Re < Rmin) Re = Rmin;
+    if (Re >= R) return full;
+    const StageBox box = {ja, WWe, Ge, NBe, Re, ylo};
+    return box;
+}
+
 
 __device__ __forceinline__ u64 mk64(u32 lo, u32 hi) { return ((u64)hi << 32) | lo; }
 __device__ __forceinline__ u64 brev64(u64 x) {
