@@ -1361,6 +1361,82 @@ int vbs_pose_cov(int device, const float* table, int n, int m_ref, int start_fra
                  const double* obs_cov, int obs_rows, const double* cam_factor, int q, double min_marker_size_px, double piv_rel,
                  const float* ref_rows, int frame_begin, int frame_end, double* work, double* pose, double* pcov, void* stream);
 
+/* vbs_refine_markers - centre, area, diameter and axes of every tracked marker measured from the grey levels themselves (ours:
+ * the reference has no grey-level measurement; table column 3 is the axis of an ellipse fitted to a thresholded contour).
+ * Handle-free, opt-in; vbs_track, vbs_track_to_3d and every other output stay what they are.
+ *   gray [dev] uint8 [n,h,w] with strides (a crop view is fine): the frames the detector saw (after vbs_undistort_frames where
+ *   that is set).  table [dev] float32 [n,m_ref,VBS_TABLE_COLS] as vbs_track writes it.
+ * THE RULE, per table row.  Everything up to the six sums is integer, so nothing depends on an order of summation; a handful of
+ * float64 operations without contraction follow.  Every expression and tie-break below is part of the interface.
+ *   Setup.  flags = (int)row[0] where 0 <= row[0] < 2^24, else 0.  Cx, Cy, major = the float32 columns 1, 2, 3 widened to double.
+ *   1. Geometry.  r = 0.5 major;  x0 = (int)floor(Cx + 0.5), y0 likewise;  R = (int)ceil(ring_f r) + 1;  c2 = floor((core_f r)
+ *      (core_f r)), g2 = floor((disc_f r) (disc_f r)), R2 = R R;  d2 = dx dx + dy dy with the integer offsets from (x0, y0).
+ *      Core = {d2 <= c2}, disc = {d2 <= g2}, ring = {g2 < d2 <= R2}.
+ *   2. Status (rec column 0), the first match wins:
+ *        1  not tracked (flags without VBS_FLAG_TRACKED)
+ *        2  Cx, Cy or major not finite, major < 2, or |Cx| or |Cy| >= 2^30
+ *        3  ceil(ring_f r) + 1 > VBS_REFINE_MAX_R (decided in float64, before the conversion): the window is never truncated
+ *        4  the square [x0 - R, x0 + R] x [y0 - R, y0 + R] is not wholly inside the frame: no pixel outside the frame is read
+ *        5  low contrast: C8 < 8 min_contrast
+ *        6  degenerate: S0 <= 0, or not l2 > 0
+ *        7  moved: shift > max_shift_f r
+ *        0  refined
+ *      A row with status 1 .. 4 costs no pixel load.
+ *   3. Levels.  A pixel's level is v, with polarity 1 (bright markers) 255 - v.  For a set of pixels with the level histogram H
+ *      and `total` pixels, q(num) is the smallest level whose cumulative count times 4 is >= total num, and
+ *        T8(set) = (8 sum{v H[v] : q(1) <= v <= q(3)}) / sum{H[v] : q(1) <= v <= q(3)}        integer division
+ *      the mean of the two middle quarters in eighths of a level (whole bins: every pixel AT q(1) or q(3) counts).  B8 = T8(ring),
+ *      D8 = T8(core), C8 = B8 - D8.  The ring is trimmed so that a neighbour's edge or a highlight in it does not move the
+ *      background level.
+ *   4. Sums over the disc, int64:  wgt = min(max(B8 - 8 v, 0), C8);  S0 = sum wgt, Sx = sum wgt dx, Sy = sum wgt dy, Sxx = sum wgt
+ *      dx dx, Sxy = sum wgt dx dy, Syy = sum wgt dy dy.
+ *   5. Float64, PI = 3.14159265358979323846:
+ *        A = (double)S0 / (double)C8;   d_area = 2.0 sqrt(A / PI)                              [status 6 if S0 <= 0]
+ *        cx = (double)x0 + (double)Sx / (double)S0, cy likewise;   shift = hypot(cx - Cx, cy - Cy)
+ *        mxx = (double)(Sxx S0 - Sx Sx) / ((double)S0 (double)S0), mxy from Sxy S0 - Sx Sy, myy from Syy S0 - Sy Sy (the
+ *        numerators are int64)
+ *        t = 0.5 (mxx + myy);  hd = 0.5 (mxx - myy);  q = sqrt(hd hd + mxy mxy);  l1 = t + q;  l2 = t - q     [status 6 unless l2 > 0]
+ *        k = sqrt(sqrt(l1 / l2));  major' = d_area k;  minor' = d_area / k
+ *        angle = (0.5 atan2(2.0 mxy, mxx - myy)) 180.0 / PI + 180.0
+ *        edge_var = sqrt(l1 l2) - A / (4.0 PI)
+ *      Blur inflates the moments but conserves the integral: the SIZE comes from the area, only the axis ratio and the direction
+ *      come from the moments.  edge_var is the excess of the second moment over a sharp ellipse's, about sigma^2 of the optics: a
+ *      focus measure.  The angle is table column 5's convention - cv2.fitEllipse's angle plus 90 where its first axis is the shorter
+ *      (marker_detection.py:217; k_finalize keeps the shorter axis first, so always): the direction of the MAJOR axis in degrees
+ *      from +x towards +y (y down), modulo 180, in [90, 270) there and in (90, 270] here.
+ * Outputs, each may be NULL (all three NULL: VBS_EINVAL):
+ *   rec [dev] float64 [n,m_ref,VBS_REFINE_COLS] = status, cx, cy, major', minor', angle, d_area, A, B8 / 8.0, D8 / 8.0, edge_var,
+ *     shift.  Status 0 and 7: every column.  Status 5: columns 8, 9.  Status 6 with S0 <= 0: columns 6 .. 9; with S0 > 0 also 1, 2
+ *     and 11.  Every other cell after column 0 is 0.
+ *   sums [dev] int64 [n,m_ref,VBS_REFINE_SUM_COLS] = B8, D8, S0, Sx, Sy, Sxx, Sxy, Syy.  Status 1 .. 4: zeros; status 5: B8, D8.
+ *   table_out [dev] float32 [n,m_ref,VBS_TABLE_COLS]: every row has VBS_FLAG_XYZ clear, X, Y, Z = 0 and column 9 (det_index) as it
+ *     came, so vbs_solve3d runs on it as on vbs_track's output.  Status 0: flags = VBS_FLAG_TRACKED, columns 1 .. 5 = cx, cy,
+ *     major', minor', angle, each cast to float32 once.  Any other status: a gap (columns 0 .. 8 zero) - or, with keep_unrefined
+ *     and a status >= 2, the input row's columns 0 .. 5 with VBS_FLAG_XYZ cleared.  The gap is the default: a series that mixes
+ *     two estimators with a systematic offset carries steps.
+ * Defaults of the shim: core_f 0.5, disc_f 1.5, ring_f 2.0, min_contrast 16, max_shift_f 1.0, polarity 0, keep_unrefined 0.
+ * VBS_EINVAL, before a device is selected: a null gray or table, n < 0, m_ref < 1, n m_ref >= 2^30, h or w outside 1 .. 16384,
+ * stride_row < w, parameters that are not finite or not 0 < core_f <= disc_f <= ring_f <= 64, min_contrast outside [0.125, 255]
+ * (so C8 >= 1 wherever it divides), max_shift_f < 0, polarity or keep_unrefined other than 0 / 1.
+ * The bound behind the int64 products at R = VBS_REFINE_MAX_R: a window holds at most 127 x 127 pixels of weight <= 8 x 255 =
+ * 2040 and |dx|, |dy| <= 63, so S0 <= 2040 x 16129 < 2^25, |Sx| <= 63 S0 < 2^31 and Sxx <= 3969 S0 < 2^37: Sxx S0 < 2^62 and
+ * Sx Sx < 2^62 (tests/test_refine_host.py proves it with Python integers for the all-saturated window). */
+#define VBS_REFINE_COLS     12   /* status, cx, cy, major', minor', angle, d_area, A, B8/8, D8/8, edge_var, shift */
+#define VBS_REFINE_SUM_COLS 8    /* B8, D8, S0, Sx, Sy, Sxx, Sxy, Syy                                            */
+#define VBS_REFINE_MAX_R    63   /* the window is at most 127 x 127: two columns a lane                          */
+#define VBS_REFINE_WAVES    4    /* table rows a workgroup takes, one wave each (no result depends on it)        */
+#define VBS_REFINE_NOT_TRACKED  1
+#define VBS_REFINE_BAD_ROW      2
+#define VBS_REFINE_TOO_LARGE    3
+#define VBS_REFINE_AT_BORDER    4
+#define VBS_REFINE_LOW_CONTRAST 5
+#define VBS_REFINE_DEGENERATE   6
+#define VBS_REFINE_MOVED        7
+int vbs_refine_markers(int device, const uint8_t* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row,
+                       const float* table, int m_ref, double core_f, double disc_f, double ring_f, double min_contrast,
+                       double max_shift_f, int polarity, int keep_unrefined, double* rec, int64_t* sums, float* table_out,
+                       void* stream);
+
 /* Frame-0 identity assignment on the device — `MarkerTracker._process_first_frame`
  * (marker_detection.py:275-347; inlined again at tracking.py:106-178): the marker nearest the mean is (0,0), the
  * others' radii are clustered into `num_layers` rings (exact 1-D k-means, the deterministic stand-in for the

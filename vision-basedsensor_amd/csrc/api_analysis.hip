@@ -347,3 +347,21 @@ extern "C" int vbs_pixel_noise(int device, const float* table, int n, int m_ref,
     launch_pixel_noise(table, m_ref, frame_begin, frame_end, out, (hipStream_t)stream);
     return launched();
 }
+
+// ---- grey-level refinement of tracked markers (k_refine.hip) ---------------------------------------------------------------------
+extern "C" int vbs_refine_markers(int device, const uint8_t* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row,
+                                  const float* table, int m_ref, double core_f, double disc_f, double ring_f, double min_contrast,
+                                  double max_shift_f, int polarity, int keep_unrefined, double* rec, int64_t* sums,
+                                  float* table_out, void* stream) {
+    if (!gray || !table || (!rec && !sums && !table_out) || n < 0 || m_ref < 1 || (int64_t)n * m_ref >= (1 << 30) || h < 1 || w < 1 ||
+        h > 16384 || w > 16384 || stride_row < w || !std::isfinite(core_f) || !std::isfinite(disc_f) || !std::isfinite(ring_f) ||
+        !(core_f > 0.0) || !(core_f <= disc_f) || !(disc_f <= ring_f) || !(ring_f <= 64.0) || !(min_contrast >= 0.125) ||
+        !(min_contrast <= 255.0) || !std::isfinite(max_shift_f) || !(max_shift_f >= 0.0) || (polarity != 0 && polarity != 1) ||
+        (keep_unrefined != 0 && keep_unrefined != 1))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (n)
+        launch_refine(gray, n, h, w, stride_n, stride_row, table, m_ref, core_f, disc_f, ring_f, min_contrast, max_shift_f, polarity,
+                      keep_unrefined, rec, (i64*)sums, table_out, (hipStream_t)stream);
+    return launched();
+}

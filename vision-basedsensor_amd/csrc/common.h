@@ -318,6 +318,10 @@ size_t retrack_workspace_bytes(int n, int m, int max_det);
 void launch_retrack(const double* det, const int32_t* counts, int n, int max_det, const double* ref_xy, int m, const double* state_in,
                     double gate, double max_travel, double vel_gain, int max_coast, int32_t* assign, float* table, double* dist2,
                     int32_t* info, double* state_out, void* workspace, hipStream_t st);
+// k_refine.hip (f23): grey-level refinement of the tracked rows of a table, one wave a row; every output may be null
+void launch_refine(const u8* gray, int n, int h, int w, int64_t stride_n, int64_t stride_row, const float* table, int m_ref,
+                   double core_f, double disc_f, double ring_f, double min_contrast, double max_shift_f, int polarity,
+                   int keep_unrefined, double* rec, i64* sums, float* table_out, hipStream_t s);
 // k_calib.hip (f9): homographies of nv views, then nb calibration problems over subsets of them
 void launch_calib(const double* obj, int n, const double* img, int nv, const u8* view_mask, int nb, int w, int h, int max_iter,
                   double* H, int32_t* view_void, int32_t* status, double* K4, double* dist, double* R, double* T, double* rms,

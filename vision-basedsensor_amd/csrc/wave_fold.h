@@ -21,6 +21,12 @@ __device__ __forceinline__ int wave_fold_down(int v) {
     return v;
 }
 
+__device__ __forceinline__ long long wave_fold_down(long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
 // every lane gets lane 0's sum
 __device__ __forceinline__ double wave_sum(double v) { return __shfl(wave_fold_down(v), 0); }
 __device__ __forceinline__ int wave_sum(int v) { return __shfl(wave_fold_down(v), 0); }

@@ -314,6 +314,53 @@ class Engine:
                 f"vbs_corner_subpix: bad argument (window half-sizes 1..{L.CHESS_MAX_WIN}) or HIP error (status {rc})")
         return (c, iters) if want_iters else c
 
+    # ---- grey-level refinement of the tracked markers (k_refine.hip; the rule: include/vbs.h) ----
+    def refine_markers(self, frames, table, want=("rec", "sums", "table"), **params):
+        """Centre, area, diameter and axes of every tracked row of `table` measured from the grey levels of `frames`
+        (`vbs_refine_markers`): threshold-free, normalised by each marker's own local contrast.  frames: gray or BGR (BGR goes
+        through k_gray), uint8 tensor or array, [n,H,W(,3)] or one frame, strided crops included.  They must be THE FRAMES THE
+        DETECTOR SAW: after `undistort_frames` when undistortion is set on the engine, and the crop the table's coordinates
+        refer to.  table float32 [n, m, 10] as `track` / `track_to_3d` return it (not modified).  `params`: core_f, disc_f,
+        ring_f, min_contrast, max_shift_f, polarity, keep_unrefined (`refine.DEFAULTS`), and `passes` (default 1): the rule
+        assumes a start within a pixel or two of the truth - its disc is 1.5 x the START's radius - which the detector's
+        diameter is not at low contrast; with passes = k the rule runs k times, each pass starting from the rows the pass
+        before wrote (a row it could not refine keeps its start until the last pass, which applies `keep_unrefined`); `rec` and
+        `sums` are the last pass's, so `shift` is the last pass's step.
+        Returns (rec float64 [n, m, 12], sums int64 [n, m, 8], table float32 [n, m, 10]) as device tensors - None for those
+        not in `want`; the returned table is `track`'s format with X, Y, Z unset, for `solve3d`.  No synchronisation."""
+        from .refine import params as _params
+        p = _params(True, **params)
+        passes = p.pop("passes", 1)
+        unknown = sorted(set(want) - {"rec", "sums", "table"})
+        if unknown or not want:
+            raise ValueError(f"refine_markers: want is a non-empty subset of rec, sums, table (got {list(want)})")
+        g = self._gray_batch(frames)
+        n = g.shape[0]
+        t = table if isinstance(table, torch.Tensor) else torch.from_numpy(np.asarray(table, dtype=np.float32))
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or t.shape[0] != n or t.shape[2] != L.TABLE_COLS or t.shape[1] < 1:
+            raise ValueError(f"table must be [n = {n}, m >= 1, {L.TABLE_COLS}] for these frames")
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        m = t.shape[1]
+        rec = torch.empty((n, m, L.REFINE_COLS), dtype=torch.float64, device=self.device) if "rec" in want else None
+        sums = torch.empty((n, m, L.REFINE_SUM_COLS), dtype=torch.int64, device=self.device) if "sums" in want else None
+        out = torch.empty((n, m, L.TABLE_COLS), dtype=torch.float32, device=self.device) if "table" in want else None
+        mid = torch.empty_like(t) if passes > 1 else None
+        with torch.cuda.device(self.device):
+            for k in range(passes):
+                last = k == passes - 1
+                rc = self.lib.vbs_refine_markers(self.device.index, _ptr(g), n, self.H, self.W, g.stride(0), g.stride(1), _ptr(t), m,
+                                                 p["core_f"], p["disc_f"], p["ring_f"], p["min_contrast"], p["max_shift_f"],
+                                                 p["polarity"], p["keep_unrefined"] if last else 1, _ptr(rec) if last else None,
+                                                 _ptr(sums) if last else None, _ptr(out) if last else _ptr(mid), self._stream())
+                if rc != L.VBS_OK:
+                    raise (ValueError if rc == L.VBS_EINVAL else L.VbsError)(
+                        f"vbs_refine_markers: bad argument or HIP error (status {rc})")
+                if not last:
+                    t, mid = mid, (torch.empty_like(t) if k == 0 else t)      # (never write into the caller's table)
+        return rec, sums, out
+
     def track(self, det, counts, ref_xy, min_dist=20.0):
         ref = torch.as_tensor(ref_xy, dtype=torch.float64, device=self.device).contiguous().reshape(-1, 2)
         if det.dtype != torch.float64 or not det.is_contiguous() or det.device != self.device or det.dim() != 3 \

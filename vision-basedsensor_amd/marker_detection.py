@@ -19,6 +19,12 @@ Differences a maintainer should know (all deliberate):
  * extra optional config keys: `id_mode` ("as_written" | "full"), `kmeans` ("optimal" | "sklearn"),
    `device` (GPU index), `batch` (frames per device batch), `gray_coeffs` (15 = OpenCV 4's BGR2GRAY fixed-point
    set, the default; 14 = the older set; identical on grey frames).
+ * `refine` (opt-in: True or a dict of `refine.DEFAULTS` keys and `passes`): centre, axes and angle of every tracked row are
+   re-measured from the grey levels (`Engine.refine_markers`) and CSV, video and `.rows` follow the refined
+   table; `self.refine_report` counts every status.  Absent, None or False: nothing changes.  ONE PASS ASSUMES A START WITHIN A
+   PIXEL OR TWO: where the detector's diameter is far too small (low contrast: 11 px for a 20 px dot at 150/100) a single pass
+   returns status 0 and is still pixels short.  `refine_report["uncovered"]` counts such rows and a warning names them; set
+   `passes` to 2 or 3 there.
  * a frame the device workspace cannot hold (more than 30720 runs in a mask, more than 1024 band components or more
    than about 512 contours) RAISES with its frame number instead of being dropped; the rows of the batches before it are
    written to the CSV first (`process`) / ride on the exception as `.rows` (`process_frames`).
@@ -31,6 +37,7 @@ import os
 import numpy as np
 
 from . import ids as _ids
+from . import refine as _refine
 from . import retrack as _retrack
 
 CSV_COLUMNS = ["frameno", "row", "col", "Ox", "Oy", "Cx", "Cy", "major_axis", "minor_axis", "angle"]
@@ -513,6 +520,30 @@ class MarkerTracker:
             info = out["info"].cpu().numpy()
             prev = getattr(self, "retrack_report", None)
             self.retrack_report = {"info": info if prev is None else np.concatenate([prev["info"], info]), "params": rt}
+        rf = _refine.params(self.config.get("refine"))
+        if rf is not None:
+            # centre, axes and angle of every tracked row re-measured from the grey levels of the frames the detector saw; a row
+            # that could not be refined is a gap (or the detection's row with keep_unrefined).  CSV, video and `.rows` follow
+            from .refine import report as _refine_report
+            src = eng.undistort_frames(ft) if self.config.get("calibration_params") is not None else ft
+            rec, _, refined = eng.refine_markers(src, table, **rf)
+            rep = _refine_report(rec, table, rf["disc_f"])
+            prev = getattr(self, "refine_report", None) if self.frame_count else None
+            self.refine_report = {"status_per_frame": rep["status_per_frame"] if prev is None else
+                                  np.concatenate([prev["status_per_frame"], rep["status_per_frame"]]),
+                                  "status_per_slot": rep["status_per_slot"] if prev is None else
+                                  prev["status_per_slot"] + rep["status_per_slot"],
+                                  "uncovered": int(rep["uncovered"].sum()) + (0 if prev is None else prev["uncovered"]), "params": rf}
+            if rf.get("passes", 1) == 1 and rep["uncovered"].any():
+                import warnings
+                warnings.warn(f"refine: {int(rep['uncovered'].sum())} refined rows of this batch started from a diameter so small that "
+                              "the disc did not cover the marker; they are still short - set config['refine']['passes'] to 2 or 3")
+            # the video draws every ellipse from the detection row a slot points to: give it the refined values there (two slots
+            # of the per-frame rule that share one detection share its row: the later slot's values are drawn for both)
+            fi_d, si_d = torch.nonzero(refined[..., 0].to(torch.int64) & 1, as_tuple=True)
+            det = det.clone()
+            det[fi_d, refined[fi_d, si_d, 9].to(torch.int64), :5] = refined[fi_d, si_d, 1:6].to(torch.float64)
+            table = refined
         table_d, det_d = table, det
         counts = counts.cpu().numpy()
         if (counts < 0).any():                  # the reference would have emitted rows: never drop a frame silently
@@ -531,6 +562,9 @@ class MarkerTracker:
         block = {"frameno": self.frame_count + fi, "row": np.asarray(ids)[si, 0].astype(np.int64),
                  "col": np.asarray(ids)[si, 1].astype(np.int64), "Ox": refs[si, 0], "Oy": refs[si, 1],
                  "Cx": d[:, 0], "Cy": d[:, 1], "major_axis": d[:, 2], "minor_axis": d[:, 3], "angle": d[:, 4]}
+        if rf is not None:                       # the refined table's own float32 columns, not the detection it started from
+            for c, name in enumerate(("Cx", "Cy", "major_axis", "minor_axis", "angle"), start=1):
+                block[name] = table[fi, si, c].astype(np.float64)
         if video:
             self._video_batch(eng, ft, det_d, table_d, ref_xy)
         n_before = self.frame_count

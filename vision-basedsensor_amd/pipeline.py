@@ -1489,6 +1489,61 @@ def to_retrack_frame(report, frame_offset=0, path=None):
     return df
 
 
+# ---- grey-level refinement of the tracked markers (k_refine.hip) --------------------------------------------------------------------
+def refine_table(eng: Engine, frames, table, cam=None, min_marker_size_px=5.0, **params):
+    """The table with centre, diameter, axes and angle of every tracked marker re-measured from the grey levels
+    (`Engine.refine_markers`): the size from the integral of the contrast-normalised darkness - which blur and
+    contrast leave alone - instead of from the contour of a threshold.  `frames` are the frames the detector saw (see
+    `Engine.refine_markers`), `table` what `eng.track` / `eng.track_to_3d` / `retrack_table` returned for them; `params`:
+    `refine.DEFAULTS`.  Returns (table, report).  table float32 [n, m, 10] is `eng.track`'s format - a row that could not be
+    refined is a gap unless `keep_unrefined` - and with `cam`, `eng.solve3d` has run on it, so `despike_table`, `fill_table`
+    and every `*_analysis` take it as it is.  report: `refine.report` of the run (status counts per frame and per slot, per slot
+    mean and standard deviation of major' - major and of the shift, the slots never refined, the median edge_var, and
+    `uncovered`: rows with status 0 whose disc did not cover the marker - a start far too small; they are still short and want
+    `passes` > 1) plus `rec` and `sums` as the engine returned them."""
+    from .refine import report as _report
+    rec, sums, out = eng.refine_markers(frames, table, **params)
+    if cam is not None:
+        eng.solve3d(out, cam, min_marker_size_px)
+    rep = _report(rec, table, params.get("disc_f", 1.5))
+    if params.get("passes", 1) > 1:
+        # `uncovered` is about the LAST pass's start, which is not `table`: a table refined again is its own start to within the
+        # rule's accuracy, so judge the disc of one more pass from the result
+        rep["uncovered"] = _report(rec, out, params.get("disc_f", 1.5))["uncovered"]
+        rep["uncovered_per_slot"] = rep["uncovered"].sum(axis=0).astype(np.int64)
+    rep["rec"], rep["sums"] = rec, sums
+    return out, rep
+
+
+def to_refine_frame(report, ids=None, path=None):
+    """The sheet of `refine_table`: one row per slot - `slot` (and `marker_id` with `ids`), the count of every status under its
+    name, `dmajor_mean`, `dmajor_std`, `shift_mean`, `shift_std`, `uncovered`.  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    from .refine import STATUS_NAMES
+    per_slot = np.asarray(report["status_per_slot"])
+    if per_slot.ndim != 2 or per_slot.shape[1] != 8:
+        raise ValueError("report must hold status_per_slot [m, 8] as refine_table returns it")
+    data = {"slot": np.arange(per_slot.shape[0], dtype=np.int64)}
+    if ids is not None:
+        mid = _ids.marker_ids(ids)
+        if len(mid) != per_slot.shape[0]:
+            raise ValueError(f"{len(mid)} ids for {per_slot.shape[0]} slots")
+        data["marker_id"] = mid
+    for s in range(8):
+        data[STATUS_NAMES[s]] = per_slot[:, s].astype(np.int64)
+    for k in ("dmajor_mean", "dmajor_std", "shift_mean", "shift_std"):
+        data[k] = np.asarray(report[k], dtype=np.float64)
+    data["uncovered"] = np.asarray(report["uncovered_per_slot"], dtype=np.int64)
+    df = pd.DataFrame(data)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 def to_marker_frame(table, ids, frame_offset=0, path=None):
     """The sheet the reference's L4 scripts read (`LocalAnalysis.py:47,58`, `MarkerDisplacement.py:72,80`): one row
     `frameno, marker_id, Xw, Yw, Zw` per table entry with a 3-D point, frame-major; `marker_id` = `ids.marker_ids`.
