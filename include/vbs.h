@@ -1361,6 +1361,73 @@ int vbs_pose_cov(int device, const float* table, int n, int m_ref, int start_fra
                  const double* obs_cov, int obs_rows, const double* cam_factor, int q, double min_marker_size_px, double piv_rel,
                  const float* ref_rows, int frame_begin, int frame_end, double* work, double* pose, double* pcov, void* stream);
 
+/* Indentation shape along a recording (ours: the reference ships no code for this): a second-order fit in SPACE, per frame, to the
+ * end points vbs_pose_series fits its plane to - where the bowl the plane leaves behind has its apex, how deep it is below the
+ * plane, how strongly and in which direction it is curved.  Handle-free; float64 without contraction, + - * / only in everything
+ * but the columns rms_plane, rms, k1, k2 and dir_deg; no atomics; every sum over slots follows the rule of vbs_axis_displacement
+ * (lane l of 64 adds slots l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1).  No result depends on the launch shape, on
+ * the frame range or on VBS_SHAPE_GROUP (the frames a workgroup takes, one wave each); tests/helpers/shape_oracle.py restates every
+ * expression bit for bit.  The call allocates nothing.
+ * vbs_shape_series - table, start_frame, ref_disp, ref_xyz, slot_mask, shell_mode, scale and the frame range exactly as
+ *   vbs_pose_series takes them: the COMMON rule, the deviation d and the end point P are that entry's, bit for bit.  Nothing of a
+ *   slot that is not common is read into a value: such cells may hold NaN.  length > 0 scales x and y (a length of the marker
+ *   field, so that the monomials are of order 1); the results do not carry it.
+ * THE FIT of a set of slots (the common set; then once its kept slots): count, the means mx, my, mz of P (sum / count); per slot
+ *     u = (Px - mx) / length,  v = (Py - my) / length,  w = Pz - mz
+ *     u2 = u u, uv = u v, v2 = v v;  u3 = u2 u, u2v = u2 v, uv2 = u v2, v3 = v2 v;  u4 = u2 u2, u3v = u3 v, u2v2 = u2 v2, uv3 = u v3,
+ *     v4 = v2 v2
+ *   the 14 sums of u, v, u2, uv, v2, u3, u2v, uv2, v3, u4, u3v, u2v2, uv3, v4 (the first two kept as computed, not taken as zero) and
+ *   the 6 sums of w, u w, v w, u2 w, uv w, v2 w.  (The sum of w w has no reader - residuals are explicit - and is not formed.)  With
+ *   the basis phi = (1, u, v, u2, uv, v2) the normal matrix is N_ij = sum phi_i phi_j read from those sums, N_00 = count as a
+ *   double, and the right-hand side g_i = sum phi_i w.  With count < 3 nothing is summed and the degree is 0.
+ *   LDL' without square roots and without pivoting, column j = 0 .. 5 in basis order, every inner sum subtracted from the left with
+ *   k ascending:
+ *     d_j = N_jj - sum_{k<j} L_jk c_jk;      for i > j:  c_ij = N_ij - sum_{k<j} L_jk c_ik,   L_ij = c_ij / d_j
+ *   (the 3 x 3 of vbs_uncert_cov continued: d_1 = N11 - L10 c10, c21 = N21 - L10 c20, d_2 = (N22 - L20 c20) - L21 c21, ..).  Pivot j
+ *   PASSES when d_j > piv_rel N_jj; the factorisation stops at the first that does not.  Its leading 3 x 3 is the factorisation of
+ *   the plane's normal equations, so one factorisation serves both degrees.  Forward: z_i = g_i - sum_{k<i} L_ik z_k, y_i = z_i / d_i.
+ *   DEGREE 2 when count >= min_count and all six pivots pass: beta_5 = y_5, beta_i = y_i - sum_{k>i} L_ki beta_k (k ascending).
+ *   DEGREE 1 when the first three pass: gamma_2 = y_2, gamma_1 = y_1 - L_21 gamma_2, gamma_0 = (y_0 - L_10 gamma_1) - L_20 gamma_2;
+ *   gamma is computed where degree 2 exists as well.  DEGREE 0 otherwise.  This degree-1 fit is the same least-squares plane as
+ *   vbs_pose_series's but NOT its bits (that entry solves the centred 2 x 2 in closed form); the two agree to rounding.
+ *   Residuals are explicit, never from the moment identity:
+ *     r1 = w - ((gamma_0 + gamma_1 u) + gamma_2 v)
+ *     r2 = w - (((((beta_0 + beta_1 u) + beta_2 v) + beta_3 u2) + beta_4 uv) + beta_5 v2)
+ *   SSR1 = sum r1 r1 and, at degree 2, SSR2 = sum r2 r2 by the same rule.
+ * ONE ROUND OF REJECTION, as vbs_pose_series words it: only when reject_k > 0, the first fit has a degree >= 1 and the SSR of that
+ *   degree is > 0.  Kept are the common slots with r r <= (reject_k reject_k) (SSR / count), r the first fit's residual of that
+ *   degree.  If fewer are kept than are common and the kept set, fitted by the same rules, reaches the first fit's degree (degree 2:
+ *   kept >= min_count and six pivots; degree 1: kept >= 3 and three pivots), every quantity is that of the kept set at THAT degree
+ *   and n_used = kept; otherwise the first fit stands and n_used = count.
+ *   shape [dev] float64 [fe-fb,VBS_SHAPE_COLS] (may be NULL), zeros where the degree does not allow a column:
+ *     0 degree  1 count  2 n_used  3-5 mx, my, mz of the used set (where count >= 1)
+ *     6 c0 = mz + beta_0               7 a = beta_1 / length            8 b = beta_2 / length        (at degree 1 from gamma)
+ *     9 p = ((2.0 beta_3) / length) / length   10 q = (beta_4 / length) / length   11 r = ((2.0 beta_5) / length) / length
+ *     12 rms_plane = sqrt(SSR1 / n_used)       13 rms = sqrt(SSR2 / n_used) at degree 2
+ *     14 H = (p + r) / 2.0    15 K = p r - q q    16, 17 k1 = H + s, k2 = H - s with hd = (p - r) / 2.0, s = sqrt(hd hd + q q)
+ *     18 dir_deg = (0.5 atan2(2.0 q, p - r)) 57.29577951308232, the direction of k1
+ *     19 apex (1 = valid)     20-22 apex_x = mx + xi, apex_y = my + eta, apex_z = c0 + (a xi + b eta) / 2.0
+ *     23 depth = apex_z - (mz + ((gamma_0 + (gamma_1 xi) / length) + (gamma_2 eta) / length)): the quadric below the plane there
+ *   so that z ~ c0 + a x + b y + (p x x + 2 q x y + r y y) / 2 in x = Px - mx, y = Py - my.  The apex is the stationary point by
+ *   Cramer, xi = (q b - r a) / K, eta = (q a - p b) / K, valid only at degree 2 where |K| > apex_rel ((p p + 2.0 (q q)) + r r) and
+ *   xi xi + eta eta <= (max_apex length) (max_apex length): squared comparisons, no root decides.  A nonzero degree keeps a row
+ *   readable as a FIR record.  Columns 12, 13, 16, 17, 18 pass through sqrt or atan2 (held to 4 ulp); every other column is exact.
+ *   coef [dev] float64 [fe-fb,2,4] (may be NULL) = (degree, c0, a, b), (degree == 2 ? 1 : 0, p, q, r): seen as [F, s = 2, cols = 4]
+ *     with n_values = 3 a vbs_fir_series_f64 record as it is (trends are taken from filtered coefficients, never from filtered
+ *     curvatures or angles).
+ *   residual [dev] float64 [fe-fb,m_ref,2] (may be NULL) = (1, r) of the standing fit's degree for every used slot where that degree
+ *     is >= 1, (0, 0) elsewhere: a vbs_field_map_f64 record as it is - the map of what no smooth surface explains.
+ * VBS_EINVAL, before a device is selected and with nothing written: what vbs_pose_series refuses (a null table, ref_disp or
+ *   ref_xyz, n or m_ref < 1, start_frame outside [0, n), a shell_mode other than 0 / 1, a scale or reject_k that is not finite,
+ *   reject_k < 0, frames outside 0 <= frame_begin <= frame_end <= n), length not finite or <= 0, min_count < 6, piv_rel, apex_rel or
+ *   max_apex not finite or < 0, and all three outputs NULL.  frame_begin == frame_end emits nothing. */
+#define VBS_SHAPE_COLS  24      /* degree, count, n_used, means [3], c0, a, b, p, q, r, two rms, H, K, k1, k2, dir, apex [4], depth */
+#define VBS_SHAPE_GROUP 4       /* frames a workgroup takes, one wave each (no result depends on it)     */
+int vbs_shape_series(int device, const float* table, int n, int m_ref, int start_frame, const double* ref_disp, const double* ref_xyz,
+                     const uint8_t* slot_mask, int shell_mode, double scale, double length, double reject_k, int min_count,
+                     double piv_rel, double apex_rel, double max_apex, int frame_begin, int frame_end, double* shape, double* coef,
+                     double* residual, void* stream);
+
 /* vbs_refine_markers - centre, area, diameter and axes of every tracked marker measured from the grey levels themselves (ours:
  * the reference has no grey-level measurement; table column 3 is the axis of an ellipse fitted to a thresholded contour).
  * Handle-free, opt-in; vbs_track, vbs_track_to_3d and every other output stay what they are.

@@ -940,6 +940,82 @@ def pose_cov(table, ref_disp, ref_xyz, cam, obs_cov, cam_factor=None, ref_rows=N
     return pose, pcov
 
 
+# ---- indentation shape along a recording (k_shape.hip): the quadric of every frame, its apex, depth and curvatures ---------------------
+_SHAPE_WANT = ("shape", "coef", "residual")
+
+
+def _shape_args(n, m, start_frame, mode, scale, length, slots, reject_k, min_count, piv_rel, apex_rel, max_apex, frame_range,
+                ref_disp_shape, ref_xyz_shape, want=_SHAPE_WANT):
+    """`shape_series`'s argument checks (no device needed): what `vbs_shape_series` refuses, in the wrappers' words
+    -> (a, b, shell_mode, min_count, want) or ValueError."""
+    if n < 1 or m < 1:
+        raise ValueError(_TABLE)
+    if mode not in ("plane", "shell"):
+        raise ValueError("mode must be 'plane' or 'shell'")
+    if int(start_frame) != start_frame or not (0 <= int(start_frame) < n):
+        raise ValueError(f"start_frame {start_frame} outside the table's {n} frames")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"scale {scale} is not finite")
+    if not (np.isfinite(float(reject_k)) and float(reject_k) >= 0.0):
+        raise ValueError(f"reject_k {reject_k} must be finite and >= 0 (0 = no rejection)")
+    if tuple(ref_disp_shape) != (m, L.AXIS_COLS) or tuple(ref_xyz_shape) != (m, 3):
+        raise ValueError(f"ref_disp must be [{m}, {L.AXIS_COLS}] and ref_xyz [{m}, 3]: one row per table slot")
+    if not (np.isfinite(float(length)) and float(length) > 0.0):
+        raise ValueError(f"length {length} must be finite and > 0")
+    if int(min_count) != min_count or int(min_count) < 6:
+        raise ValueError("min_count must be an integer >= 6 (a quadric has six coefficients)")
+    for name, v in (("piv_rel", piv_rel), ("apex_rel", apex_rel), ("max_apex", max_apex)):
+        if not (np.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"{name} {v} must be finite and >= 0")
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= m):
+            raise ValueError(f"slots outside the table's {m} slots")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _SHAPE_WANT for w in want):
+        raise ValueError(f"want must name at least one of {_SHAPE_WANT}")
+    a, b = _frame_range(frame_range, n)
+    return a, b, 1 if mode == "shell" else 0, int(min_count), want
+
+
+def shape_series(table, ref_disp, ref_xyz, start_frame=0, mode="plane", scale=1.0, length=None, slots=None, reject_k=0.0,
+                 min_count=9, piv_rel=1e-10, apex_rel=1e-6, max_apex=2.0, frame_range=None, want=_SHAPE_WANT, device=None):
+    """The quadric through the end points of every frame (`vbs_shape_series`): z ~ c0 + a x + b y + (p x x + 2 q x y +
+    r y y) / 2 around the means of the used slots, with the fallback to the plane of the same factorisation and to nothing.  table,
+    ref_disp, ref_xyz, start_frame, mode, scale, slots, reject_k and frame_range as `Engine.pose_series` takes them.  `length`
+    scales x and y inside the fit (default `shapes.default_length(ref_xyz, slots)`, the rms radius of the selected reference
+    positions; the results do not carry it).  Degree 2 needs `min_count` common slots (>= 6) and six pivots above `piv_rel` times
+    their diagonal, degree 1 three; the apex is valid where |K| > `apex_rel` (p^2 + 2 q^2 + r^2) and it lies within `max_apex`
+    lengths of the mean.  The defaults are this project's.  Returns a dict of float64 device tensors for the frames [a, b), with
+    the keys of `want`: `shape` [b-a, 24] = degree, count, n_used, mx, my, mz, c0, a, b, p, q, r, rms_plane, rms, H, K, k1, k2,
+    dir_deg, apex, apex_x, apex_y, apex_z, depth; `coef` [b-a, 2, 4] = (degree, c0, a, b), (degree == 2, p, q, r), a FIR record
+    with n_values 3; `residual` [b-a, m, 2] = (1, r) for every used slot of a frame with a fit, a `field_map_f64` record."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    rd = torch.as_tensor(ref_disp, dtype=torch.float64, device=dev).contiguous()
+    rx = torch.as_tensor(ref_xyz, dtype=torch.float64, device=dev).contiguous()
+    if length is None and tuple(rx.shape) == (m, 3):
+        from .shapes import default_length
+        length = default_length(rx.cpu().numpy(), slots)
+    a, b, shell, mc, want = _shape_args(n, m, start_frame, mode, scale, length, slots, reject_k, min_count, piv_rel, apex_rel, max_apex,
+                                        frame_range, rd.shape, rx.shape, want)
+    shapes = {"shape": (b - a, L.SHAPE_COLS), "coef": (b - a, 2, 4), "residual": (b - a, m, 2)}
+    out = {w: torch.empty(shapes[w], dtype=torch.float64, device=dev) for w in want}
+    if a == b:
+        return out
+    mask = None
+    if slots is not None:
+        mask = torch.zeros((m,), dtype=torch.uint8, device=dev)
+        mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=dev)] = 1
+    _call("vbs_shape_series", "start_frame inside the table, scale and reject_k finite, reject_k >= 0, length > 0, min_count >= 6, "
+          "piv_rel, apex_rel and max_apex finite and >= 0, at least one output",
+          dev, _ptr(t), n, m, int(start_frame), _ptr(rd), _ptr(rx), _ptr(mask), shell, float(scale), float(length), float(reject_k),
+          mc, float(piv_rel), float(apex_rel), float(max_apex), a, b, _ptr(out.get("shape")), _ptr(out.get("coef")),
+          _ptr(out.get("residual")))
+    return out
+
+
 def pixel_noise(table, frame_range=None, device=None):
     """The scatter of the observation over a still segment (`vbs_pixel_noise`): table float32 [n, m, 10] -> float64 [m, 10] = count,
     mean Cx, Cy, major, then uu, uv, ud, vv, vd, dd, the sample covariance (ddof 1) over the tracked rows of the frames [a, b) of

@@ -340,6 +340,25 @@ extern "C" int vbs_pose_cov(int device, const float* table, int n, int m_ref, in
     return launched();
 }
 
+// ---- indentation shape along a recording (k_shape.hip) --------------------------------------------------------------------------
+static inline bool finite_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
+
+extern "C" int vbs_shape_series(int device, const float* table, int n, int m_ref, int start_frame, const double* ref_disp,
+                                const double* ref_xyz, const uint8_t* slot_mask, int shell_mode, double scale, double length,
+                                double reject_k, int min_count, double piv_rel, double apex_rel, double max_apex, int frame_begin,
+                                int frame_end, double* shape, double* coef, double* residual, void* stream) {
+    if (!table || !ref_disp || !ref_xyz || (!shape && !coef && !residual) || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) ||
+        start_frame < 0 || start_frame >= n || !range_ok(frame_begin, frame_end, n) || (shell_mode != 0 && shell_mode != 1) ||
+        !std::isfinite(scale) || !finite_nonneg(reject_k) || !std::isfinite(length) || !(length > 0.0) || min_count < 6 ||
+        !finite_nonneg(piv_rel) || !finite_nonneg(apex_rel) || !finite_nonneg(max_apex))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_shape_series(table, m_ref, start_frame, ref_disp, ref_xyz, slot_mask, shell_mode, scale, length, reject_k, min_count,
+                            piv_rel, apex_rel, max_apex, frame_begin, frame_end, shape, coef, residual, (hipStream_t)stream);
+    return launched();
+}
+
 extern "C" int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out,
                                void* stream) {
     if (!table || !out || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n)) return VBS_EINVAL;

@@ -309,6 +309,10 @@ void launch_pose_cov(const float* table, int m, int start_frame, const double* r
                      int shell, double scale, double reject_k, const vbs_camera& cam, const double* obs, int obs_rows,
                      const double* cam_factor, int q, double min_size, double piv_rel, const float* ref_rows, int frame_begin,
                      int frame_end, double* fix, double* pose, double* pcov, hipStream_t s);
+// k_shape.hip (f24): the quadric through the end points of every frame, its apex and curvatures, the residual per marker
+void launch_shape_series(const float* table, int m, int start_frame, const double* ref_disp, const double* ref_xyz, const u8* slot_mask,
+                         int shell, double scale, double length, double reject_k, int min_count, double piv_rel, double apex_rel,
+                         double max_apex, int frame_begin, int frame_end, double* shape, double* coef, double* residual, hipStream_t s);
 // k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,

@@ -468,6 +468,111 @@ def to_pose_uncertainty_frame(result, frame_offset=0, path=None):
     return df
 
 
+# ---- indentation shape along a recording (k_shape.hip): what the plane leaves behind - the bowl, its apex, depth and curvatures ------
+def _hessian_columns(p, q, r):
+    """H, K, k1, k2, dir_deg of a Hessian (p, q, r), the expressions of `vbs_shape_series` on torch tensors."""
+    H, K = (p + r) / 2.0, p * r - q * q
+    hd = (p - r) / 2.0
+    s = torch.sqrt(hd * hd + q * q)
+    return H, K, H + s, H - s, (0.5 * torch.atan2(2.0 * q, p - r)) * _DEG
+
+
+def shape_analysis(eng: Engine, table: torch.Tensor, table_ref: torch.Tensor, ref_xyz, taps=None, start=0, ref_start=0, ref_end=-1,
+                   mode="plane", scale=1.0, slots=None, reject_k=0.0, min_coverage=0.5, length=None, min_count=9, piv_rel=1e-10,
+                   apex_rel=1e-6, max_apex=2.0, grid=None):
+    """`shape_series` for every frame of a recording, on the inputs of `misalignment_analysis` and with `ref_disp`
+    formed as that function forms it.  Returns a dict: the device tensors `ref_disp` [M, 4], `shape` [N, 24], `coef` [N, 2, 4] and
+    `residual` [N, M, 2]; with `taps` (a full odd-length symmetric FIR) `coef_filtered` [N, 2, 7] (`fir_series_f64` of `coef`: row 0
+    over the frames with a fit, row 1 over those of degree 2) and `trend` [N, 6] = flag (1 where the frame has a filtered Hessian),
+    H, K, k1, k2, dir_deg RECOMPUTED from the filtered p, q, r - curvatures and angles themselves are never filtered; with `grid` =
+    (W [P, M], wsum [P]) of `fields` the `residual_map` [N, P, 2] (`field_map_f64`): what no smooth surface explains, smoothed.  Per
+    recording, on the host: `kind` [N] (`shapes.kind`), `kind_share` (name -> share of the frames), `apex_track` [N, 4] = valid,
+    apex_x, apex_y, apex_z (NaN where not valid) and `deepest_frame`, the frame of largest |depth| among those with an apex
+    (-1: none)."""
+    from . import shapes
+    from .engine import field_map_f64, fir_series_f64, shape_series
+    n_ref = int(table_ref.shape[0])
+    end = int(ref_end) + n_ref if int(ref_end) < 0 else int(ref_end)
+    if not (0 <= end < n_ref):
+        raise ValueError(f"ref_end {ref_end} outside the reference table's {n_ref} frames")
+    ref_disp = eng.axis_displacement(table_ref, ref_start, slots, frame_range=(end, end + 1))[0][0]
+    out = shape_series(table, ref_disp, ref_xyz, start, mode, scale, length, slots, reject_k, min_count, piv_rel, apex_rel, max_apex,
+                       device=eng.device.index)
+    out["ref_disp"] = ref_disp
+    if taps is not None:
+        cf = fir_series_f64(out["coef"], taps, 3, min_coverage, device=eng.device.index)
+        ok = cf[:, 1, 0] == 3.0
+        zero = torch.zeros_like(cf[:, 1, 1])
+        cols = _hessian_columns(cf[:, 1, 1], cf[:, 1, 2], cf[:, 1, 3])
+        out["coef_filtered"] = cf
+        out["trend"] = torch.stack([ok.to(torch.float64)] + [torch.where(ok, c, zero) for c in cols], dim=1)
+    if grid is not None:
+        W, wsum = grid
+        out["residual_map"] = field_map_f64(out["residual"], W, wsum, min_coverage, 1, device=eng.device.index)
+    sh = out["shape"].cpu().numpy()
+    kinds = shapes.kind(sh, apex_rel)
+    valid = sh[:, shapes.APEX] == 1.0
+    out["kind"] = kinds
+    out["kind_share"] = {name: float((kinds == k).mean()) if kinds.size else 0.0 for k, name in enumerate(shapes.KIND_NAMES)}
+    out["apex_track"] = np.concatenate([valid[:, None].astype(np.float64),
+                                        np.where(valid[:, None], sh[:, shapes.APEX_X:shapes.APEX_Z + 1], np.nan)], axis=1)
+    out["deepest_frame"] = int(np.argmax(np.where(valid, np.abs(sh[:, shapes.DEPTH]), -1.0))) if valid.any() else -1
+    return out
+
+
+SHAPE_FRAME_COLUMNS = ("frameno", "kind", "degree", "count", "n_used", "mx", "my", "mz", "c0", "a", "b", "p", "q", "r", "rms_plane",
+                       "rms", "H", "K", "k1", "k2", "dir_deg", "apex", "apex_x", "apex_y", "apex_z", "depth")
+SHAPE_TREND_COLUMNS = ("c0_f", "a_f", "b_f", "p_f", "q_f", "r_f", "H_f", "K_f", "k1_f", "k2_f", "dir_deg_f")
+
+
+def to_shape_frame(result, frame_offset=0, path=None):
+    """The sheet of `shape_analysis`: one row `SHAPE_FRAME_COLUMNS` per frame - `kind` as its name, degree, count, n_used and apex
+    as integers, c0 .. rms_plane empty (NaN) below degree 1, p .. dir_deg below degree 2, the apex and the depth where there is no
+    valid apex - and with a trend also `SHAPE_TREND_COLUMNS` (empty where the filter has no value).  `path`: also written, as .csv
+    or as .xlsx."""
+    import pandas as pd
+    from . import shapes
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    sh = host(result["shape"]).astype(np.float64)
+    if sh.ndim != 2 or sh.shape[1] != L.SHAPE_COLS:
+        raise ValueError(f"shape must be [N, {L.SHAPE_COLS}]")
+    N = sh.shape[0]
+    deg, apex = sh[:, shapes.DEGREE], sh[:, shapes.APEX] == 1.0
+    kinds = np.asarray(result["kind"]) if "kind" in result else shapes.kind(sh)
+    cols = {"frameno": np.arange(N, dtype=np.int64) + int(frame_offset), "kind": [shapes.KIND_NAMES[int(k)] for k in kinds]}
+    for c, name in enumerate(shapes.SHAPE_COLUMNS):
+        if name in ("degree", "count", "n_used", "apex"):
+            cols[name] = sh[:, c].astype(np.int64)
+        elif c <= shapes.MZ:
+            cols[name] = np.where(sh[:, shapes.COUNT] >= 1.0, sh[:, c], np.nan)
+        elif c in (shapes.C0, shapes.A, shapes.B, shapes.RMS_PLANE):
+            cols[name] = np.where(deg >= 1.0, sh[:, c], np.nan)
+        elif c >= shapes.APEX_X:
+            cols[name] = np.where(apex, sh[:, c], np.nan)
+        else:
+            cols[name] = np.where(deg == 2.0, sh[:, c], np.nan)
+    names = list(SHAPE_FRAME_COLUMNS)
+    if "coef_filtered" in result:
+        cf, tr = host(result["coef_filtered"]), host(result["trend"])
+        if cf.shape != (N, 2, 7) or tr.shape != (N, 6):
+            raise ValueError("coef_filtered must be [N, 2, 7] and trend [N, 6]")
+        for k, name in enumerate(("c0_f", "a_f", "b_f")):
+            cols[name] = np.where(cf[:, 0, 0] == 3.0, cf[:, 0, 1 + k], np.nan)
+        for k, name in enumerate(("p_f", "q_f", "r_f")):
+            cols[name] = np.where(cf[:, 1, 0] == 3.0, cf[:, 1, 1 + k], np.nan)
+        for k, name in enumerate(("H_f", "K_f", "k1_f", "k2_f", "dir_deg_f")):
+            cols[name] = np.where(tr[:, 0] == 1.0, tr[:, 1 + k], np.nan)
+        names += list(SHAPE_TREND_COLUMNS)
+    df = pd.DataFrame(cols, columns=names)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- shear, torsion and strain along a recording (k_motion.hip): the affine part of the field, globally and around every marker ----
 def motion_analysis(eng: Engine, table: torch.Tensor, ref_frame=0, slots=None, reject_k=0.0, neighbours=6, radius=None, min_count=4,
                     det_rel=0.01, taps=None, min_coverage=0.5):
