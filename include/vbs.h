@@ -1428,6 +1428,77 @@ int vbs_shape_series(int device, const float* table, int n, int m_ref, int start
                      double piv_rel, double apex_rel, double max_apex, int frame_begin, int frame_end, double* shape, double* coef,
                      double* residual, void* stream);
 
+/* Rigid motion along a recording (ours: the reference ships no code for this): how the markers moved AS A BODY and what is left
+ * once that motion is removed.  Per frame the rotation R, the translation t and optionally the scale s with  P ~ s R Q + t  in the
+ * least-squares sense, Q a point set given once (`source`: a frame of a table, or a layout) and P the frame's 3-D points, by Horn's
+ * closed form: the unit quaternion of R is the eigenvector of the largest eigenvalue of a symmetric 4 x 4 matrix N built from the
+ * nine products sum q p'.  That form always returns a proper rotation (no determinant fix) and is well defined on a planar cloud.
+ * Handle-free; float64 without contraction; + - * / and sqrt only in everything but columns 26 - 31; no atomics, no LDS, no
+ * barrier; every sum over slots follows the rule of vbs_axis_displacement (lane l of 64 adds slots l, l + 64, .. ascending, then
+ * the fold 32, 16, 8, 4, 2, 1).  No result depends on the launch shape, on the frame range or on VBS_RIGID_GROUP (the frames a
+ * workgroup takes, one wave each); tests/helpers/rigid_oracle.py restates every expression bit for bit.  The call allocates nothing.
+ * vbs_rigid_series - table [dev] float32 [n,m_ref,VBS_TABLE_COLS]; source [dev] float64 [m_ref,4] = (flag, X, Y, Z); slot_mask [dev]
+ *   uint8 [m_ref] or NULL (all).  A slot is COMMON in frame f when it is selected, source[r][0] != 0 and its row in f carries
+ *   VBS_FLAG_XYZ; then Q = source[r][1..3] and P = (double) of the row's columns 6 - 8.  Nothing else of a slot is read into a
+ *   value: such cells may hold NaN, 1e30 or 1e300.
+ * THE FIT of a set of slots (the common set; then once its kept slots):
+ *   Sweep 1: count, qm = (sum Q) / count and pm = (sum P) / count per component.  With count < 3 nothing more is summed: no fit.
+ *   Sweep 2: per slot q = Q - qm, p = P - pm per component; the nine sums H_ij = sum q_i p_j (i the SOURCE component, j the frame's:
+ *     Hxy = sum qx py), Sqq = sum ((qx qx + qy qy) + qz qz) and Spp = sum ((px px + py py) + pz pz).
+ *   N, symmetric (the lower triangle mirrors the upper):
+ *     N00 = (Hxx + Hyy) + Hzz   N11 = (Hxx - Hyy) - Hzz   N22 = (Hyy - Hxx) - Hzz   N33 = (Hzz - Hxx) - Hyy
+ *     N01 = Hyz - Hzy   N02 = Hzx - Hxz   N03 = Hxy - Hyx   N12 = Hxy + Hyx   N13 = Hzx + Hxz   N23 = Hyz + Hzy
+ *   Jacobi: T = N, V = I, VBS_RIGID_SWEEPS sweeps of the cyclic method exactly as vbs_modes' Ritz step states it: pairs (p, q), p < q,
+ *     row by row - (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) -; a pair with T[p][q] == 0 is skipped; else
+ *       theta = (T[q][q] - T[p][p]) / (2.0 T[p][q])
+ *       tt = (theta < 0 ? -1.0 : 1.0) / (|theta| + sqrt(theta theta + 1.0))      cs = 1.0 / sqrt(tt tt + 1.0)      sn = tt cs
+ *     then for k = 0 .. 3 the columns  (T[k][p], T[k][q]) <- (cs T[k][p] - sn T[k][q], sn T[k][p] + cs T[k][q])  from the old pair,
+ *     then the rows  (T[p][k], T[q][k]) <- (cs T[p][k] - sn T[q][k], sn T[p][k] + cs T[q][k]),  then V's columns as T's columns,
+ *     then T[p][q] = T[q][p] = 0.  theta theta may overflow to +inf: then tt = +-0, cs = 1, sn = +-0 and the rotation is the
+ *     identity (IEEE, the same on every side).
+ *   Eigenvector: k = the index of the largest T[k][k], the smaller index among equals; d2 = the largest T[i][i] over i != k.  With
+ *     v = V[:, k]:  nn = ((v0 v0 + v1 v1) + v2 v2) + v3 v3,  (w, x, y, z) = v / sqrt(nn)  (each component divided by the root);  all
+ *     four are negated when w < 0, or when w == 0 and the first nonzero of x, y, z is negative.
+ *   Gap: gap = (T[k][k] - d2) / (Sqq + Spp), formed where Sqq + Spp > 0 (else 0).  A fit EXISTS iff count >= 3, Sqq + Spp > 0 and
+ *     gap > gap_rel; otherwise the two sets do not fix a rotation (collinear or coincident points).
+ *   Rotation:  R00 = 1.0 - 2.0 (y y + z z)   R01 = 2.0 (x y - w z)         R02 = 2.0 (x z + w y)
+ *              R10 = 2.0 (x y + w z)         R11 = 1.0 - 2.0 (x x + z z)   R12 = 2.0 (y z - w x)
+ *              R20 = 2.0 (x z - w y)         R21 = 2.0 (y z + w x)         R22 = 1.0 - 2.0 (x x + y y)
+ *   Scale: s = 1.0 exactly unless with_scale is set and Sqq > 0; then s = D / Sqq with D = sum_j sum_i R[j][i] H[i][j] added from
+ *     the left, j outer and i inner:  D = (((R00 Hxx + R01 Hyx) + R02 Hzx) + R10 Hxy) + R11 Hyy ... + R22 Hzz  (= sum (R q) . p).
+ *   Translation: t_i = pm_i - s ((R_i0 qm_x + R_i1 qm_y) + R_i2 qm_z).
+ *   Residual of a slot, explicit and never from a moment identity:  e_i = P_i - (s ((R_i0 Qx + R_i1 Qy) + R_i2 Qz) + t_i).
+ *   Sweep 3: SSR = sum ((ex ex + ey ey) + ez ez) and, over the same slots, SS0 = the same sum of d = P - Q per component.
+ * ONE ROUND OF REJECTION, as vbs_pose_series words it: only when reject_k > 0, a fit exists and SSR > 0.  Kept are the common slots
+ *   with (ex ex + ey ey) + ez ez <= (reject_k reject_k) (SSR / count), e the first fit's residual: a squared comparison, no root
+ *   decides.  If fewer are kept than are common and the kept set, fitted by the same rules, gives a fit, every quantity is the kept
+ *   set's, n_used = kept and flag = 2; otherwise the first fit stands with n_used = count and flag = 1.
+ *   rigid [dev] float64 [fe-fb,VBS_RIGID_COLS] (may be NULL):
+ *     0 flag (0 none, 1 fit, 2 refit on the kept set)   1 count   2 n_used   3-5 qm   6-8 pm   9-12 w, x, y, z   13-21 R row-major
+ *     22-24 t   25 s   26 rms = sqrt(SSR / n_used)   27 rms0 = sqrt(SS0 / n_used)
+ *     28 angle_deg = (2.0 atan2(sqrt((x x + y y) + z z), w)) 57.29577951308232
+ *     29 tilt_deg = atan2(sqrt(R02 R02 + R12 R12), R22) 57.29577951308232: the lean of the rotated normal R (0, 0, 1)
+ *     30 azimuth_deg = atan2(R12, R02) 57.29577951308232: where it leans to
+ *     31 twist_deg = (2.0 atan2(z, w)) 57.29577951308232: the twist about z of the swing-twist split
+ *     32 gap
+ *     At flag 0 the row holds zeros but count, n_used = count, qm and pm where count >= 1, and gap where it was formed.  Columns
+ *     26 - 31 pass through a root or an arc tangent last (held to 4 ulp); every other column is exact.
+ *   coef [dev] float64 [fe-fb,4,4] (may be NULL) = (flag, R row i) for i = 0, 1, 2, then (flag, t): seen as [F, s = 4, cols = 4] with
+ *     n_values = 3 a vbs_fir_series_f64 record as it is (trends are taken from filtered matrices, brought back to rotations on the
+ *     host, never from filtered angles or quaternions).
+ *   residual [dev] float64 [fe-fb,m_ref,4] (may be NULL) = (1, ex, ey, ez) for every used slot of a frame with a fit, zeros
+ *     elsewhere: a record vbs_field_map_f64, vbs_fir_series_f64, vbs_hampel_series_f64, vbs_cross_moments_f64 and the step entries
+ *     take as it is, with n_values = 3.
+ * VBS_EINVAL, before a device is selected and with nothing written: a null table or source, n or m_ref < 1, frames outside
+ *   0 <= frame_begin <= frame_end <= n, with_scale other than 0 / 1, reject_k or gap_rel not finite or < 0, all three outputs NULL.
+ *   frame_begin == frame_end emits nothing. */
+#define VBS_RIGID_COLS   33     /* flag, count, n_used, qm [3], pm [3], quaternion [4], R [9], t [3], s, rms, rms0, 4 angles, gap */
+#define VBS_RIGID_GROUP  4      /* frames a workgroup takes, one wave each (no result depends on it)     */
+#define VBS_RIGID_SWEEPS 8      /* Jacobi sweeps: one more than the 7 after which every host case is diagonal in bits */
+int vbs_rigid_series(int device, const float* table, int n, int m_ref, const double* source, const uint8_t* slot_mask,
+                     int with_scale, double reject_k, double gap_rel, int frame_begin, int frame_end,
+                     double* rigid, double* coef, double* residual, void* stream);
+
 /* vbs_refine_markers - centre, area, diameter and axes of every tracked marker measured from the grey levels themselves (ours:
  * the reference has no grey-level measurement; table column 3 is the axis of an ellipse fitted to a thresholded contour).
  * Handle-free, opt-in; vbs_track, vbs_track_to_3d and every other output stay what they are.

@@ -1016,6 +1016,63 @@ def shape_series(table, ref_disp, ref_xyz, start_frame=0, mode="plane", scale=1.
     return out
 
 
+# ---- rigid motion along a recording (k_rigid.hip): rotation, translation and scale of every frame, the residual per marker ------------
+_RIGID_WANT = ("rigid", "coef", "residual")
+
+
+def _rigid_args(n, m, source_shape, slots, with_scale, reject_k, gap_rel, frame_range, want=_RIGID_WANT):
+    """`rigid_series`'s argument checks (no device needed): what `vbs_rigid_series` refuses, in the order the entry checks, in the
+    wrappers' words -> (a, b, with_scale 0 / 1, want) or ValueError."""
+    if n < 1 or m < 1:
+        raise ValueError(_TABLE)
+    if tuple(source_shape) != (m, 4):
+        raise ValueError(f"source must be [{m}, 4] = (flag, X, Y, Z): one row per table slot")
+    a, b = _frame_range(frame_range, n)
+    if not isinstance(with_scale, (bool, np.bool_)) and with_scale not in (0, 1):
+        raise ValueError("with_scale must be False / True")
+    for name, v in (("reject_k", reject_k), ("gap_rel", gap_rel)):
+        if not (np.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"{name} {v} must be finite and >= 0")
+    if slots is not None:
+        idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= m):
+            raise ValueError(f"slots outside the table's {m} slots")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _RIGID_WANT for w in want):
+        raise ValueError(f"want must name at least one of {_RIGID_WANT}")
+    return a, b, int(bool(with_scale)), want
+
+
+def rigid_series(table, source, slots=None, with_scale=False, reject_k=0.0, gap_rel=1e-6, frame_range=None, want=_RIGID_WANT,
+                 device=None):
+    """How the markers of every frame moved as a body against `source` (`vbs_rigid_series`): the rotation R, the
+    translation t and, with `with_scale`, the scale s of  P ~ s R Q + t  by Horn's quaternion form, and what that motion leaves per
+    marker.  table float32 [n, m, 10]; source float64 [m, 4] = (flag, X, Y, Z), the point set the frames are registered TO
+    (`rigid.source_from_table`, `rigid.source_from_layout`); `slots` selects; `reject_k` > 0 asks for one round of rejection at
+    reject_k times the rms; a fit exists where three or more slots are common and the two largest eigenvalues differ by more than
+    `gap_rel` of Sqq + Spp.  The defaults are this project's.  Returns a dict of float64 device tensors for the frames [a, b), with
+    the keys of `want`: `rigid` [b-a, 33] = flag, count, n_used, qm [3], pm [3], w, x, y, z, R [9] row-major, t [3], s, rms, rms0,
+    angle_deg, tilt_deg, azimuth_deg, twist_deg, gap; `coef` [b-a, 4, 4] = (flag, R row i), (flag, t), a FIR record with n_values
+    3; `residual` [b-a, m, 4] = (1, ex, ey, ez) for every used slot of a frame with a fit, a record with n_values 3."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    src = torch.as_tensor(source, dtype=torch.float64, device=dev).contiguous()
+    a, b, ws, want = _rigid_args(n, m, src.shape, slots, with_scale, reject_k, gap_rel, frame_range, want)
+    shapes = {"rigid": (b - a, L.RIGID_COLS), "coef": (b - a, 4, 4), "residual": (b - a, m, 4)}
+    out = {w: torch.empty(shapes[w], dtype=torch.float64, device=dev) for w in want}
+    if a == b:
+        return out
+    mask = None
+    if slots is not None:
+        mask = torch.zeros((m,), dtype=torch.uint8, device=dev)
+        mask[torch.as_tensor(np.asarray(slots, dtype=np.int64).reshape(-1), device=dev)] = 1
+    _call("vbs_rigid_series", "with_scale 0 / 1, reject_k and gap_rel finite and >= 0, at least one output",
+          dev, _ptr(t), n, m, _ptr(src), _ptr(mask), ws, float(reject_k), float(gap_rel), a, b, _ptr(out.get("rigid")),
+          _ptr(out.get("coef")), _ptr(out.get("residual")))
+    return out
+
+
 def pixel_noise(table, frame_range=None, device=None):
     """The scatter of the observation over a still segment (`vbs_pixel_noise`): table float32 [n, m, 10] -> float64 [m, 10] = count,
     mean Cx, Cy, major, then uu, uv, ud, vv, vd, dd, the sample covariance (ddof 1) over the tracked rows of the frames [a, b) of

@@ -359,6 +359,20 @@ extern "C" int vbs_shape_series(int device, const float* table, int n, int m_ref
     return launched();
 }
 
+// ---- rigid motion along a recording (k_rigid.hip) --------------------------------------------------------------------------------
+extern "C" int vbs_rigid_series(int device, const float* table, int n, int m_ref, const double* source, const uint8_t* slot_mask,
+                                int with_scale, double reject_k, double gap_rel, int frame_begin, int frame_end, double* rigid,
+                                double* coef, double* residual, void* stream) {
+    if (!table || !source || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n) ||
+        (with_scale != 0 && with_scale != 1) || !finite_nonneg(reject_k) || !finite_nonneg(gap_rel) || (!rigid && !coef && !residual))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_rigid_series(table, m_ref, source, slot_mask, with_scale, reject_k, gap_rel, frame_begin, frame_end, rigid, coef,
+                            residual, (hipStream_t)stream);
+    return launched();
+}
+
 extern "C" int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out,
                                void* stream) {
     if (!table || !out || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n)) return VBS_EINVAL;

@@ -573,6 +573,127 @@ def to_shape_frame(result, frame_offset=0, path=None):
     return df
 
 
+# ---- rigid motion along a recording (k_rigid.hip): how the markers moved as a body, and what is left once that is removed -----------
+def rigid_analysis(eng: Engine, table: torch.Tensor, source="start", start_frame=0, layout=None, with_scale=False, reject_k=3.0,
+                   taps=None, grid=None, slots=None, gap_rel=1e-6, min_coverage=0.5, worst=5):
+    """`rigid_series` for every frame of a recording.  `source`: "start" registers every frame against frame
+    `start_frame` of the table itself (`rigid.source_from_table`), "layout" against `layout` [M, 3] (`rigid.source_from_layout`:
+    the sensor's pose against its design), or a ready [M, 4] array.  Returns a dict: the device tensors `rigid` [N, 33], `coef`
+    [N, 4, 4] and `residual` [N, M, 4] and the host array `source` [M, 4]; per frame, on the host (NaN where the frame has no fit):
+    `rotvec` [N, 3] (the axis times the angle in degrees), `tilt_deg`, `azimuth_deg`, `twist_deg`, `shift` [N, 3] = pm - qm (the
+    shift of the centroid), `scale`, `rms`, `share` = 1 - SSR / SS0 (`rigid.rigid_share`) and `kind` (`rigid.kind`, default
+    thresholds); with `taps` (a full odd-length symmetric FIR) `coef_filtered` [N, 4, 7] (`fir_series_f64` of `coef`) and `trend`
+    [N, 8] = flag, angle_deg, tilt_deg, azimuth_deg, twist_deg of the rotation NEAREST to the filtered matrix
+    (`rigid.nearest_rotation`; angles and quaternions themselves are never filtered) and the filtered t; with `grid` = (W [P, M],
+    wsum [P]) of `fields` the `residual_map` [N, P, 2] (`field_map_f64` of the record (flag, |e|)) and, where the grid's positions are
+    given as a third element grid_xy [P, 2], its `residual_patch` [N, 8] (`patch_stats_f64`); `max_tilt_frame` and
+    `max_twist_frame` (-1: no frame has a fit); `slot_rms` [M] (the rms of |e| along the recording, NaN for a slot that was never
+    used) and `worst_slots`, the `worst` slots of largest `slot_rms`, descending."""
+    from . import rigid as RG
+    from .engine import field_map_f64, fir_series_f64, patch_stats_f64, rigid_series
+    if isinstance(source, str):
+        if source == "start":
+            src = RG.source_from_table(table, start_frame)
+        elif source == "layout":
+            if layout is None:
+                raise ValueError("source='layout' needs `layout` [M, 3]")
+            src = RG.source_from_layout(layout)
+        else:
+            raise ValueError("source must be 'start', 'layout' or an [M, 4] array")
+    else:
+        src = np.asarray(source, dtype=np.float64)
+    out = rigid_series(table, src, slots, with_scale, reject_k, gap_rel, device=eng.device.index)
+    out["source"] = src
+    rg = out["rigid"].cpu().numpy()
+    fit = rg[:, RG.FLAG] != 0.0
+    nan = lambda v: np.where(fit.reshape((-1,) + (1,) * (v.ndim - 1)), v, np.nan)                   # noqa: E731
+    v = rg[:, RG.QX:RG.QZ + 1]
+    vn = np.sqrt((v * v).sum(axis=1))
+    out["rotvec"] = nan(np.where(vn[:, None] > 0.0, v / np.where(vn > 0.0, vn, 1.0)[:, None], 0.0) * rg[:, RG.ANGLE_DEG, None])
+    for name, col in (("tilt_deg", RG.TILT_DEG), ("azimuth_deg", RG.AZIMUTH_DEG), ("twist_deg", RG.TWIST_DEG), ("scale", RG.SCALE),
+                      ("rms", RG.RMS)):
+        out[name] = nan(rg[:, col])
+    out["shift"] = nan(rg[:, RG.PMX:RG.PMZ + 1] - rg[:, RG.QMX:RG.QMZ + 1])
+    out["share"] = nan(RG.rigid_share(rg[:, RG.RMS], rg[:, RG.RMS0]))
+    out["kind"] = RG.kind(rg)
+    if taps is not None:
+        cf = fir_series_f64(out["coef"], taps, 3, min_coverage, device=eng.device.index)
+        ch = cf.cpu().numpy()
+        ok = (ch[:, :, 0] == 3.0).all(axis=1)
+        Rf = RG.nearest_rotation(np.where(ok[:, None, None], ch[:, :3, 1:4], np.eye(3)[None]))
+        out["coef_filtered"] = cf
+        out["trend"] = np.concatenate([ok[:, None].astype(np.float64), np.where(ok[:, None], RG.angles(Rf), 0.0),
+                                       np.where(ok[:, None], ch[:, 3, 1:4], 0.0)], axis=1)
+    res = out["residual"]
+    if grid is not None:
+        W, wsum = grid[0], grid[1]
+        mag = torch.sqrt((res[..., 1] * res[..., 1] + res[..., 2] * res[..., 2]) + res[..., 3] * res[..., 3])
+        out["residual_map"] = field_map_f64(torch.stack([res[..., 0], mag], dim=-1), W, wsum, min_coverage, 1, device=eng.device.index)
+        if len(grid) > 2:
+            out["residual_patch"] = patch_stats_f64(out["residual_map"], grid[2], 0, 1.0, 0.0, device=eng.device.index)
+    tilt, twist = np.where(fit, rg[:, RG.TILT_DEG], -1.0), np.where(fit, np.abs(rg[:, RG.TWIST_DEG]), -1.0)
+    out["max_tilt_frame"] = int(np.argmax(tilt)) if fit.any() else -1
+    out["max_twist_frame"] = int(np.argmax(twist)) if fit.any() else -1
+    rh = res.cpu().numpy()
+    used = rh[..., 0].sum(axis=0)
+    ee = (rh[..., 1:] * rh[..., 1:]).sum(axis=2).sum(axis=0)
+    out["slot_rms"] = np.where(used > 0.0, np.sqrt(ee / np.where(used > 0.0, used, 1.0)), np.nan)
+    order = np.argsort(-np.where(used > 0.0, out["slot_rms"], -1.0), kind="stable")
+    out["worst_slots"] = order[:min(int(worst), int((used > 0.0).sum()))].astype(np.int64)
+    return out
+
+
+RIGID_FRAME_COLUMNS = ("frameno", "kind", "flag", "count", "n_used", "shift_x", "shift_y", "shift_z", "rot_x", "rot_y", "rot_z",
+                       "angle_deg", "tilt_deg", "azimuth_deg", "twist_deg", "tx", "ty", "tz", "scale", "rms", "rms0", "share", "gap")
+RIGID_TREND_COLUMNS = ("angle_f", "tilt_f", "azimuth_f", "twist_f", "tx_f", "ty_f", "tz_f")
+
+
+def to_rigid_frame(result, frame_offset=0, path=None):
+    """The sheet of `rigid_analysis`: one row `RIGID_FRAME_COLUMNS` per frame - `kind` as its name, flag, count and n_used as
+    integers, everything from shift_x to share empty (NaN) where the frame has no fit - and with a trend also
+    `RIGID_TREND_COLUMNS` (empty where the filter has no value).  `path`: also written, as .csv or as .xlsx."""
+    import pandas as pd
+    from . import rigid as RG
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    rg = host(result["rigid"]).astype(np.float64)
+    if rg.ndim != 2 or rg.shape[1] != L.RIGID_COLS:
+        raise ValueError(f"rigid must be [N, {L.RIGID_COLS}]")
+    N = rg.shape[0]
+    fit = rg[:, RG.FLAG] != 0.0
+    nan = lambda v: np.where(fit, v, np.nan)                                                        # noqa: E731
+    kinds = np.asarray(result["kind"]) if "kind" in result else RG.kind(rg)
+    v = rg[:, RG.QX:RG.QZ + 1]
+    vn = np.sqrt((v * v).sum(axis=1))
+    rot = np.where(vn[:, None] > 0.0, v / np.where(vn > 0.0, vn, 1.0)[:, None], 0.0) * rg[:, RG.ANGLE_DEG, None]
+    cols = {"frameno": np.arange(N, dtype=np.int64) + int(frame_offset), "kind": [RG.KIND_NAMES[int(k)] for k in kinds],
+            "flag": rg[:, RG.FLAG].astype(np.int64), "count": rg[:, RG.COUNT].astype(np.int64), "n_used": rg[:, RG.N_USED].astype(np.int64)}
+    for k, name in enumerate(("shift_x", "shift_y", "shift_z")):
+        cols[name] = nan(rg[:, RG.PMX + k] - rg[:, RG.QMX + k])
+    for k, name in enumerate(("rot_x", "rot_y", "rot_z")):
+        cols[name] = nan(rot[:, k])
+    for name, c in (("angle_deg", RG.ANGLE_DEG), ("tilt_deg", RG.TILT_DEG), ("azimuth_deg", RG.AZIMUTH_DEG), ("twist_deg", RG.TWIST_DEG),
+                    ("tx", RG.TX), ("ty", RG.TY), ("tz", RG.TZ), ("scale", RG.SCALE), ("rms", RG.RMS), ("rms0", RG.RMS0)):
+        cols[name] = nan(rg[:, c])
+    cols["share"] = nan(RG.rigid_share(rg[:, RG.RMS], rg[:, RG.RMS0]))
+    cols["gap"] = rg[:, RG.GAP]
+    names = list(RIGID_FRAME_COLUMNS)
+    if "trend" in result:
+        tr = host(result["trend"])
+        if tr.shape != (N, 8):
+            raise ValueError("trend must be [N, 8]")
+        for k, name in enumerate(RIGID_TREND_COLUMNS):
+            cols[name] = np.where(tr[:, 0] == 1.0, tr[:, 1 + k], np.nan)
+        names += list(RIGID_TREND_COLUMNS)
+    df = pd.DataFrame(cols, columns=names)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- shear, torsion and strain along a recording (k_motion.hip): the affine part of the field, globally and around every marker ----
 def motion_analysis(eng: Engine, table: torch.Tensor, ref_frame=0, slots=None, reject_k=0.0, neighbours=6, radius=None, min_count=4,
                     det_rel=0.01, taps=None, min_coverage=0.5):
