@@ -544,3 +544,58 @@ extern "C" int vbs_jpeg_encode(const uint8_t* frames, int n, int width, int heig
                        offsets);
     return hipGetLastError() == hipSuccess ? VBS_OK : VBS_EHIP;
 }
+
+#ifdef VBS_DEBUG_KNOBS
+namespace {
+// the word stream of k_jenc_pack (bit 0 = the most significant bit of word 0), one bit at a time into zeroed words
+struct HostSink {
+    uint32_t* words;
+    uint64_t pos;
+    void put(uint32_t code, uint32_t len) {
+        for (uint32_t i = len; i-- > 0; ++pos)
+            if ((code >> i) & 1) words[pos >> 5] |= 0x80000000u >> (pos & 31);
+    }
+};
+}  // namespace
+
+// ONE frame (HOST memory, BGR, rows stride_row bytes apart) through the __host__ __device__ functions the kernels above run -
+// build_tables, block_coefs, dummy_dc, encode_block, scan_byte - with plain loops in place of threads: debug library only, not
+// declared in vbs.h.  `file` has room for file_cap >= the frame bound of vbs_jpeg_encode_workspace; *file_bytes = its length.
+// What this does NOT run, and what therefore rests on the GPU tests alone: PackSink (the words a block shares with its
+// neighbours, atomicOr), the two workgroup scans (k_jenc_scan's bit offsets, block_ff_scan's stuffing offsets), the zeroing of
+// the word stream, and k_jenc_count / k_jenc_write (sizes, offsets, the placement of the stuffed bytes in the payload).
+extern "C" int vbs_dbg_jpeg_encode_emulate(const uint8_t* frame, int width, int height, int64_t stride_row, int quality,
+                                           uint8_t* file, int64_t file_cap, int64_t* file_bytes) {
+    Layout L;
+    if (layout(width, height, 1, &L) != VBS_OK || quality < 1 || quality > 100) return VBS_EINVAL;
+    if (!frame || !file || !file_bytes || stride_row < 3 * (int64_t)width || file_cap < L.g.frame_bound) return VBS_EINVAL;
+    Geom g = L.g;
+    g.sn = 0; g.sr = stride_row;
+    Tables* t = new Tables;
+    uint32_t* mem = new uint32_t[(size_t)g.nblk * 32 + (size_t)g.words]();   // coefficients (dword stores), then the words
+    int16_t* coef = (int16_t*)mem;
+    uint32_t* words = mem + (size_t)g.nblk * 32;
+    build_tables(t, quality, width, height);
+    for (int b = 0; b < g.nblk; ++b) block_coefs(frame, g, t, b, coef + (int64_t)b * 64);
+    for (int mcu = 0; mcu < g.mcux * g.mcuy; ++mcu) dummy_dc(g, coef, mcu);
+    HostSink s{words, 0};
+    for (int b = 0; b < g.nblk; ++b) {
+        const int p = dc_pred_block(b), c = b % 6 >= 4 ? 1 : 0;
+        encode_block(coef + (int64_t)b * 64, p < 0 ? 0 : coef[(int64_t)p * 64], t->dc[c], t->ac[c], s);
+    }
+    const uint32_t tot = (uint32_t)s.pos;
+    const int64_t nbytes = ((int64_t)tot + 7) / 8;
+    int64_t o = 0;
+    for (int i = 0; i < HDR; ++i) file[o++] = t->header[i];
+    for (int64_t j = 0; j < nbytes; ++j) {
+        const uint32_t v = scan_byte(words, j, tot);
+        file[o++] = (uint8_t)v;
+        if (v == 0xFF) file[o++] = 0;
+    }
+    file[o++] = 0xFF; file[o++] = 0xD9;
+    *file_bytes = o;
+    delete[] mem;
+    delete t;
+    return VBS_OK;
+}
+#endif
