@@ -1499,6 +1499,82 @@ int vbs_rigid_series(int device, const float* table, int n, int m_ref, const dou
                      int with_scale, double reject_k, double gap_rel, int frame_begin, int frame_end,
                      double* rigid, double* coef, double* residual, void* stream);
 
+/* Bonnet contact geometry along a recording (ours: the reference ships no code for this): the bonnet is a spherical cap, and a
+ * workpiece cuts it by a plane.  Per frame the sphere the markers lie on - fitted, or GIVEN and held -, the CONTACT (the markers that
+ * lie inside that sphere by more than contact_depth), the plane through the contact markers alone, and from the two the contact
+ * normal, the tool offset, the spot radius and the spot centre.  Handle-free; float64 without contraction; + - * / and sqrt only in
+ * everything but columns 24 and 25; no atomics, no LDS, no barrier; every sum over slots follows the rule of vbs_axis_displacement
+ * (lane l of 64 adds slots l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1).  No result depends on the launch shape, on the
+ * frame range or on VBS_SPHERE_GROUP (the frames a workgroup takes, one wave each); tests/helpers/sphere_oracle.py restates every
+ * expression bit for bit.  The call allocates nothing.
+ * vbs_sphere_series - table [dev] float32 [n,m_ref,VBS_TABLE_COLS]; sphere_in [HOST] double [4] = (Cx, Cy, Cz, R) or NULL (fit per
+ *   frame); fit_mask [dev] uint8 [m_ref] or NULL (all): the slots the sphere is fitted to, or held against; slot_mask [dev] uint8
+ *   [m_ref] or NULL (all): the slots analysed; source [dev] float64 [m_ref,4] = (flag, X, Y, Z) as vbs_rigid_series takes it, or NULL.
+ *   A slot is USED (for the fit, for the analysis) when its mask selects it and its row carries VBS_FLAG_XYZ; then P = (double) of
+ *   the row's columns 6 - 8.  Nothing else of a row is read into a value, and nothing of a source row whose flag is 0: such cells
+ *   may hold NaN, 1e30 or 1e300.  With d = P - C per component, r2 = (dx dx + dy dy) + dz dz and rho = sqrt(r2) - R.
+ * THE FIT of a set of slots (sphere_in == NULL; the used fit_mask slots, then once its kept slots):
+ *   Sweep 1: count and pm = (sum P) / count per component.  With count < 4 nothing more is summed: no sphere.
+ *   Sweep 2: per slot u = P - pm per component and s = (ux ux + uy uy) + uz uz; the 13 sums
+ *     Sx, Sy, Sz of u;  Sxx, Sxy, Sxz, Syy, Syz, Szz of the products u_i u_j;  Ss of s;  Sxs, Sys, Szs of u_i s
+ *   (the first three kept as computed, not taken as zero); with count as a double they are the 14 sums of the normal equations of
+ *   [ux uy uz 1] beta = s in that basis order: N00 = Sxx, N10 = Sxy, N20 = Sxz, N30 = Sx, N11 = Syy, N21 = Syz, N31 = Sy,
+ *   N22 = Szz, N32 = Sz, N33 = count, g = (Sxs, Sys, Szs, Ss).
+ *   LDL' without square roots and without pivoting exactly as vbs_shape_series states it, j = 0 .. 3:
+ *     d_j = N_jj - sum_{k<j} L_jk c_jk;      for i > j:  c_ij = N_ij - sum_{k<j} L_jk c_ik,   L_ij = c_ij / d_j
+ *   every inner sum subtracted from the left with k ascending; pivot j PASSES when d_j > piv_rel N_jj and all four must pass.
+ *   Forward z_i = g_i - sum_{k<i} L_ik z_k, y_i = z_i / d_i; back beta_3 = y_3, beta_i = y_i - sum_{k>i} L_ki beta_k (k ascending).
+ *   c = beta_i / 2.0 (i < 3), kappa = beta_3, C = pm + c per component, R2 = kappa + ((cx cx + cy cy) + cz cz).  A sphere EXISTS iff
+ *   count >= 4, four pivots pass and R2 > 0; then R = sqrt(R2).
+ *   Sweep 3: SSR = sum rho rho.
+ * ONE ROUND OF REJECTION, as vbs_pose_series words it: only when reject_k > 0, a sphere exists and SSR > 0.  Kept are the fit slots
+ *   with rho rho <= (reject_k reject_k) (SSR / count), rho the first sphere's: a squared comparison.  If fewer are kept than were
+ *   fitted and the kept set, fitted by the same rules, gives a sphere, every quantity is the kept set's, n_fit_used = kept and
+ *   rejected = 1; otherwise the first sphere stands with n_fit_used = n_fit and rejected = 0.
+ * THE SPHERE GIVEN (sphere_in != NULL): C and R as they are; a sphere always exists; n_fit = n_fit_used = the used fit_mask slots,
+ *   SSR = sum rho rho over them (it tells whether the held sphere still fits the rim); piv_rel and reject_k are not read.
+ * THE CONTACT, with a sphere: Rc = R - contact_depth.  The contact set is the used slot_mask slots with r2 < Rc Rc, and is empty
+ *   unless Rc > 0: squared, no root decides membership.  n_contact; the centroid cm = (sum P) / n_contact per component; per contact
+ *   slot the depth R - sqrt(r2) (= -rho); depth_sum by the rule, depth_mean = depth_sum / n_contact, depth_max = R - sqrt(r2min),
+ *   r2min the smallest r2 of the set, `deepest` its slot, the smaller slot among equals.
+ *   With n_contact >= 3: q = P - cm per component and the six sums Axx, Axy, Axz, Ayy, Ayz, Azz of q_i q_j; tr = (Axx + Ayy) + Azz.
+ *   With tr > 0: T = the symmetric 3 x 3 of those sums, V = I, VBS_SPHERE_SWEEPS sweeps of the cyclic Jacobi exactly as vbs_modes'
+ *   Ritz step and vbs_rigid_series state it (theta, tt, cs, sn; columns, rows, V's columns, both entries set to 0; a pair with
+ *   T[p][q] == 0 is skipped), pairs (0,1) (0,2) (1,2).  k = the index of the SMALLEST T[k][k], the smaller index among equals;
+ *   lmin = T[k][k], lmid = the smaller of the other two diagonal entries; gap = (lmid - lmin) / tr.  With v = V[:, k]:
+ *   n = v / sqrt((v0 v0 + v1 v1) + v2 v2) (each component divided by the root), dist = (nx (Cx - cmx) + ny (Cy - cmy)) + nz (Cz - cmz);
+ *   where dist < 0 all three components of n and dist are negated: n points from the contact towards the centre of the sphere.
+ *   A plane EXISTS iff n_contact >= 3, tr > 0, gap > gap_rel and dist > 0 (collinear or coincident contact slots fix no plane).
+ * FLAG: 0 no sphere; 1 a sphere and no contact slot; 2 contact without a plane (depths reported, plane columns zero); 3 a plane.
+ *   sphere [dev] float64 [fe-fb,VBS_SPHERE_COLS] (may be NULL), zeros where the flag does not allow a column:
+ *     0 flag   1 n_fit   2 n_fit_used   3 rejected   4-6 C   7 R   8 rms_fit = sqrt(SSR / n_fit_used) (0 where n_fit_used == 0)
+ *     9 n_used (the used slot_mask slots, at every flag)   10 n_contact   11-13 cm   14 depth_sum   15 depth_mean   16 depth_max
+ *     17 deepest (-1 without a contact slot)   18-20 n   21 dist   22 offset = R - dist
+ *     23 spot_radius = sqrt(max(R R - dist dist, 0))
+ *     24 tilt_deg = atan2(sqrt(nx nx + ny ny), nz) 57.29577951308232     25 azimuth_deg = atan2(ny, nx) 57.29577951308232
+ *     26-28 the spot centre C - dist n per component   29 plane_rms = sqrt(max(lmin, 0) / n_contact)
+ *     30 gap (wherever it was formed: n_contact >= 3 and tr > 0)
+ *     Columns 8, 23, 24, 25 and 29 pass through a root or an arc tangent last (held to 4 ulp); every other column is exact.
+ *   radial [dev] float64 [fe-fb,m_ref,2] (may be NULL) = (1, rho) for every used slot_mask slot of a frame with a sphere, zeros
+ *     elsewhere: a record vbs_field_map_f64, vbs_fir_series_f64, vbs_hampel_series_f64 and the step entries take as it is, with
+ *     n_values = 1.
+ *   decomp [dev] float64 [fe-fb,m_ref,4] (may be NULL; needs source) = (1, d_n, d_mer, d_az) for every used slot_mask slot of a frame
+ *     with a sphere whose source flag is != 0 and whose Q = source[r][1..3] is not the centre; zeros elsewhere.  D = P - Q per
+ *     component is resolved in the shell's own frame at Q:  w = Q - C, wn = sqrt((wx wx + wy wy) + wz wz), h = w / wn (the normal);
+ *     h2 = hx hx + hy hy; where h2 == 0 exactly e_az = (0, 1, 0) and e_mer = (1, 0, 0); else hh = sqrt(h2),
+ *     e_az = (-hy / hh, hx / hh, 0) and e_mer = e_az x h = (az_y hz, -(az_x hz), az_x hy - az_y hx).
+ *     d_n = (Dx hx + Dy hy) + Dz hz,  d_mer = (Dx mer_x + Dy mer_y) + Dz mer_z,  d_az = Dx az_x + Dy az_y.  A record with n_values = 3.
+ * VBS_EINVAL, before a device is selected and with nothing written: a null table, n or m_ref < 1, frames outside
+ *   0 <= frame_begin <= frame_end <= n, contact_depth not finite or <= 0, piv_rel, gap_rel or reject_k not finite or < 0, a sphere_in
+ *   with a non-finite entry or R <= 0, decomp without source, all three outputs NULL.  frame_begin == frame_end emits nothing. */
+#define VBS_SPHERE_COLS   31    /* flag, n_fit, n_fit_used, rejected, C [3], R, rms_fit, n_used, n_contact, cm [3], 3 depths, deepest,
+                                   n [3], dist, offset, spot_radius, tilt, azimuth, spot centre [3], plane_rms, gap */
+#define VBS_SPHERE_GROUP  4     /* frames a workgroup takes, one wave each (no result depends on it)     */
+#define VBS_SPHERE_SWEEPS 6     /* Jacobi sweeps: one more than the 5 after which every host case is diagonal in bits */
+int vbs_sphere_series(int device, const float* table, int n, int m_ref, const double* sphere_in, const uint8_t* fit_mask,
+                      const uint8_t* slot_mask, const double* source, double contact_depth, double piv_rel, double gap_rel,
+                      double reject_k, int frame_begin, int frame_end, double* sphere, double* radial, double* decomp, void* stream);
+
 /* vbs_refine_markers - centre, area, diameter and axes of every tracked marker measured from the grey levels themselves (ours:
  * the reference has no grey-level measurement; table column 3 is the axis of an ellipse fitted to a thresholded contour).
  * Handle-free, opt-in; vbs_track, vbs_track_to_3d and every other output stay what they are.

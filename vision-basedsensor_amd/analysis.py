@@ -1073,6 +1073,87 @@ def rigid_series(table, source, slots=None, with_scale=False, reject_k=0.0, gap_
     return out
 
 
+# ---- bonnet contact geometry along a recording (k_sphere.hip): the sphere, the contact set, its plane, the two records ----------------
+_SPHERE_WANT = ("sphere", "radial", "decomp")
+
+
+def _mask_idx(slots, m, name):
+    if slots is None:
+        return None
+    idx = np.asarray(slots, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= m):
+        raise ValueError(f"{name} outside the table's {m} slots")
+    return idx
+
+
+def _sphere_args(n, m, sphere, source_shape, fit_slots, slots, contact_depth, piv_rel, gap_rel, reject_k, frame_range, want=None):
+    """`sphere_series`'s argument checks (no device needed): what `vbs_sphere_series` refuses, in the wrappers' words ->
+    (a, b, sphere as float64 [4] or None, want) or ValueError.  `want` None: `sphere` and `radial`, and `decomp` with a source."""
+    if n < 1 or m < 1:
+        raise ValueError(_TABLE)
+    a, b = _frame_range(frame_range, n)
+    if not (np.isfinite(float(contact_depth)) and float(contact_depth) > 0.0):
+        raise ValueError(f"contact_depth {contact_depth} must be finite and > 0")
+    for name, v in (("piv_rel", piv_rel), ("gap_rel", gap_rel), ("reject_k", reject_k)):
+        if not (np.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"{name} {v} must be finite and >= 0")
+    sph = None
+    if sphere is not None:
+        sph = np.ascontiguousarray(np.asarray(sphere, dtype=np.float64).reshape(-1))
+        if sph.shape != (4,) or not np.isfinite(sph).all() or not sph[3] > 0.0:
+            raise ValueError("sphere must be (Cx, Cy, Cz, R), finite, with R > 0")
+    if source_shape is not None and tuple(source_shape) != (m, 4):
+        raise ValueError(f"source must be [{m}, 4] = (flag, X, Y, Z): one row per table slot")
+    _mask_idx(fit_slots, m, "fit_slots")
+    _mask_idx(slots, m, "slots")
+    if want is None:
+        want = _SPHERE_WANT if source_shape is not None else _SPHERE_WANT[:2]
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _SPHERE_WANT for w in want):
+        raise ValueError(f"want must name at least one of {_SPHERE_WANT}")
+    if "decomp" in want and source_shape is None:
+        raise ValueError("decomp needs `source` [M, 4]: the positions the displacement is taken from")
+    return a, b, sph, want
+
+
+def sphere_series(table, sphere=None, fit_slots=None, slots=None, source=None, contact_depth=0.1, piv_rel=1e-9, gap_rel=1e-3,
+                  reject_k=0.0, frame_range=None, want=None, device=None):
+    """The bonnet's contact geometry of every frame (`vbs_sphere_series`): the sphere the markers lie on - fitted per
+    frame over `fit_slots` when `sphere` is None, else `sphere` = (Cx, Cy, Cz, R) given and HELD (what a loaded recording needs: a
+    per-frame fit over a pressed cap is wrong) -, the contact set (the `slots` that lie inside the sphere by more than
+    `contact_depth`), the plane through those alone and from the two the contact normal, the offset, the spot radius and the spot
+    centre.  table float32 [n, m, 10]; `source` float64 [m, 4] = (flag, X, Y, Z) as `rigid_series` takes it, needed for `decomp`
+    only; `reject_k` > 0 asks for one round of rejection in the per-frame fit; a plane exists where three or more contact slots
+    spread by more than `gap_rel` of their scatter's trace in two directions.  The defaults are this project's.  Returns a dict of
+    float64 device tensors for the frames [a, b), with the keys of `want` (default: `sphere`, `radial`, and `decomp` with a source):
+    `sphere` [b-a, 31] (the columns of `vbs_amd.sphere`), `radial` [b-a, m, 2] = (flag, rho), a record with n_values 1, `decomp`
+    [b-a, m, 4] = (flag, d_n, d_mer, d_az), the displacement from `source` in the shell's own frame, a record with n_values 3."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    src = None if source is None else torch.as_tensor(source, dtype=torch.float64, device=dev).contiguous()
+    a, b, sph, want = _sphere_args(n, m, sphere, None if src is None else src.shape, fit_slots, slots, contact_depth, piv_rel, gap_rel,
+                                   reject_k, frame_range, want)
+    shapes = {"sphere": (b - a, L.SPHERE_COLS), "radial": (b - a, m, 2), "decomp": (b - a, m, 4)}
+    out = {w: torch.empty(shapes[w], dtype=torch.float64, device=dev) for w in want}
+    if a == b:
+        return out
+
+    def mask_of(sl):
+        if sl is None:
+            return None
+        mk = torch.zeros((m,), dtype=torch.uint8, device=dev)
+        mk[torch.as_tensor(np.asarray(sl, dtype=np.int64).reshape(-1), device=dev)] = 1
+        return mk
+    fm, sm = mask_of(fit_slots), mask_of(slots)
+    _call("vbs_sphere_series", "contact_depth > 0, piv_rel, gap_rel and reject_k finite and >= 0, a finite sphere with R > 0, decomp "
+          "only with a source, at least one output",
+          dev, _ptr(t), n, m, _host_ptr(sph) if sph is not None else C.c_void_p(0), _ptr(fm), _ptr(sm), _ptr(src),
+          float(contact_depth), float(piv_rel), float(gap_rel), float(reject_k), a, b, _ptr(out.get("sphere")), _ptr(out.get("radial")),
+          _ptr(out.get("decomp")))
+    return out
+
+
 def pixel_noise(table, frame_range=None, device=None):
     """The scatter of the observation over a still segment (`vbs_pixel_noise`): table float32 [n, m, 10] -> float64 [m, 10] = count,
     mean Cx, Cy, major, then uu, uv, ud, vv, vd, dd, the sample covariance (ddof 1) over the tracked rows of the frames [a, b) of

@@ -373,6 +373,25 @@ extern "C" int vbs_rigid_series(int device, const float* table, int n, int m_ref
     return launched();
 }
 
+// ---- bonnet contact geometry along a recording (k_sphere.hip) ------------------------------------------------------------------------
+extern "C" int vbs_sphere_series(int device, const float* table, int n, int m_ref, const double* sphere_in, const uint8_t* fit_mask,
+                                 const uint8_t* slot_mask, const double* source, double contact_depth, double piv_rel, double gap_rel,
+                                 double reject_k, int frame_begin, int frame_end, double* sphere, double* radial, double* decomp,
+                                 void* stream) {
+    if (!table || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n) ||
+        !(std::isfinite(contact_depth) && contact_depth > 0.0) || !finite_nonneg(piv_rel) || !finite_nonneg(gap_rel) ||
+        !finite_nonneg(reject_k) || (decomp && !source) || (!sphere && !radial && !decomp))
+        return VBS_EINVAL;
+    if (sphere_in && !(std::isfinite(sphere_in[0]) && std::isfinite(sphere_in[1]) && std::isfinite(sphere_in[2]) &&
+                       std::isfinite(sphere_in[3]) && sphere_in[3] > 0.0))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_sphere_series(table, m_ref, sphere_in, fit_mask, slot_mask, source, contact_depth, piv_rel, gap_rel, reject_k,
+                             frame_begin, frame_end, sphere, radial, decomp, (hipStream_t)stream);
+    return launched();
+}
+
 extern "C" int vbs_pixel_noise(int device, const float* table, int n, int m_ref, int frame_begin, int frame_end, double* out,
                                void* stream) {
     if (!table || !out || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) || !range_ok(frame_begin, frame_end, n)) return VBS_EINVAL;

@@ -316,6 +316,10 @@ void launch_shape_series(const float* table, int m, int start_frame, const doubl
 // k_rigid.hip (f25): rotation, translation and scale of every frame against a given point set, the residual per marker
 void launch_rigid_series(const float* table, int m, const double* source, const u8* slot_mask, int with_scale, double reject_k,
                          double gap_rel, int frame_begin, int frame_end, double* rigid, double* coef, double* residual, hipStream_t s);
+// k_sphere.hip (f26): the sphere of the markers (fitted, or `given` [4] read on the host), the contact set, its plane, the records
+void launch_sphere_series(const float* table, int m, const double* given, const u8* fit_mask, const u8* slot_mask, const double* source,
+                          double contact_depth, double piv_rel, double gap_rel, double reject_k, int frame_begin, int frame_end,
+                          double* sphere, double* radial, double* decomp, hipStream_t s);
 // k_pnp.hip (f7): hypotheses + refit of nb PnP problems; one of image / table is null
 void launch_pnp(const double* world, int n, const double* image, const float* table, const u8* valid, int nb, const vbs_camera& cam,
                 const int32_t* samples, int nh, double reproj_px, int32_t* hyp_count, double* hyp_pose, int32_t* status, double* pose,

@@ -694,6 +694,105 @@ def to_rigid_frame(result, frame_offset=0, path=None):
     return df
 
 
+# ---- bonnet contact geometry along a recording (k_sphere.hip): the held sphere, the contact plane, offset, spot and normal ----------
+def bonnet_analysis(eng: Engine, table: torch.Tensor, still=(0, 8), sphere=None, contact_depth=0.1, source="start", fit_slots=None,
+                    taps=None, grid=None, slots=None, piv_rel=1e-9, gap_rel=1e-3, reject_k=3.0, min_coverage=0.5):
+    """`sphere_series` for every frame of a recording of a bonnet pressed against a workpiece.  The camera sits inside
+    the tool, so the unloaded sphere is a constant of the sensor in the table's coordinates: unless `sphere` = (Cx, Cy, Cz, R) is
+    given it is fitted per frame over the UNLOADED frames `still` = (a, b) (over `fit_slots`, one round of rejection at `reject_k`)
+    and combined by `sphere.combine` (refused unless three frames fit); the whole recording then runs against that HELD sphere - a
+    per-frame fit over a pressed cap is wrong by millimetres.  `source`: "start" resolves the displacement against frame still[0] of
+    the table itself (`rigid.source_from_table`), an [M, 4] array against that, None leaves `decomp` out.  Returns a dict: the
+    device tensors `sphere` [N, 31], `radial` [N, M, 2] and, with a source, `decomp` [N, M, 4]; the host arrays `held` [4], `source`
+    and, where the sphere was fitted here, `still` (what `sphere.combine` returns); everything `sphere.summary` reads off the rows
+    (kind, offset, tilt_deg, azimuth_deg, spot_radius, plane_rms, normal, spot_centre, depth_max, first_contact, max_offset_frame,
+    max_tilt_frame, share); with `taps` (a full odd-length symmetric FIR) `trend_filtered` [N, 1, 15] (`fir_series_f64` of
+    `sphere.trend_record`) and `trend` [N, 10] = flag, offset, spot centre, the RENORMALISED filtered normal and the angles
+    recomputed from it (`sphere.trend`; angles are never filtered); with `grid` = (W [P, M], wsum [P]) of `fields` the `depth_map`
+    [N, P, 2] (`field_map_f64` of the record (flag, -rho): how far inside the held sphere the shell lies) and, where the grid's
+    positions are given as a third element grid_xy [P, 2], its `depth_patch` [N, 8] (`patch_stats_f64` at `contact_depth`)."""
+    from . import rigid as RG
+    from . import sphere as SP
+    from .engine import field_map_f64, fir_series_f64, patch_stats_f64, sphere_series
+    dev = eng.device.index
+    a, b = int(still[0]), int(still[1])
+    if isinstance(source, str):
+        if source != "start":
+            raise ValueError("source must be 'start', None or an [M, 4] array")
+        src = RG.source_from_table(table, a)
+    else:
+        src = None if source is None else np.asarray(source, dtype=np.float64)
+    out = {}
+    if sphere is None:
+        fit = sphere_series(table, None, fit_slots, slots, None, contact_depth, piv_rel, gap_rel, reject_k, (a, b), ("sphere",), dev)
+        held = SP.combine(fit["sphere"])
+        if held["frames"] < 3:
+            raise ValueError(f"only {held['frames']} of the still frames [{a}, {b}) give a sphere: three are needed")
+        out["still"] = held
+        sphere = held["sphere"]
+    sphere = np.asarray(sphere, dtype=np.float64).reshape(-1)
+    out.update(sphere_series(table, sphere, fit_slots, slots, src, contact_depth, piv_rel, gap_rel, 0.0, device=dev))
+    out["held"], out["source"] = sphere, src
+    rows = out["sphere"].cpu().numpy()
+    out.update(SP.summary(rows))
+    if taps is not None:
+        out["trend_filtered"] = fir_series_f64(SP.trend_record(rows), taps, 7, min_coverage, device=dev)
+        out["trend"] = SP.trend(out["trend_filtered"])
+    if grid is not None:
+        rad = out["radial"]
+        out["depth_map"] = field_map_f64(torch.stack([rad[..., 0], -rad[..., 1]], dim=-1), grid[0], grid[1], min_coverage, 1, device=dev)
+        if len(grid) > 2:
+            out["depth_patch"] = patch_stats_f64(out["depth_map"], grid[2], 0, 1.0, float(contact_depth), device=dev)
+    return out
+
+
+BONNET_FRAME_COLUMNS = ("frameno", "kind", "flag", "n_used", "n_contact", "deepest", "rms_fit", "depth_mean", "depth_max", "offset",
+                        "spot_radius", "tilt_deg", "azimuth_deg", "nx", "ny", "nz", "spot_x", "spot_y", "spot_z", "plane_rms", "gap")
+BONNET_TREND_COLUMNS = ("offset_f", "spot_x_f", "spot_y_f", "spot_z_f", "nx_f", "ny_f", "nz_f", "tilt_f", "azimuth_f")
+
+
+def to_bonnet_frame(result, frame_offset=0, path=None):
+    """The sheet of `bonnet_analysis`: one row `BONNET_FRAME_COLUMNS` per frame - `kind` as its name, flag, n_used, n_contact and
+    deepest as integers, depth_mean and depth_max empty (NaN) without a contact slot, everything from offset to plane_rms empty
+    without a contact plane - and with a trend also `BONNET_TREND_COLUMNS` (empty where the filter has no value).  `path`: also
+    written, as .csv or as .xlsx."""
+    import pandas as pd
+    from . import sphere as SP
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    r = host(result["sphere"]).astype(np.float64)
+    if r.ndim != 2 or r.shape[1] != L.SPHERE_COLS:
+        raise ValueError(f"sphere must be [N, {L.SPHERE_COLS}]")
+    N = r.shape[0]
+    flat, touch = r[:, SP.FLAG] == 3.0, r[:, SP.FLAG] >= 2.0
+    cols = {"frameno": np.arange(N, dtype=np.int64) + int(frame_offset), "kind": [SP.KIND_NAMES[int(k)] for k in SP.kind(r)]}
+    for name, c in (("flag", SP.FLAG), ("n_used", SP.N_USED), ("n_contact", SP.N_CONTACT), ("deepest", SP.DEEPEST)):
+        cols[name] = r[:, c].astype(np.int64)
+    cols["rms_fit"] = np.where(r[:, SP.FLAG] != 0.0, r[:, SP.RMS_FIT], np.nan)
+    for name, c in (("depth_mean", SP.DEPTH_MEAN), ("depth_max", SP.DEPTH_MAX)):
+        cols[name] = np.where(touch, r[:, c], np.nan)
+    for name, c in (("offset", SP.OFFSET), ("spot_radius", SP.SPOT_RADIUS), ("tilt_deg", SP.TILT_DEG), ("azimuth_deg", SP.AZIMUTH_DEG),
+                    ("nx", SP.NX), ("ny", SP.NY), ("nz", SP.NZ), ("spot_x", SP.SX), ("spot_y", SP.SY), ("spot_z", SP.SZ),
+                    ("plane_rms", SP.PLANE_RMS)):
+        cols[name] = np.where(flat, r[:, c], np.nan)
+    cols["gap"] = r[:, SP.GAP]
+    names = list(BONNET_FRAME_COLUMNS)
+    if "trend" in result:
+        tr = host(result["trend"])
+        if tr.shape != (N, 10):
+            raise ValueError("trend must be [N, 10]")
+        for k, name in enumerate(BONNET_TREND_COLUMNS):
+            cols[name] = np.where(tr[:, 0] == 1.0, tr[:, 1 + k], np.nan)
+        names += list(BONNET_TREND_COLUMNS)
+    df = pd.DataFrame(cols, columns=names)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- shear, torsion and strain along a recording (k_motion.hip): the affine part of the field, globally and around every marker ----
 def motion_analysis(eng: Engine, table: torch.Tensor, ref_frame=0, slots=None, reject_k=0.0, neighbours=6, radius=None, min_count=4,
                     det_rel=0.01, taps=None, min_coverage=0.5):
