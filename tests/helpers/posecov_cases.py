@@ -4,6 +4,7 @@ the entry has to step around planted where a test can name it."""
 import numpy as np
 
 import pose_oracle as PO
+import posecov_oracle as O
 import uncert_cases as UC
 import uncert_oracle as U
 
@@ -122,3 +123,76 @@ def tilted_recording(cam, ref, tilt_deg, azimuth_deg=30.0, pixel_sigma=(0.05, 0.
     t[..., 0] = FLAG_TRACKED + FLAG_XYZ
     s0, s1 = pixel_sigma[0] ** 2, pixel_sigma[1] ** 2
     return t, np.array([s0, 0.0, 0.0, s0, 0.0, s1])
+
+
+# ---- a recording that reaches every exit of the rejection round ---------------------------------------------------------------------
+# what frame f of `exit_recording` does after its first plane, in frame order
+EXIT_FRAMES = ("no round", "refitted", "nothing rejected", "fewer than 3 kept", "kept set degenerate")
+EXIT_RK = 1.0                # a slot is kept where r * r <= SSR / count
+
+
+def second_round_exits(k, reject_k=EXIT_RK):
+    """Which way every frame of the recording k leaves the rejection round, from the restatement alone (`pose_oracle._plane` on
+    the end points of `posecov_oracle.end_points`): one of EXIT_FRAMES per frame."""
+    sel = None if k.get("slots") is None else np.isin(np.arange(k["table"].shape[1]), k["slots"])
+    pose, P, ok, used = O.end_points(k["table"], k["ref_disp"], k["ref_xyz"], k["start"], sel, False, 1.0, reject_k, (0, k["table"].shape[0]))
+    cnt = ok.sum(axis=1)
+    with np.errstate(all="ignore"):
+        exists, _, _, _, ssr, r = PO._plane(P, ok, cnt)
+        keep = ok & (r * r <= ((reject_k * reject_k) * (ssr / cnt.astype(np.float64)))[:, None])
+    kc = keep.sum(axis=1)
+    out = []
+    for f in range(cnt.size):
+        if not (reject_k > 0.0 and exists[f] and ssr[f] > 0.0):
+            name = "no round"
+        elif kc[f] >= cnt[f]:
+            name = "nothing rejected"
+        elif kc[f] < 3:
+            name = "fewer than 3 kept"
+        else:
+            refit = bool(PO._plane(P[f:f + 1], keep[f:f + 1], kc[f:f + 1])[0][0])
+            name = "refitted" if refit else "kept set degenerate"
+        # the restatement's own outputs say the same: only a refit changes flag, n_used and the used set
+        assert (pose[f, 0] == 2.0) == (name == "refitted") and pose[f, 7] == (kc[f] if name == "refitted" else cnt[f]), (f, name)
+        assert np.array_equal(used[f], keep[f] if name == "refitted" else ok[f]) and (pose[f, 0] != 0.0) == bool(exists[f]), (f, name)
+        out.append(name)
+    return out
+
+
+def exit_recording(cam, masked=False, seed=0):
+    """VBS_POSECOV_GROUP + 1 = 5 frames of 7 slots (8 with `masked`: one more slot that a slot mask hides and that would tilt every
+    plane), frame f leaving the rejection round by EXIT_FRAMES[f] at reject_k = EXIT_RK; asserted here from the restatement.
+    The pixel columns are a recording's; X and Y never move, the reference positions are five on the line y = 0 and one on
+    either side of it, and Z is set so that every sum of a frame is exact:
+      0  the start frame: no deviation, SSR = 0, no round
+      1  one slot lifted at the end of the line: it and two more go, four stay and are refitted
+      2  the cross (+-1, 0), (0, +-1) alone at Z = +d, +d, -d, -d: the plane is flat, every r * r equals SSR / 4, all are kept
+      3  that cross and the centre at Z = 0: only the centre is kept
+      4  both slots off the line lifted: they go, and the five that stay lie on the line
+    -> the dict of `recording`, with `slots` (None, or the seven under the mask)."""
+    m, n, d = 8 if masked else 7, len(EXIT_FRAMES), 0.5
+    k = recording(cam, n, m, seed=40 + seed, drop=0.0)
+    pos = np.array([[-2.0, 0.0], [-1.0, 0.0], [0.0, 0.0], [1.0, 0.0], [2.0, 0.0], [0.0, 1.0], [0.0, -1.0]])
+    z = np.zeros((n, 7))
+    z[1, 4] = 8.0
+    z[2, [1, 3]], z[2, [5, 6]] = d, -d
+    z[3] = z[2]
+    z[4, [5, 6]] = 7.0
+    t = k["table"]
+    t[..., 0] = FLAG_TRACKED + FLAG_XYZ
+    t[..., 6:8] = 0.0
+    t[:, :7, 8] = z
+    dead = np.zeros((n, m), dtype=bool)
+    dead[2, [0, 2, 4]] = True
+    dead[3, [0, 4]] = True
+    drop_rows(t, dead, np.random.default_rng(41 + seed))
+    k["ref_disp"] = np.concatenate([np.ones((m, 1)), np.zeros((m, 3))], axis=1)
+    k["ref_xyz"] = np.concatenate([pos, np.full((7, 1), 0.5)], axis=1)
+    k["slots"], k["start"] = None, 0
+    if masked:
+        t[1:, 7, 8] = 40.0
+        k["ref_xyz"] = np.concatenate([k["ref_xyz"], [[3.0, 2.0, 0.5]]], axis=0)
+        k["slots"] = np.arange(7)
+    got = second_round_exits(k)
+    assert got == list(EXIT_FRAMES), got
+    return k

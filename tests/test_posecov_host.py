@@ -115,6 +115,21 @@ def test_doubling_scale_at_reference_positions_zero_scales_sigma_as_the_algebra_
     assert (s1[ok][:, [2, 5, 7]] > 0.0).all()
 
 
+@pytest.mark.parametrize("masked", [False, True])
+def test_the_exit_recording_reaches_every_exit_of_the_rejection_round(masked):
+    """`posecov_cases.exit_recording` asserts, from the restatement alone, that its frame f leaves the round by EXIT_FRAMES[f]: no
+    frame is unnamed and each of the four exits of the second round has its frame (what `tests/test_gpu_posecov.py` then holds the
+    device to).  Every frame has a plane and a covariance, so that a wrong exit shows in `pose` and in `pcov`."""
+    cam = UC.camera((640, 480), distorted=True)
+    k = PC.exit_recording(cam, masked)
+    assert PC.second_round_exits(k) == list(PC.EXIT_FRAMES) and len(set(PC.EXIT_FRAMES)) == k["table"].shape[0] == O.GROUP + 1
+    sel = None if k["slots"] is None else np.isin(np.arange(k["table"].shape[1]), k["slots"])
+    pose, pcov = O.pose_cov(k["table"], k["ref_disp"], k["ref_xyz"], U.Cam(*cam), PC.obs_cov("one", 7), UC.factor(5, 2), k["ref_rows"],
+                            k["start"], sel, False, 1.0, PC.EXIT_RK)
+    assert pose[:, 0].tolist() == [1.0, 2.0, 1.0, 1.0, 1.0] and pose[:, 7].tolist() == [7.0, 4.0, 4.0, 5.0, 7.0]
+    assert ((pcov[:, 0].astype(np.int64) & 1) != 0).all() and (pcov[:, 1] == 0.0).all()
+
+
 def test_the_shim_refuses_what_the_header_refuses_without_a_device():
     from vbs_amd import engine as E, pipeline as PL
     obs, m, n = np.eye(3) * 0.01, 7, 4

@@ -18,6 +18,7 @@ typedef uint8_t u8;
 #define VBS_LAT_MAXN 32            // passes of at most this many frames may take the few-frames labelling kernel (k_stage_lat.hip)
 #define VBS_LAT_HDR 128            // dwords of counters / flags per frame of that kernel
 #define VBS_WINDOWS_PER_LAUNCH 16  // k_window_partial takes its windows as kernel arguments; longer lists are launched in groups
+#define VBS_DEG 57.29577951308232  // degrees per radian as every entry multiplies by it: x * VBS_DEG
 
 struct BranchParams {              // marker_detection.py:117-126,129,170
     int taps_a, taps_b;            // GaussianBlur sizes

@@ -325,7 +325,8 @@ __global__ __launch_bounds__(MODES_THREADS) void k_modes_ritz(const double* __re
     if (tid == 0) {
         for (int k = 0; k < r; ++k)
             for (int l = 0; l < r; ++l) V[k][l] = k == l ? 1.0 : 0.0;
-        // cyclic Jacobi: pairs (p, q), p < q, row by row, VBS_MODES_SWEEPS sweeps; both sides applied to the full matrix
+        // cyclic Jacobi: pairs (p, q), p < q, row by row, VBS_MODES_SWEEPS sweeps; both sides applied to the full matrix.  The
+        // expressions of a pair are those fit_math.h states (jacobi_pair), here on a run-time r x r in LDS by one thread
         for (int sweep = 0; sweep < VBS_MODES_SWEEPS; ++sweep)
             for (int p = 0; p + 1 < r; ++p)
                 for (int qq = p + 1; qq < r; ++qq) {

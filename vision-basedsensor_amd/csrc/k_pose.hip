@@ -98,7 +98,8 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
     float* tile = tiles[wave];
     const bool many = m_ref > POSE_CHUNK;                        // more than one chunk: every sweep stages again
 
-    // the point of a slot, or false: common = staged selection && this frame's row has a 3-D point
+    // the point of a slot, or false: common = staged selection && this frame's row has a 3-D point.  The expressions are those of
+    // fit_math.h's end_point (which k_posecov and k_shape call), here on the staged operands
     auto point = [&](int slot, int cs, const float* row, PosePoint& p) -> bool {
         if (slot >= m_ref || !S.sel[cs] || !((int)row[0] & VBS_FLAG_XYZ)) return false;
         p.dx = ((double)row[6] - (double)S.x0[0][cs]) - S.rd[0][cs];
@@ -230,8 +231,8 @@ __global__ __launch_bounds__(POSE_WAVES * 64) void k_pose(const float* __restric
         double* o = pose + fi * VBS_POSE_COLS;
         const bool any = flag != 0.0;
         o[0] = flag; o[1] = a; o[2] = b; o[3] = cc;
-        o[4] = any ? atan(sqrt(a * a + b * b)) * 57.29577951308232 : 0.0;
-        o[5] = any ? atan2(b, a) * 57.29577951308232 : 0.0;
+        o[4] = any ? atan(sqrt(a * a + b * b)) * VBS_DEG : 0.0;
+        o[5] = any ? atan2(b, a) * VBS_DEG : 0.0;
         o[6] = any ? sqrt(ssr / n_used) : 0.0;
         o[7] = n_used;
     }

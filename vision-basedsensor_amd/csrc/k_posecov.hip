@@ -13,6 +13,7 @@
 // is squared; pixel noise is independent per row and adds in quadrature.  Per column the primal is RECOMPUTED (as k_uncert_total
 // does) instead of keeping 3 q = 48 accumulators next to it: the loop over c stays rolled, no register array is indexed with a
 // runtime value, and the kernel needs no scratch (profiles/posecov_resource_usage.txt).
+#include "fit_math.h"
 #include "uncert_math.h"
 #include "wave_fold.h"
 #pragma clang fp contract(off)
@@ -102,123 +103,86 @@ __global__ __launch_bounds__(PCV_WAVES * 64) void k_posecov(const float* __restr
     const float* frow = table + ((int64_t)frame_begin + fi) * row_step;
     const float* srow = table + (int64_t)start_frame * row_step;
 
-    // the end point of a slot, or false: the common rule and the expressions of k_pose
+    // the end point of a slot, or false: the common rule (fit_math.h)
     auto point = [&](int slot, double* p) -> bool {
-        const double* d = ref_disp + (int64_t)slot * 4;
-        const float* r0 = srow + (int64_t)slot * VBS_TABLE_COLS;
-        const float* r = frow + (int64_t)slot * VBS_TABLE_COLS;
-        if (!((!slot_mask || slot_mask[slot]) && d[0] != 0.0 && ((int)r0[0] & VBS_FLAG_XYZ) && ((int)r[0] & VBS_FLAG_XYZ))) return false;
-        const double* rp = ref_xyz + (int64_t)slot * 3;
-        const double dx = ((double)r[6] - (double)r0[6]) - d[1];
-        const double dy = ((double)r[7] - (double)r0[7]) - d[2];
-        const double dz = ((double)r[8] - (double)r0[8]) - d[3];
-        const double sx = scale * dx, sy = scale * dy, sz = scale * dz;
-        p[0] = rp[0] + sx; p[1] = rp[1] + sy; p[2] = (shell ? rp[2] : 0.0) + sz;
-        return true;
+        return end_point(frow, srow, ref_disp, ref_xyz, slot_mask, shell, scale, slot, p);
     };
 
-    // ---- the plane of vbs_pose_series: means, centred sums, SSR -------------------------------------------------------------------
-    double sp[3] = {0.0, 0.0, 0.0};
+    // ---- the plane of vbs_pose_series and its one round of rejection ------------------------------------------------------------------
+    // A fit is three sweeps - count and means, centred sums, SSR - and the kept set takes the same three through the same code (the
+    // round loop stays rolled).  The plane that stands (a, b, cc, ssr, f) and the first plane (f_*), which decides the kept set in
+    // every later sweep.
+    double a = 0.0, b = 0.0, cc = 0.0, ssr = 0.0, flag = 0.0, thr = 0.0, f_a = 0.0, f_b = 0.0, f_m[3] = {0.0, 0.0, 0.0};
+    PcvPlane f = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int cnt = 0;
-    for (int slot = lane; slot < m; slot += 64) {
-        double p[3];
-        if (!point(slot, p)) continue;
-        ++cnt;
-        sp[0] = sp[0] + p[0]; sp[1] = sp[1] + p[1]; sp[2] = sp[2] + p[2];
-    }
-    cnt = wave_sum(cnt);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sp[k] = wave_sum(sp[k]);
-    const double n0 = (double)cnt;
-    double m1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) m1[k] = cnt > 0 ? sp[k] / n0 : 0.0;
-    double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};                     // xx, xy, yy, xz, yz
-    if (cnt >= 3) {
-        for (int slot = lane; slot < m; slot += 64) {
-            double p[3];
-            if (!point(slot, p)) continue;
-            const double x = p[0] - m1[0], y = p[1] - m1[1], z = p[2] - m1[2];
-            c[0] = c[0] + x * x; c[1] = c[1] + x * y; c[2] = c[2] + y * y; c[3] = c[3] + x * z; c[4] = c[4] + y * z;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) c[k] = wave_sum(c[k]);
-    const double det1 = c[0] * c[2] - c[1] * c[1];
-    const bool plane1 = cnt >= 3 && fabs(det1) > 1e-300;
-    double a = 0.0, b = 0.0, cc = 0.0, ssr = 0.0;
-    if (plane1) {
-        a = (c[3] * c[2] - c[4] * c[1]) / det1; b = (c[4] * c[0] - c[3] * c[1]) / det1;
-        cc = m1[2] - a * m1[0] - b * m1[1];
-        for (int slot = lane; slot < m; slot += 64) {
-            double p[3];
-            if (!point(slot, p)) continue;
-            const double x = p[0] - m1[0], y = p[1] - m1[1], z = p[2] - m1[2];
-            const double r = z - (a * x + b * y);
-            ssr = ssr + r * r;
-        }
-    }
-    ssr = wave_sum(ssr);
-    double flag = plane1 ? 1.0 : 0.0;
-    PcvPlane f = {a, b, m1[0], m1[1], m1[2], c[0], c[1], c[2], det1, n0};
-
-    // ---- one round of rejection; the kept set is decided by the FIRST plane ----------------------------------------------------------
-    const double a1 = a, b1 = b;
-    const double thr = (reject_k * reject_k) * (ssr / n0);
+    bool two = false;
     auto kept = [&](const double* p) -> bool {
-        const double x = p[0] - m1[0], y = p[1] - m1[1], z = p[2] - m1[2];
-        const double r = z - (a1 * x + b1 * y);
+        const double x = p[0] - f_m[0], y = p[1] - f_m[1], z = p[2] - f_m[2];
+        const double r = z - (f_a * x + f_b * y);
         return r * r <= thr;
     };
-    bool two = false;
-    if (reject_k > 0.0 && plane1 && ssr > 0.0) {                  // (the same for every lane of the wave)
-        double kp[3] = {0.0, 0.0, 0.0};
-        int kc = 0;
+#pragma unroll 1
+    for (int round = 0; round < 2; ++round) {                    // 0: the common set, 1: its kept slots (every test below is wave-uniform)
+        const bool second = round == 1;
+        double sp[3] = {0.0, 0.0, 0.0};
+        int c = 0;
         for (int slot = lane; slot < m; slot += 64) {
             double p[3];
-            if (!point(slot, p) || !kept(p)) continue;
-            ++kc;
-            kp[0] = kp[0] + p[0]; kp[1] = kp[1] + p[1]; kp[2] = kp[2] + p[2];
+            if (!point(slot, p) || (second && !kept(p))) continue;
+            ++c;
+            sp[0] = sp[0] + p[0]; sp[1] = sp[1] + p[1]; sp[2] = sp[2] + p[2];
         }
-        kc = wave_sum(kc);
+        c = wave_sum(c);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) kp[k] = wave_sum(kp[k]);
-        if (kc < cnt && kc >= 3) {
-            const double n2 = (double)kc;
-            const double m2[3] = {kp[0] / n2, kp[1] / n2, kp[2] / n2};
-            double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int slot = lane; slot < m; slot += 64) {
-                double p[3];
-                if (!point(slot, p) || !kept(p)) continue;
-                const double x = p[0] - m2[0], y = p[1] - m2[1], z = p[2] - m2[2];
-                e[0] = e[0] + x * x; e[1] = e[1] + x * y; e[2] = e[2] + y * y; e[3] = e[3] + x * z; e[4] = e[4] + y * z;
-            }
-#pragma unroll
-            for (int k = 0; k < 5; ++k) e[k] = wave_sum(e[k]);
-            const double det2 = e[0] * e[2] - e[1] * e[1];
-            if (fabs(det2) > 1e-300) {
-                const double a2 = (e[3] * e[2] - e[4] * e[1]) / det2, b2 = (e[4] * e[0] - e[3] * e[1]) / det2;
-                double ssr2 = 0.0;
-                for (int slot = lane; slot < m; slot += 64) {
-                    double p[3];
-                    if (!point(slot, p) || !kept(p)) continue;
-                    const double x = p[0] - m2[0], y = p[1] - m2[1], z = p[2] - m2[2];
-                    const double r = z - (a2 * x + b2 * y);
-                    ssr2 = ssr2 + r * r;
-                }
-                ssr = wave_sum(ssr2);
-                a = a2; b = b2; cc = m2[2] - a2 * m2[0] - b2 * m2[1];
-                flag = 2.0; two = true;
-                f = {a2, b2, m2[0], m2[1], m2[2], e[0], e[1], e[2], det2, n2};
-            }
+        for (int k = 0; k < 3; ++k) sp[k] = wave_sum(sp[k]);
+        const double n = (double)c;
+        if (!second) {
+            cnt = c;
+            f.n_used = n;                                        // (the `pose` column n_used, with or without a plane)
+        } else if (c >= cnt) {
+            break;                                               // nothing was rejected
         }
+        if (c < 3) break;
+        const double mn[3] = {sp[0] / n, sp[1] / n, sp[2] / n};
+
+        double e[5] = {0.0, 0.0, 0.0, 0.0, 0.0};                 // xx, xy, yy, xz, yz
+        for (int slot = lane; slot < m; slot += 64) {
+            double p[3];
+            if (!point(slot, p) || (second && !kept(p))) continue;
+            const double x = p[0] - mn[0], y = p[1] - mn[1], z = p[2] - mn[2];
+            e[0] = e[0] + x * x; e[1] = e[1] + x * y; e[2] = e[2] + y * y; e[3] = e[3] + x * z; e[4] = e[4] + y * z;
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) e[k] = wave_sum(e[k]);
+        const double det = e[0] * e[2] - e[1] * e[1];
+        if (!(fabs(det) > 1e-300)) break;                        // the set does not fix a plane
+        const double an = (e[3] * e[2] - e[4] * e[1]) / det, bn = (e[4] * e[0] - e[3] * e[1]) / det;
+
+        double s1 = 0.0;
+        for (int slot = lane; slot < m; slot += 64) {
+            double p[3];
+            if (!point(slot, p) || (second && !kept(p))) continue;
+            const double x = p[0] - mn[0], y = p[1] - mn[1], z = p[2] - mn[2];
+            const double r = z - (an * x + bn * y);
+            s1 = s1 + r * r;
+        }
+        s1 = wave_sum(s1);
+        const bool again = !second && reject_k > 0.0 && s1 > 0.0;
+        if (again) {                                             // kept() reads thr and f_*
+            thr = (reject_k * reject_k) * (s1 / n);
+            f_a = an; f_b = bn; f_m[0] = mn[0]; f_m[1] = mn[1]; f_m[2] = mn[2];
+        }
+        a = an; b = bn; cc = mn[2] - an * mn[0] - bn * mn[1]; ssr = s1;
+        f = {an, bn, mn[0], mn[1], mn[2], e[0], e[1], e[2], det, n};
+        flag = second ? 2.0 : 1.0; two = second;
+        if (!again) break;
     }
     const bool plane = flag != 0.0;
     if (pose && lane == 0) {
         double* o = pose + fi * VBS_POSE_COLS;
         o[0] = flag; o[1] = a; o[2] = b; o[3] = cc;
-        o[4] = plane ? atan(sqrt(a * a + b * b)) * 57.29577951308232 : 0.0;
-        o[5] = plane ? atan2(b, a) * 57.29577951308232 : 0.0;
+        o[4] = plane ? atan(sqrt(a * a + b * b)) * VBS_DEG : 0.0;
+        o[5] = plane ? atan2(b, a) * VBS_DEG : 0.0;
         o[6] = plane ? sqrt(ssr / f.n_used) : 0.0;
         o[7] = f.n_used;
     }
@@ -291,7 +255,7 @@ __global__ __launch_bounds__(PCV_WAVES * 64) void k_posecov(const float* __restr
         for (int e = 0; e < 6; ++e) S[e] = so[e] + sc[e];
         const double aa = f.a * f.a, bb = f.b * f.b, ab2 = (2.0 * f.a) * f.b;
         const double rho2 = aa + bb;
-        const double k2 = 57.29577951308232 * 57.29577951308232;
+        const double k2 = VBS_DEG * VBS_DEG;
         if (rho2 > 0.0) {
             angles = true;
             const double w = 1.0 + rho2;

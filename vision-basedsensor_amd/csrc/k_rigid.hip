@@ -8,44 +8,17 @@
 //             frame's result cannot depend on the frames next to it.  A fit is three sweeps - count and means, the nine products
 //             and the two spreads, the residuals - and the kept set of the one round of rejection takes the same three through the
 //             same code (the round loop stays rolled); a last sweep writes the residual record.  The 4 x 4 eigenproblem is
-//             k_modes_ritz's cyclic Jacobi, every lane alike: the six pairs are unrolled over constant indices and the sweep loop
-//             stays rolled, so T and V live in registers (profiles/rigid_resource_usage.txt).
+//             the cyclic Jacobi of fit_math.h, every lane alike: the six pairs are unrolled over constant indices and the sweep
+//             loop stays rolled, so T and V live in registers (profiles/rigid_resource_usage.txt).
 #include "common.h"
+#include "fit_math.h"
 #include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define RGD_WAVES VBS_RIGID_GROUP
-#define RGD_DEG   57.29577951308232
 static_assert(RGD_WAVES >= 1 && RGD_WAVES <= 16, "a workgroup is at most 1024 threads");
 static_assert(VBS_RIGID_COLS == 33, "flag, count, n_used, qm [3], pm [3], w x y z, R [9], t [3], s, rms, rms0, four angles, gap");
 static_assert(VBS_RIGID_SWEEPS >= 1, "at least one sweep");
-
-// one pair of the cyclic Jacobi, k_modes_ritz's expressions: columns, rows, V, then both off-diagonal entries are set to 0.
-// theta * theta may overflow to +inf: then tt = +-0, cs = 1, sn = +-0 and the rotation is the identity.
-template <int P, int Q>
-static __device__ __forceinline__ void rgd_pair(double (&T)[4][4], double (&V)[4][4]) {
-    const double apq = T[P][Q];
-    if (apq == 0.0) return;                                      // (the same for every lane: the sums are broadcast)
-    const double theta = (T[Q][Q] - T[P][P]) / (2.0 * apq);
-    const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double x = T[k][P], y = T[k][Q];
-        T[k][P] = cs * x - sn * y; T[k][Q] = sn * x + cs * y;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double x = T[P][k], y = T[Q][k];
-        T[P][k] = cs * x - sn * y; T[Q][k] = sn * x + cs * y;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double x = V[k][P], y = V[k][Q];
-        V[k][P] = cs * x - sn * y; V[k][Q] = sn * x + cs * y;
-    }
-    T[P][Q] = 0.0; T[Q][P] = 0.0;
-}
 
 // Horn's N from the nine products H [i * 3 + j] = sum q_i p_j, its leading eigenvector as a unit quaternion with w >= 0, and the
 // distance lam - d2 of the two largest eigenvalues.
@@ -61,8 +34,8 @@ static __device__ __forceinline__ double rgd_quaternion(const double* H, double*
         for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
 #pragma unroll 1
     for (int sweep = 0; sweep < VBS_RIGID_SWEEPS; ++sweep) {
-        rgd_pair<0, 1>(T, V); rgd_pair<0, 2>(T, V); rgd_pair<0, 3>(T, V);
-        rgd_pair<1, 2>(T, V); rgd_pair<1, 3>(T, V); rgd_pair<2, 3>(T, V);
+        jacobi_pair<4, 0, 1>(T, V); jacobi_pair<4, 0, 2>(T, V); jacobi_pair<4, 0, 3>(T, V);
+        jacobi_pair<4, 1, 2>(T, V); jacobi_pair<4, 1, 3>(T, V); jacobi_pair<4, 2, 3>(T, V);
     }
     // the largest diagonal entry, the smaller index among equals; then the largest of the other three, likewise
     int k = 0;
@@ -104,10 +77,8 @@ __global__ __launch_bounds__(RGD_WAVES * 64) void k_rigid(const float* __restric
     // the pair (Q, P) of a slot, or false: the common rule
     auto point = [&](int slot, double* q, double* p) -> bool {
         const double* sr = source + (int64_t)slot * 4;
-        const float* r = frow + (int64_t)slot * VBS_TABLE_COLS;
-        if (!((!slot_mask || slot_mask[slot]) && sr[0] != 0.0 && ((int)r[0] & VBS_FLAG_XYZ))) return false;
+        if (!((!slot_mask || slot_mask[slot]) && sr[0] != 0.0 && row_point(frow + (int64_t)slot * VBS_TABLE_COLS, p))) return false;
         q[0] = sr[1]; q[1] = sr[2]; q[2] = sr[3];
-        p[0] = (double)r[6]; p[1] = (double)r[7]; p[2] = (double)r[8];
         return true;
     };
     // e = P - (s R Q + t) and e . e
@@ -253,10 +224,10 @@ __global__ __launch_bounds__(RGD_WAVES * 64) void k_rigid(const float* __restric
         o[25] = s;
         o[26] = flag ? sqrt(ssr / nu) : 0.0;
         o[27] = flag ? sqrt(ss0 / nu) : 0.0;
-        o[28] = flag ? (2.0 * atan2(sqrt((x * x + y * y) + z * z), w)) * RGD_DEG : 0.0;
-        o[29] = flag ? atan2(sqrt(R[2] * R[2] + R[5] * R[5]), R[8]) * RGD_DEG : 0.0;
-        o[30] = flag ? atan2(R[5], R[2]) * RGD_DEG : 0.0;
-        o[31] = flag ? (2.0 * atan2(z, w)) * RGD_DEG : 0.0;
+        o[28] = flag ? (2.0 * atan2(sqrt((x * x + y * y) + z * z), w)) * VBS_DEG : 0.0;
+        o[29] = flag ? atan2(sqrt(R[2] * R[2] + R[5] * R[5]), R[8]) * VBS_DEG : 0.0;
+        o[30] = flag ? atan2(R[5], R[2]) * VBS_DEG : 0.0;
+        o[31] = flag ? (2.0 * atan2(z, w)) * VBS_DEG : 0.0;
         o[32] = gap;
     }
     if (coef) {

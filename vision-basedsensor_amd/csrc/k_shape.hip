@@ -10,6 +10,7 @@
 //             sums in registers and the 6 x 6 factorisation is unrolled over constant indices: no scratch
 //             (profiles/shape_resource_usage.txt).
 #include "common.h"
+#include "fit_math.h"
 #include "wave_fold.h"
 #pragma clang fp contract(off)
 
@@ -18,62 +19,17 @@
 static_assert(SHP_WAVES >= 1 && SHP_WAVES <= 16, "a workgroup is at most 1024 threads");
 static_assert(VBS_SHAPE_COLS == 24, "degree, count, n_used, means [3], c0, a, b, p, q, r, two rms, H, K, k1, k2, dir, apex [4], depth");
 
-// LDL' of the normal matrix in basis order without pivoting, stopped at the first pivot that fails d_k > piv_rel N_kk; returns the
-// number of leading pivots that passed.  gam [3] (from the leading 3 x 3 alone) is written where 3 passed, beta [6] where all 6 did.
+// The 6 x 6 normal equations in basis order (1, u, v, u2, uv, v2) by fit_math.h's LDL'; returns the number of leading pivots that
+// passed.  gam [3] (from the leading 3 x 3 alone) is written where 3 passed, beta [6] where all 6 did.
 static __device__ __forceinline__ int shp_solve(double n, const double* S, double piv_rel, double* beta, double* gam) {
     const double N[6][6] = {{n, S[0], S[1], S[2], S[3], S[4]},      {S[0], S[2], S[3], S[5], S[6], S[7]},
                             {S[1], S[3], S[4], S[6], S[7], S[8]},   {S[2], S[5], S[6], S[9], S[10], S[11]},
                             {S[3], S[6], S[7], S[10], S[11], S[12]}, {S[4], S[7], S[8], S[11], S[12], S[13]}};
-    double Lm[6][6], c[6][6], d[6], z[6], y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        d[i] = 1.0; z[i] = 0.0; y[i] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { Lm[i][j] = 0.0; c[i][j] = 0.0; }
-    }
-    int npass = 0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double dj = N[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) dj = dj - Lm[j][k] * c[j][k];
-        ok = ok && dj > piv_rel * N[j][j];
-        if (ok) {                                                // (the same for every lane: the sums are broadcast)
-            ++npass;
-            d[j] = dj;
-#pragma unroll
-            for (int i = j + 1; i < 6; ++i) {
-                double cij = N[i][j];
-#pragma unroll
-                for (int k = 0; k < j; ++k) cij = cij - Lm[j][k] * c[i][k];
-                c[i][j] = cij; Lm[i][j] = cij / dj;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        if (i < npass) {
-            double zi = S[14 + i];
-#pragma unroll
-            for (int k = 0; k < i; ++k) zi = zi - Lm[i][k] * z[k];
-            z[i] = zi; y[i] = zi / d[i];
-        }
-    }
-    if (npass >= 3) {
-        gam[2] = y[2];
-        gam[1] = y[1] - Lm[2][1] * gam[2];
-        gam[0] = (y[0] - Lm[1][0] * gam[1]) - Lm[2][0] * gam[2];
-    }
-    if (npass == 6) {
-#pragma unroll
-        for (int i = 5; i >= 0; --i) {
-            double b = y[i];
-#pragma unroll
-            for (int k = i + 1; k < 6; ++k) b = b - Lm[k][i] * beta[k];
-            beta[i] = b;
-        }
-    }
+    double Lm[6][6], d[6], y[6];
+    const int npass = ldl_factor(N, piv_rel, Lm, d);
+    ldl_forward(Lm, d, S + 14, npass, y);
+    if (npass >= 3) ldl_back<3>(Lm, y, gam);
+    if (npass == 6) ldl_back<6>(Lm, y, beta);
     return npass;
 }
 
@@ -90,19 +46,9 @@ __global__ __launch_bounds__(SHP_WAVES * 64) void k_shape(const float* __restric
     const float* frow = table + ((int64_t)frame_begin + fi) * row_step;
     const float* srow = table + (int64_t)start_frame * row_step;
 
-    // the end point of a slot, or false: the common rule and the expressions of k_pose
+    // the end point of a slot, or false: the common rule (fit_math.h)
     auto point = [&](int slot, double* p) -> bool {
-        const double* d = ref_disp + (int64_t)slot * 4;
-        const float* r0 = srow + (int64_t)slot * VBS_TABLE_COLS;
-        const float* r = frow + (int64_t)slot * VBS_TABLE_COLS;
-        if (!((!slot_mask || slot_mask[slot]) && d[0] != 0.0 && ((int)r0[0] & VBS_FLAG_XYZ) && ((int)r[0] & VBS_FLAG_XYZ))) return false;
-        const double* rp = ref_xyz + (int64_t)slot * 3;
-        const double dx = ((double)r[6] - (double)r0[6]) - d[1];
-        const double dy = ((double)r[7] - (double)r0[7]) - d[2];
-        const double dz = ((double)r[8] - (double)r0[8]) - d[3];
-        const double sx = scale * dx, sy = scale * dy, sz = scale * dz;
-        p[0] = rp[0] + sx; p[1] = rp[1] + sy; p[2] = (shell ? rp[2] : 0.0) + sz;
-        return true;
+        return end_point(frow, srow, ref_disp, ref_xyz, slot_mask, shell, scale, slot, p);
     };
     // the residual of a point against a fit of `degree` (1: g, 2: b) around the means mn
     auto resid = [&](const double* p, const double* mn, int degree, const double* b, const double* g) -> double {
@@ -229,7 +175,7 @@ __global__ __launch_bounds__(SHP_WAVES * 64) void k_shape(const float* __restric
         const double hd = (p - r) / 2.0;
         const double s = sqrt(hd * hd + q * q);
         k1 = H + s; k2 = H - s;
-        dir = (0.5 * atan2(2.0 * q, p - r)) * 57.29577951308232;
+        dir = (0.5 * atan2(2.0 * q, p - r)) * VBS_DEG;
         rms = sqrt(ssr2 / nu);
         if (fabs(K) > apex_rel * ((p * p + 2.0 * (q * q)) + r * r)) {
             const double xi = (q * b - r * a) / K, eta = (q * a - p * b) / K;

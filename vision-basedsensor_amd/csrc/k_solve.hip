@@ -132,7 +132,7 @@ __global__ __launch_bounds__(64) void k_plane_fit(const float* __restrict__ tabl
             double b = (c[4] * c[0] - c[3] * c[1]) / det;
             double cc = mzv - a * mxv - b * myv;
             o[1] = (float)a; o[2] = (float)b; o[3] = (float)cc;
-            o[4] = (float)(atan(sqrt(a * a + b * b)) * 57.29577951308232);
+            o[4] = (float)(atan(sqrt(a * a + b * b)) * VBS_DEG);
         } else {
             o[1] = o[2] = o[3] = o[4] = 0.f;
         }
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(64) void k_deviation_plane(const float* __restrict_
         if (cnt >= 3 && fabs(det) > 1e-300) {
             const double a = (c[3] * c[2] - c[4] * c[1]) / det, b = (c[4] * c[0] - c[3] * c[1]) / det;
             out[1] = (float)a; out[2] = (float)b; out[3] = (float)(mzv - a * mxv - b * myv);
-            out[4] = (float)(atan(sqrt(a * a + b * b)) * 57.29577951308232);
+            out[4] = (float)(atan(sqrt(a * a + b * b)) * VBS_DEG);
         } else {
             out[1] = out[2] = out[3] = out[4] = 0.f;
         }

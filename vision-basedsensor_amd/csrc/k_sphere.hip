@@ -8,78 +8,26 @@
 //             frame's result cannot depend on the frames next to it.  A fit is three sweeps - count and mean, the 13 sums, the radial
 //             residuals - and the kept set of the one round of rejection takes the same three through the same code (the round loop
 //             stays rolled); two sweeps form the contact set and its scatter, a last one writes the two records.  The 4 x 4 LDL' and
-//             the 3 x 3 Jacobi run in every lane alike over constant indices, so they live in registers
+//             the 3 x 3 Jacobi (fit_math.h) run in every lane alike over constant indices, so they live in registers
 //             (profiles/sphere_resource_usage.txt).
 #include "common.h"
+#include "fit_math.h"
 #include "wave_fold.h"
 #pragma clang fp contract(off)
 
 #define SPH_WAVES VBS_SPHERE_GROUP
-#define SPH_DEG   57.29577951308232
 static_assert(SPH_WAVES >= 1 && SPH_WAVES <= 16, "a workgroup is at most 1024 threads");
 static_assert(VBS_SPHERE_COLS == 31, "flag, n_fit, n_fit_used, rejected, C [3], R, rms_fit, n_used, n_contact, centroid [3], three "
                                      "depths, deepest, n [3], dist, offset, spot radius, two angles, spot centre [3], plane_rms, gap");
 static_assert(VBS_SPHERE_SWEEPS >= 1, "at least one sweep");
 
-// one pair of the cyclic Jacobi, k_modes_ritz's expressions on a 3 x 3: columns, rows, V, then both off-diagonal entries are set to 0
-template <int P, int Q>
-static __device__ __forceinline__ void sph_pair(double (&T)[3][3], double (&V)[3][3]) {
-    const double apq = T[P][Q];
-    if (apq == 0.0) return;                                      // (the same for every lane: the sums are broadcast)
-    const double theta = (T[Q][Q] - T[P][P]) / (2.0 * apq);
-    const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = T[k][P], y = T[k][Q];
-        T[k][P] = cs * x - sn * y; T[k][Q] = sn * x + cs * y;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = T[P][k], y = T[Q][k];
-        T[P][k] = cs * x - sn * y; T[Q][k] = sn * x + cs * y;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = V[k][P], y = V[k][Q];
-        V[k][P] = cs * x - sn * y; V[k][Q] = sn * x + cs * y;
-    }
-    T[P][Q] = 0.0; T[Q][P] = 0.0;
-}
-
-// LDL' of the 4 x 4 normal matrix in basis order (ux, uy, uz, 1) without pivoting, vbs_shape_series's rule: false at the first
-// pivot that does not pass.  beta = (2 cx, 2 cy, 2 cz, kappa).
+// The 4 x 4 normal equations in basis order (ux, uy, uz, 1), all pivots or nothing: false at the first pivot that does not pass.
+// beta = (2 cx, 2 cy, 2 cz, kappa).
 static __device__ __forceinline__ bool sph_solve(const double (&N)[4][4], const double (&g)[4], double piv_rel, double (&beta)[4]) {
-    double Lm[4][4], c[4][4], d[4], z[4], y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        double dj = N[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) dj = dj - Lm[j][k] * c[j][k];
-        if (!(dj > piv_rel * N[j][j])) return false;
-        d[j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < 4; ++i) {
-            double cij = N[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) cij = cij - Lm[j][k] * c[i][k];
-            c[i][j] = cij; Lm[i][j] = cij / dj;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        double zi = g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) zi = zi - Lm[i][k] * z[k];
-        z[i] = zi; y[i] = zi / d[i];
-    }
-#pragma unroll
-    for (int i = 3; i >= 0; --i) {
-        double b = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 4; ++k) b = b - Lm[k][i] * beta[k];
-        beta[i] = b;
-    }
+    double Lm[4][4], d[4], y[4];
+    if (ldl_factor(N, piv_rel, Lm, d) < 4) return false;
+    ldl_forward(Lm, d, g, 4, y);
+    ldl_back<4>(Lm, y, beta);
     return true;
 }
 
@@ -96,10 +44,7 @@ __global__ __launch_bounds__(SPH_WAVES * 64) void k_sphere(const float* __restri
 
     // the point of a slot selected by `mask`, or false: the used rule
     auto point = [&](const u8* mask, int slot, double* p) -> bool {
-        const float* r = frow + (int64_t)slot * VBS_TABLE_COLS;
-        if (!((!mask || mask[slot]) && ((int)r[0] & VBS_FLAG_XYZ))) return false;
-        p[0] = (double)r[6]; p[1] = (double)r[7]; p[2] = (double)r[8];
-        return true;
+        return (!mask || mask[slot]) && row_point(frow + (int64_t)slot * VBS_TABLE_COLS, p);
     };
     // |P - C|^2
     auto dist2 = [](const double* p, const double* c) -> double {
@@ -247,7 +192,7 @@ __global__ __launch_bounds__(SPH_WAVES * 64) void k_sphere(const float* __restri
                 for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
 #pragma unroll 1
             for (int sweep = 0; sweep < VBS_SPHERE_SWEEPS; ++sweep) {
-                sph_pair<0, 1>(T, V); sph_pair<0, 2>(T, V); sph_pair<1, 2>(T, V);
+                jacobi_pair<3, 0, 1>(T, V); jacobi_pair<3, 0, 2>(T, V); jacobi_pair<3, 1, 2>(T, V);
             }
             // the smallest diagonal entry, the smaller index among equals; then the smaller of the other two
             int k = 0;
@@ -333,8 +278,8 @@ __global__ __launch_bounds__(SPH_WAVES * 64) void k_sphere(const float* __restri
     o[21] = dist; o[22] = R - dist;
     const double h2 = R * R - dist * dist;
     o[23] = sqrt(h2 > 0.0 ? h2 : 0.0);
-    o[24] = atan2(sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1]), nrm[2]) * SPH_DEG;
-    o[25] = atan2(nrm[1], nrm[0]) * SPH_DEG;
+    o[24] = atan2(sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1]), nrm[2]) * VBS_DEG;
+    o[25] = atan2(nrm[1], nrm[0]) * VBS_DEG;
     o[26] = C[0] - dist * nrm[0]; o[27] = C[1] - dist * nrm[1]; o[28] = C[2] - dist * nrm[2];
     o[29] = sqrt((lmin > 0.0 ? lmin : 0.0) / ncd);
 }

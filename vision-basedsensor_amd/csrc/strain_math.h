@@ -3,9 +3,8 @@
 #pragma once
 #include <math.h>
 
+#include "common.h"
 #pragma clang fp contract(off)
-
-#define STRAIN_DEG 57.29577951308232
 
 // the centred normal equations of one component: g_x = (xe yy - ye xy) / det, g_y = (ye xx - xe xy) / det
 __device__ __forceinline__ void strain_solve(double xx, double xy, double yy, double xe, double ye, double det, double& gx,
@@ -32,9 +31,9 @@ __device__ __forceinline__ void strain_finite(double gxx, double gxy, double gyx
     const double p = f11 + f22, q = f21 - f12;
     const double a = f11 - f22, b = f12 + f21;
     const double h = sqrt(p * p + q * q), w = sqrt(a * a + b * b);
-    v.shear_deg = 0.5 * atan2(v.e2, v.e1) * STRAIN_DEG;
-    v.rot_deg = atan2(q, p) * STRAIN_DEG;
+    v.shear_deg = 0.5 * atan2(v.e2, v.e1) * VBS_DEG;
+    v.rot_deg = atan2(q, p) * VBS_DEG;
     v.lambda1 = 0.5 * (h + w);
     v.lambda2 = 0.5 * (h - w);
-    v.tilt_deg = atan(sqrt(gzx * gzx + gzy * gzy)) * STRAIN_DEG;
+    v.tilt_deg = atan(sqrt(gzx * gzx + gzy * gzy)) * VBS_DEG;
 }
