@@ -1499,6 +1499,86 @@ int vbs_rigid_series(int device, const float* table, int n, int m_ref, const dou
                      int with_scale, double reject_k, double gap_rel, int frame_begin, int frame_end,
                      double* rigid, double* coef, double* residual, void* stream);
 
+/* Noise-weighted rigid motion along a recording (ours): the maximum-likelihood pose of a frame under the covariance of every 3-D
+ * point, the covariance of that pose, chi^2 and the Mahalanobis distance of every marker.  The model is
+ *     P_i ~ R (Q_i - qm) + c        with        S_i = Sigma_P,i + R Sigma_Q,i R'   (the second term only with source_cov),
+ * qm the source centroid of the start record - a pivot that decorrelates rotation and centre - and no scale (s = 1).  The pose is
+ * started at the one vbs_rigid_series left and improved by a FIXED number of Gauss-Newton steps on x = (omega, dc), the rotation
+ * updated as R <- exp([omega]x) R through the quaternion (1, omega / 2) / |.|: no sine or cosine appears, and the fixed point is
+ * the exponential map's because g = 0 there.  Handle-free; float64 without contraction; + - * / and sqrt only in everything but
+ * columns 31 - 34; no atomics, no LDS, no barrier; every sum over slots follows the rule of vbs_axis_displacement (lane l of 64 adds
+ * slots l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1).  No result depends on the launch shape, on the frame range or on
+ * VBS_RIGID_ML_GROUP (the frames a workgroup takes, one wave each); tests/helpers/rigid_ml_oracle.py restates every expression bit
+ * for bit.  The call allocates nothing.
+ * vbs_rigid_ml_series - table [dev] float32 [n,m_ref,VBS_TABLE_COLS] and source [dev] float64 [m_ref,4] as vbs_rigid_series took
+ *   them.  Per-frame inputs that cover exactly the frames [frame_begin, frame_end), index 0 = frame_begin: cov [dev] float64
+ *   [fe-fb,m_ref,VBS_UNCERT_COV_COLS] as vbs_uncert_cov writes it; rigid [dev] float64 [fe-fb,VBS_RIGID_COLS] and residual [dev]
+ *   float64 [fe-fb,m_ref,4] as vbs_rigid_series wrote them for this table and source.  source_cov [dev] float64
+ *   [m_ref,VBS_UNCERT_COV_COLS] in cov's format, or NULL: an exact source (a layout).  iters in [1, VBS_RIGID_ML_MAX_ITERS].
+ *   A frame HAS A START where rigid[f][0] != 0; of such a row columns 3 - 5 (qm), 9 - 12 (the quaternion q) and 22 - 24 (t) are read
+ *   and nothing else; of a row without a start nothing else is read.  R is formed from q by vbs_rigid_series's nine expressions (so
+ *   the start's R is the record's to the bit) and c_i = ((R_i0 qm_x + R_i1 qm_y) + R_i2 qm_z) + t_i.
+ *   A slot is BEGUN in frame f where residual[f][r][0] != 0 (the set vbs_rigid_series let stand, its rejection included; this
+ *   entry rejects nothing itself) and USED in a sweep where it is begun, cov[f][r][0] != 0, source_cov is NULL or source_cov[r][0]
+ *   != 0, and all three pivots of S pass (below).  Nothing else of a slot that fails one of the flags is read into a value.
+ * THE SWEEP at a pose (q, R, c), per used slot (every 3-term sum is (a + b) + c from the left):
+ *     d = Q - qm per component;   y_i = (R_i0 d_x + R_i1 d_y) + R_i2 d_z;   e_i = P_i - (y_i + c_i),  P the (double) of columns 6 - 8
+ *     S = Sigma_P (xx xy xz yy yz zz);  with source_cov  T_ij = (R_i0 G_0j + R_i1 G_1j) + R_i2 G_2j  (G = Sigma_Q) and, for i <= j,
+ *       S_ij = S_ij + ((T_i0 R_j0 + T_i1 R_j1) + T_i2 R_j2), mirrored
+ *     S = L D L' by vbs_shape_series's LDL' (pivot j passes iff d_j > piv_rel S_jj; d_1 = S11 - L10 c10, ..); W = S^-1 column by
+ *       column: for j = 0, 1, 2 the forward substitution z_0 = b_0, z_1 = b_1 - L10 z_0, z_2 = (b_2 - L20 z_0) - L21 z_1, y_k = z_k
+ *       / d_k of the unit vector b = e_j, then x_2 = y_2, x_1 = y_1 - L21 x_2, x_0 = (y_0 - L10 x_1) - L20 x_2; W_ij = W_ji = x_i for
+ *       i <= j (the upper triangle of the columns is the one kept)
+ *     u_i = (W_i0 e_x + W_i1 e_y) + W_i2 e_z;   dist = (e_x u_x + e_y u_y) + e_z u_z            (the slot's Mahalanobis distance^2)
+ *     M = W B with B = -[y]x, the rotation block of J = [B | I]:
+ *       M_i0 = W_i2 y_y - W_i1 y_z     M_i1 = W_i0 y_z - W_i2 y_x     M_i2 = W_i1 y_x - W_i0 y_y
+ *     N = B' M, upper:  N_0b = M_2b y_y - M_1b y_z  (b = 0, 1, 2)    N_1b = M_0b y_z - M_2b y_x  (b = 1, 2)    N_22 = M_12 y_x - M_02 y_y
+ *     g_0 = u_z y_y - u_y y_z    g_1 = u_x y_z - u_z y_x    g_2 = u_y y_x - u_x y_y    g_3..5 = u
+ *   28 sums over the used slots: N [6], M [9], W [6] (xx xy xz yy yz zz), g [6], chi^2 = sum dist; and two counts, begun and used.
+ *   A, symmetric 6 x 6 over (omega, c):  A[a][b] = N_ab (a <= b < 3),  A[a][3+i] = M_ia,  A[3+i][3+j] = W_ij.
+ * THE ITERATION: sweep k = 0 .. iters.  After a sweep with used >= 3, A = L D L' by the same LDL' at N = 6 with all six pivots
+ *   required.  For k < iters the step follows: x = A^-1 g (forward, then back substitution),
+ *     h = 0.5 omega per component;  hn = sqrt(((1.0 + h_x h_x) + h_y h_y) + h_z h_z);  a = (1.0 / hn, h_x / hn, h_y / hn, h_z / hn)
+ *     q <- a (x) q, Hamilton's product with b = q:   w = ((a_w b_w - a_x b_x) - a_y b_y) - a_z b_z
+ *       x = ((a_w b_x + a_x b_w) + a_y b_z) - a_z b_y    y = ((a_w b_y - a_x b_z) + a_y b_w) + a_z b_x    z = ((a_w b_z + a_x b_y) - a_y b_x) + a_z b_w
+ *     each divided by sqrt(((w w + x x) + y y) + z z), then vbs_rigid_series's sign rule;  R from q;  c <- c + dc per component
+ *     step_rot = the largest of |omega_x|, |omega_y|, |omega_z| and step_c likewise of dc, by comparisons
+ *   For k = iters the sweep was at the final pose: its chi^2, its counts and its A are reported; the covariance is A^-1 column by
+ *   column (unit vector j through the forward and the back substitution), entry (i, j), i <= j, taken from column j.  flag = 2.
+ *   A frame STOPS at flag 1 where a sweep has used < 3 or a pivot of A fails, in any sweep, the last included: the pose is set back
+ *   to the start, ONE more sweep runs there, chi2 = chi2_start = its sum, n_used its count, the steps are 0, the covariance is 0 and
+ *   column 3 holds the steps taken before the stop.
+ *   ml [dev] float64 [fe-fb,VBS_RIGID_ML_COLS] (may be NULL):
+ *     0 flag (0 no start, 1 the start only, 2 the weighted fit)   1 n_start (begun)   2 n_used   3 steps taken   4-7 w, x, y, z
+ *     8-16 R row-major   17-19 t_i = c_i - ((R_i0 qm_x + R_i1 qm_y) + R_i2 qm_z)   20-22 c   23-25 qm   26 chi2   27 dof = 3 n_used - 6
+ *     28 chi2_start: sweep 0's sum, the Horn pose under the same weights   29 step_rot, 30 step_c of the LAST step: what was reached
+ *     31 angle_deg, 32 tilt_deg, 33 azimuth_deg, 34 twist_deg by vbs_rigid_series's four expressions (held to 4 ulp)
+ *     With n = R z = (R02, R12, R22), Sg = the rotation block of the covariance and G the x, y rows of -[n]x (dn = omega x n):
+ *       a_j = n_z Sg_1j - n_y Sg_2j (j = 0, 1, 2)    b_j = n_x Sg_2j - n_z Sg_0j (j = 0, 2)
+ *     35 nxx = a_1 n_z - a_2 n_y   36 nxy = a_2 n_x - a_0 n_z   37 nyy = b_2 n_x - b_0 n_z            (Sigma_n = G Sg G', mm-free, rad^2)
+ *     38 t2_tilt = (n_x n_x) / nxx + (z2 z2) / d2 with l = nxy / nxx, d2 = nyy - l nxy, z2 = n_y - l n_x, where nxx > 0 and d2 >
+ *        piv_rel nyy, else 0: (n_x, n_y) Sigma_n^-1 (n_x, n_y)'.  A tilt is >= 0 and not Gaussian near 0, so t2_tilt decides whether
+ *        a frame is tilted, not tilt / sigma (as vbs_pose_cov argues).
+ *     39 var_twist = (n_x v_x + n_y v_y) + n_z v_z with v_i = (Sg_i0 n_x + Sg_i1 n_y) + Sg_i2 n_z
+ *     Columns 35 - 39 are 0 but at flag 2.  At flag 0 the row holds zeros.
+ *   pcov [dev] float64 [fe-fb,VBS_RIGID_ML_PCOV_COLS] (may be NULL) = flag (1 at ml's flag 2, else 0 and zeros), then the 21 upper
+ *     entries of the covariance of (omega, c) row by row, in rad^2, rad mm and mm^2.  c is the image of qm; the covariance of t, or of
+ *     the image of any other point, follows on the host (rigid.move_centre).
+ *   coef [dev] float64 [fe-fb,4,4] (may be NULL) = (flag, R row i), (flag, t) with ml's flag: vbs_rigid_series's FIR record.
+ *   mahal [dev] float64 [fe-fb,m_ref,3] (may be NULL) = (1, dist at the final pose, dist at the start) for every slot used in the
+ *     last sweep, zeros elsewhere (a slot used at the start only holds zeros); at flag 1 both columns hold the start's.  A record
+ *     vbs_field_map_f64, vbs_fir_series_f64, vbs_hampel_series_f64 and vbs_patch_stats_f64 take as it is, with n_values = 2.
+ * VBS_EINVAL, before a device is selected and with nothing written: a null table, source, cov, rigid or residual, n or m_ref < 1,
+ *   frames outside 0 <= frame_begin <= frame_end <= n, iters outside [1, VBS_RIGID_ML_MAX_ITERS], piv_rel not finite or < 0, all four
+ *   outputs NULL.  frame_begin == frame_end emits nothing. */
+#define VBS_RIGID_ML_COLS      40   /* flag, n_start, n_used, steps, q [4], R [9], t [3], c [3], qm [3], chi2, dof, chi2_start, 2 steps, 4 angles, Sigma_n [3], t2_tilt, var_twist */
+#define VBS_RIGID_ML_PCOV_COLS 22   /* flag, the 21 upper entries of the covariance of (omega, c)            */
+#define VBS_RIGID_ML_GROUP     4    /* frames a workgroup takes, one wave each (no result depends on it)     */
+#define VBS_RIGID_ML_MAX_ITERS 16   /* Gauss-Newton steps a call may ask for                                 */
+int vbs_rigid_ml_series(int device, const float* table, int n, int m_ref, const double* source, const double* cov, const double* rigid,
+                        const double* residual, const double* source_cov, int iters, double piv_rel, int frame_begin, int frame_end,
+                        double* ml, double* pcov, double* coef, double* mahal, void* stream);
+
 /* Bonnet contact geometry along a recording (ours: the reference ships no code for this): the bonnet is a spherical cap, and a
  * workpiece cuts it by a plane.  Per frame the sphere the markers lie on - fitted, or GIVEN and held -, the CONTACT (the markers that
  * lie inside that sphere by more than contact_depth), the plane through the contact markers alone, and from the two the contact

@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libvbs.so")
-SOURCES = ("api.hip", "api_analysis.hip", "k_gray.hip", "k_blur_mfma.hip", "k_blur16.hip", "k_ncc_mfma.hip", "k_ncc_map.hip", "k_ncc_general.hip", "k_morph.hip", "k_label.hip", "k_finalize.hip", "labelling.hip", "k_ccl.hip", "k_stage.hip", "k_stage_lat.hip", "k_solve.hip", "k_undistort.hip", "k_ids.hip", "host_csv.hip", "host_mjpeg.hip", "k_annotate.hip", "k_jpeg_enc.hip", "k_series.hip", "k_filter.hip", "k_steps.hip", "k_pose.hip", "k_field.hip", "k_spectrum.hip", "k_envelope.hip", "k_kinematics.hip", "k_modes.hip", "k_motion.hip", "k_robust.hip", "k_jpeg_huff.hip", "k_diameter.hip", "k_pnp.hip", "k_chess.hip", "k_calib.hip", "k_retrack.hip", "k_uncert.hip", "k_posecov.hip", "k_refine.hip", "k_shape.hip", "k_rigid.hip", "k_sphere.hip")
+SOURCES = ("api.hip", "api_analysis.hip", "k_gray.hip", "k_blur_mfma.hip", "k_blur16.hip", "k_ncc_mfma.hip", "k_ncc_map.hip", "k_ncc_general.hip", "k_morph.hip", "k_label.hip", "k_finalize.hip", "labelling.hip", "k_ccl.hip", "k_stage.hip", "k_stage_lat.hip", "k_solve.hip", "k_undistort.hip", "k_ids.hip", "host_csv.hip", "host_mjpeg.hip", "k_annotate.hip", "k_jpeg_enc.hip", "k_series.hip", "k_filter.hip", "k_steps.hip", "k_pose.hip", "k_field.hip", "k_spectrum.hip", "k_envelope.hip", "k_kinematics.hip", "k_modes.hip", "k_motion.hip", "k_robust.hip", "k_jpeg_huff.hip", "k_diameter.hip", "k_pnp.hip", "k_chess.hip", "k_calib.hip", "k_retrack.hip", "k_uncert.hip", "k_posecov.hip", "k_refine.hip", "k_shape.hip", "k_rigid.hip", "k_sphere.hip", "k_rigid_ml.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # k_ncc_mfma.hip: no SLP pairings (they cost registers, 127 -> 108, and instructions) and no packed float32 instructions at all:

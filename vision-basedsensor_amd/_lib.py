@@ -34,6 +34,7 @@ UNCERT_REF_COLS, UNCERT_WORK_COLS, NOISE_COLS = 55, 61, 10
 POSECOV_COLS, POSECOV_GROUP = 17, 4
 SHAPE_COLS, SHAPE_GROUP = 24, 4
 RIGID_COLS, RIGID_GROUP, RIGID_SWEEPS = 33, 4, 8
+RIGID_ML_COLS, RIGID_ML_PCOV_COLS, RIGID_ML_GROUP, RIGID_ML_MAX_ITERS = 40, 22, 4, 16
 SPHERE_COLS, SPHERE_GROUP, SPHERE_SWEEPS = 31, 4, 6
 REFINE_COLS, REFINE_SUM_COLS, REFINE_MAX_R, REFINE_WAVES = 12, 8, 63, 4
 REFINE_NOT_TRACKED, REFINE_BAD_ROW, REFINE_TOO_LARGE, REFINE_AT_BORDER, REFINE_LOW_CONTRAST, REFINE_DEGENERATE, REFINE_MOVED = 1, 2, 3, 4, 5, 6, 7
@@ -52,7 +53,7 @@ SYMBOLS = ("vbs_create", "vbs_destroy", "vbs_last_error", "vbs_version", "vbs_co
            "vbs_step_lut", "vbs_threshold_bits", "vbs_measure_markers", "vbs_pnp_ransac",
            "vbs_chess_workspace", "vbs_chess_corners", "vbs_corner_subpix", "vbs_calibrate_camera",
            "vbs_retrack_workspace", "vbs_retrack",
-           "vbs_uncert_points", "vbs_uncert_cov", "vbs_uncert_total", "vbs_pixel_noise", "vbs_pose_cov", "vbs_shape_series", "vbs_rigid_series", "vbs_sphere_series", "vbs_refine_markers",
+           "vbs_uncert_points", "vbs_uncert_cov", "vbs_uncert_total", "vbs_pixel_noise", "vbs_pose_cov", "vbs_shape_series", "vbs_rigid_series", "vbs_rigid_ml_series", "vbs_sphere_series", "vbs_refine_markers",
            "vbs_axis_displacement", "vbs_fir_series_f64",
            "vbs_step_response_f64", "vbs_find_steps_f64", "vbs_dwell_stats_f64", "vbs_pose_series",
            "vbs_field_map_f64", "vbs_patch_stats_f64", "vbs_project_series_f64", "vbs_harmonic_fit_f64", "vbs_window_moments_f64", "vbs_window_fit_f64",
@@ -195,6 +196,7 @@ def lib():
                                vp]),
         "vbs_shape_series": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, i32, f64, f64, f64, i32, f64, f64, f64, i32, i32, vp, vp, vp, vp]),
         "vbs_rigid_series": (i32, [i32, vp, i32, i32, vp, vp, i32, f64, f64, i32, i32, vp, vp, vp, vp]),
+        "vbs_rigid_ml_series": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, f64, i32, i32, vp, vp, vp, vp, vp]),
         "vbs_sphere_series": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, f64, f64, f64, f64, i32, i32, vp, vp, vp, vp]),
         "vbs_refine_markers": (i32, [i32, vp, i32, i32, i32, i64, i64, vp, i32, f64, f64, f64, f64, f64, i32, i32, vp, vp, vp, vp]),
     }

@@ -1073,6 +1073,65 @@ def rigid_series(table, source, slots=None, with_scale=False, reject_k=0.0, gap_
     return out
 
 
+# ---- noise-weighted rigid motion (k_rigid_ml.hip): the ML pose from rigid_series's start, its covariance, chi^2, distances ------------
+_RIGID_ML_WANT = ("ml", "pcov", "coef", "mahal")
+
+
+def _rigid_ml_args(n, m, source_shape, cov_shape, rigid_shape, residual_shape, source_cov_shape, iters, piv_rel, frame_range,
+                   want=_RIGID_ML_WANT):
+    """`rigid_ml_series`'s argument checks (no device needed): what `vbs_rigid_ml_series` refuses, in the order the entry checks, and
+    the shapes of the per-frame inputs, in the wrappers' words -> (a, b, iters, want) or ValueError."""
+    if n < 1 or m < 1:
+        raise ValueError(_TABLE)
+    if tuple(source_shape) != (m, 4):
+        raise ValueError(f"source must be [{m}, 4] = (flag, X, Y, Z): one row per table slot")
+    a, b = _frame_range(frame_range, n)
+    for name, shape, expect in (("cov", cov_shape, (b - a, m, L.UNCERT_COV_COLS)), ("rigid", rigid_shape, (b - a, L.RIGID_COLS)),
+                                ("residual", residual_shape, (b - a, m, 4))):
+        if tuple(shape) != expect:
+            raise ValueError(f"{name} must be {list(expect)}: one row per frame of [{a}, {b}), as its entry wrote it for that range")
+    if source_cov_shape is not None and tuple(source_cov_shape) != (m, L.UNCERT_COV_COLS):
+        raise ValueError(f"source_cov must be [{m}, {L.UNCERT_COV_COLS}] = (flag, xx, xy, xz, yy, yz, zz), or None")
+    if isinstance(iters, (bool, np.bool_)) or int(iters) != iters or not (1 <= int(iters) <= L.RIGID_ML_MAX_ITERS):
+        raise ValueError(f"iters {iters} must be an integer in [1, {L.RIGID_ML_MAX_ITERS}]")
+    if not (np.isfinite(float(piv_rel)) and float(piv_rel) >= 0.0):
+        raise ValueError(f"piv_rel {piv_rel} must be finite and >= 0")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _RIGID_ML_WANT for w in want):
+        raise ValueError(f"want must name at least one of {_RIGID_ML_WANT}")
+    return a, b, int(iters), want
+
+
+def rigid_ml_series(table, source, cov, rigid, residual, source_cov=None, iters=8, piv_rel=1e-12, frame_range=None,
+                    want=_RIGID_ML_WANT, device=None):
+    """The noise-weighted rigid motion of every frame (`vbs_rigid_ml_series`): the maximum-likelihood pose of
+    P ~ R (Q - qm) + c  under the covariance of every 3-D point, from the pose `rigid_series` left, by `iters` Gauss-Newton steps;
+    the covariance of that pose; chi^2; the Mahalanobis distance of every marker.  table and source as `rigid_series` took them;
+    `cov` [b-a, m, 7] as `solve3d_cov` writes it, `rigid` [b-a, 33] and `residual` [b-a, m, 4] as `rigid_series(with_scale=False)`
+    wrote them, all three for exactly the frames [a, b) of `frame_range`; `source_cov` [m, 7] in cov's format where the source is
+    itself measured (a frame of a table), None for an exact one (a layout).  Returns a dict of float64 device tensors with the keys
+    of `want`: `ml` [b-a, 40] = flag (0 no start, 1 the start only, 2 the weighted fit), n_start, n_used, steps, w, x, y, z, R [9],
+    t [3], c [3], qm [3], chi2, dof, chi2_start, step_rot, step_c, angle_deg, tilt_deg, azimuth_deg, twist_deg, nxx, nxy, nyy, t2_tilt,
+    var_twist; `pcov` [b-a, 22] = flag, the 21 upper entries of the covariance of (omega, c); `coef` [b-a, 4, 4], the FIR record of
+    `rigid_series` from the weighted pose; `mahal` [b-a, m, 3] = (1, distance^2 at the final pose, at the start), a record with
+    n_values 2.  `rigid.pose_sigma`, `rigid.move_centre` and `rigid.consistent` read them."""
+    dev = _device(device)
+    t = _f32_table(table, dev)
+    n, m, _ = t.shape
+    f64 = lambda x: None if x is None else torch.as_tensor(x, dtype=torch.float64, device=dev).contiguous()   # noqa: E731
+    src, cv, rg, rs, sc = f64(source), f64(cov), f64(rigid), f64(residual), f64(source_cov)
+    a, b, iters, want = _rigid_ml_args(n, m, src.shape, cv.shape, rg.shape, rs.shape, None if sc is None else sc.shape, iters, piv_rel,
+                                       frame_range, want)
+    shapes = {"ml": (b - a, L.RIGID_ML_COLS), "pcov": (b - a, L.RIGID_ML_PCOV_COLS), "coef": (b - a, 4, 4), "mahal": (b - a, m, 3)}
+    out = {w: torch.empty(shapes[w], dtype=torch.float64, device=dev) for w in want}
+    if a == b:
+        return out
+    _call("vbs_rigid_ml_series", "iters in [1, 16], piv_rel finite and >= 0, at least one output",
+          dev, _ptr(t), n, m, _ptr(src), _ptr(cv), _ptr(rg), _ptr(rs), _ptr(sc), iters, float(piv_rel), a, b, _ptr(out.get("ml")),
+          _ptr(out.get("pcov")), _ptr(out.get("coef")), _ptr(out.get("mahal")))
+    return out
+
+
 # ---- bonnet contact geometry along a recording (k_sphere.hip): the sphere, the contact set, its plane, the two records ----------------
 _SPHERE_WANT = ("sphere", "radial", "decomp")
 

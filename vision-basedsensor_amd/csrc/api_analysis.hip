@@ -373,6 +373,22 @@ extern "C" int vbs_rigid_series(int device, const float* table, int n, int m_ref
     return launched();
 }
 
+// ---- noise-weighted rigid motion along a recording (k_rigid_ml.hip) -----------------------------------------------------------------
+extern "C" int vbs_rigid_ml_series(int device, const float* table, int n, int m_ref, const double* source, const double* cov,
+                                   const double* rigid, const double* residual, const double* source_cov, int iters, double piv_rel,
+                                   int frame_begin, int frame_end, double* ml, double* pcov, double* coef, double* mahal,
+                                   void* stream) {
+    if (!table || !source || !cov || !rigid || !residual || n < 1 || m_ref < 1 || !slots_fit_grid(m_ref) ||
+        !range_ok(frame_begin, frame_end, n) || iters < 1 || iters > VBS_RIGID_ML_MAX_ITERS || !finite_nonneg(piv_rel) ||
+        (!ml && !pcov && !coef && !mahal))
+        return VBS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return VBS_EHIP;
+    if (frame_end > frame_begin)
+        launch_rigid_ml_series(table, m_ref, source, cov, rigid, residual, source_cov, iters, piv_rel, frame_begin, frame_end, ml,
+                               pcov, coef, mahal, (hipStream_t)stream);
+    return launched();
+}
+
 // ---- bonnet contact geometry along a recording (k_sphere.hip) ------------------------------------------------------------------------
 extern "C" int vbs_sphere_series(int device, const float* table, int n, int m_ref, const double* sphere_in, const uint8_t* fit_mask,
                                  const uint8_t* slot_mask, const double* source, double contact_depth, double piv_rel, double gap_rel,

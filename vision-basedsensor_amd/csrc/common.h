@@ -317,6 +317,10 @@ void launch_shape_series(const float* table, int m, int start_frame, const doubl
 // k_rigid.hip (f25): rotation, translation and scale of every frame against a given point set, the residual per marker
 void launch_rigid_series(const float* table, int m, const double* source, const u8* slot_mask, int with_scale, double reject_k,
                          double gap_rel, int frame_begin, int frame_end, double* rigid, double* coef, double* residual, hipStream_t s);
+// k_rigid_ml.hip (f27): the noise-weighted pose from the start vbs_rigid_series left, its covariance, chi^2, the distance per marker
+void launch_rigid_ml_series(const float* table, int m, const double* source, const double* cov, const double* start,
+                            const double* residual, const double* source_cov, int iters, double piv_rel, int frame_begin,
+                            int frame_end, double* ml, double* pcov, double* coef, double* mahal, hipStream_t s);
 // k_sphere.hip (f26): the sphere of the markers (fitted, or `given` [4] read on the host), the contact set, its plane, the records
 void launch_sphere_series(const float* table, int m, const double* given, const u8* fit_mask, const u8* slot_mask, const double* source,
                           double contact_depth, double piv_rel, double gap_rel, double reject_k, int frame_begin, int frame_end,

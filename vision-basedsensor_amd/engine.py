@@ -17,11 +17,11 @@ from .analysis import (KIN_PIV_REL, covariance_f64, cross_moments_f64, dwell_sta
                        fir_series_f64, hampel_series_f64, harmonic_fit_f64, kin_thresholds, leading_modes_f64, local_strain_f64,
                        mode_scores_f64, motion_series_f64, n_kin_sums, patch_stats_f64, poly_fit_f64, poly_moments_f64,
                        project_series_f64, step_response_f64, taps_sum, window_fit_f64, window_moments_f64)
-from .analysis import pixel_noise, pose_cov, rigid_series, shape_series, solve3d_cov, solve3d_jacobian, sphere_series  # noqa: F401
+from .analysis import pixel_noise, pose_cov, rigid_ml_series, rigid_series, shape_series, solve3d_cov, solve3d_jacobian, sphere_series  # noqa: F401
 # the wrappers' argument checkers, under the names the host tests have held them to since before they moved
 from .analysis import (_covariance_args, _envelope_args, _envelope_fit_args, _field_args, _fit_args, _kin_args,  # noqa: F401
                        _kin_fit_args, _lstrain_args, _modes_args, _moments_args, _motion_args, _patch_args, _project_args,
-                       _posecov_args, _rigid_args, _robust_args, _scores_args, _shape_args, _sphere_args, _uncert_args)
+                       _posecov_args, _rigid_args, _rigid_ml_args, _robust_args, _scores_args, _shape_args, _sphere_args, _uncert_args)
 
 
 class Engine:

@@ -694,6 +694,157 @@ def to_rigid_frame(result, frame_offset=0, path=None):
     return df
 
 
+# ---- noise-weighted rigid motion (k_rigid_ml.hip): the pose under the noise of every point, its covariance, chi^2, the distances ------
+def _rigid_uncertainty_args(n, source, reject_k, iters, k, worst):
+    """`rigid_uncertainty`'s own argument checks (no device needed), reject_k and iters included so that nothing it can refuse by
+    value waits for the device; the entries' shape checks are `engine._rigid_args` and `engine._rigid_ml_args`.  -> (source frame or
+    None, k, worst)."""
+    frame = None
+    if isinstance(source, str):
+        if source not in ("start", "layout"):
+            raise ValueError("source must be 'start', 'layout' or a frame of the table")
+        frame = 0 if source == "start" else None
+    else:
+        if isinstance(source, (bool, np.bool_)) or int(source) != source or not (0 <= int(source) < n):
+            raise ValueError(f"source frame {source} outside the table's {n} frames")
+        frame = int(source)
+    if not (np.isfinite(float(reject_k)) and float(reject_k) >= 0.0):
+        raise ValueError(f"reject_k {reject_k} must be finite and >= 0")
+    if isinstance(iters, (bool, np.bool_)) or int(iters) != iters or not (1 <= int(iters) <= L.RIGID_ML_MAX_ITERS):
+        raise ValueError(f"iters {iters} must be an integer in [1, {L.RIGID_ML_MAX_ITERS}]")
+    if not (np.isfinite(float(k)) and float(k) > 0.0):
+        raise ValueError("k must be finite and > 0")
+    if int(worst) != worst or int(worst) < 0:
+        raise ValueError("worst must be an integer >= 0")
+    return frame, float(k), int(worst)
+
+
+def rigid_uncertainty_columns(ml, pc, mh, kk=3.0, worst=5):
+    """The per-frame columns `rigid_uncertainty` derives from the host copies of `ml` [N, 40], `pcov` [N, 22] and `mahal` [N, M, 3]
+    (no device needed) -> a dict: tilt_deg, azimuth_deg, twist_deg, t2_tilt, centre, sigma_rot_deg, sigma_centre, significant,
+    twist_z, chi2_dof, tilt_limit_deg, consistent, worst_frames, slot_mahal, worst_slots (NaN where the frame has no weighted fit)."""
+    from . import rigid as RG
+    ml, pc, mh = np.asarray(ml, dtype=np.float64), np.asarray(pc, dtype=np.float64), np.asarray(mh, dtype=np.float64)
+    out = {}
+    fit = ml[:, RG.ML_FLAG] == 2.0
+    nan = lambda v: np.where(fit.reshape((-1,) + (1,) * (v.ndim - 1)), v, np.nan)                   # noqa: E731
+    for name, col in (("tilt_deg", RG.ML_TILT_DEG), ("azimuth_deg", RG.ML_AZIMUTH_DEG), ("twist_deg", RG.ML_TWIST_DEG),
+                      ("t2_tilt", RG.ML_T2_TILT)):
+        out[name] = nan(ml[:, col])
+    out["centre"] = nan(ml[:, RG.ML_CX:RG.ML_CX + 3])
+    out["sigma_rot_deg"], out["sigma_centre"] = RG.pose_sigma(ml, pc)
+    with np.errstate(all="ignore"):
+        out["significant"] = fit & (ml[:, RG.ML_T2_TILT] > kk * kk)
+        out["twist_z"] = nan(ml[:, RG.ML_TWIST_DEG] / (np.sqrt(ml[:, RG.ML_VAR_TWIST]) * _DEG))
+        out["chi2_dof"] = np.where(fit & (ml[:, RG.ML_DOF] >= 1.0), ml[:, RG.ML_CHI2] / np.where(ml[:, RG.ML_DOF] >= 1.0, ml[:, RG.ML_DOF], 1.0), np.nan)
+        nxx, nxy, nyy = ml[:, RG.ML_NXX], ml[:, RG.ML_NXY], ml[:, RG.ML_NYY]
+        lam = 0.5 * (nxx + nyy) + np.sqrt(0.25 * (nxx - nyy) ** 2 + nxy * nxy)
+        out["tilt_limit_deg"] = nan(np.arcsin(np.minimum(kk * np.sqrt(lam), 1.0)) * _DEG)
+    out["consistent"] = RG.consistent(ml, kk)
+    ratio = np.where(np.isnan(out["chi2_dof"]), -1.0, out["chi2_dof"])
+    out["worst_frames"] = np.argsort(-ratio, kind="stable")[:min(worst, int((ratio >= 0.0).sum()))].astype(np.int64)
+    used = mh[..., 0].sum(axis=0)
+    out["slot_mahal"] = np.where(used > 0.0, mh[..., 1].sum(axis=0) / np.where(used > 0.0, used, 1.0), np.nan)
+    order = np.argsort(-np.where(used > 0.0, out["slot_mahal"], -1.0), kind="stable")
+    out["worst_slots"] = order[:min(worst, int((used > 0.0).sum()))].astype(np.int64)
+    return out
+
+
+def rigid_uncertainty(eng: Engine, table, cam: L.Camera, obs_cov, source="start", reject_k=0.0, iters=8, k=3.0, taps=None,
+                      layout=None, slots=None, min_marker_size_px=5.0, piv_rel=1e-12, min_coverage=0.5, worst=5):
+    """The rigid motion of every frame under the noise of its 3-D points, and how good it is: `rigid_series`
+    (with_scale off) for the start, `solve3d_cov` with an exact camera for the covariance of every point - the weights are the pixel
+    noise `obs_cov`: a camera error moves all markers together and is no independent noise -, the source row's covariance as
+    `source_cov` where the source is a frame of the table ("start" = frame 0, or a frame number; "layout" registers against `layout`
+    [M, 3], an exact source), then `rigid_ml_series`.  Returns a dict: the device tensors `ml`, `pcov`, `coef`, `mahal`, `rigid`,
+    `residual`, `cov` and the host array `source`; per frame on the host (NaN where the frame has no weighted fit) `tilt_deg`,
+    `azimuth_deg`, `twist_deg`, `centre` [N, 3], `sigma_rot_deg` [N, 3], `sigma_centre` [N, 3] (`rigid.pose_sigma`), `t2_tilt` and
+    `significant` = t2_tilt > k^2 (two degrees of freedom: a false-alarm rate of exp(-k^2 / 2), as `misalignment_uncertainty`),
+    `twist_z` = twist / sigma_twist, `chi2_dof`, `consistent` (`rigid.consistent`), `tilt_limit_deg` = the smallest tilt the frame
+    could tell from zero in its worst direction, k sqrt(lambda_max(Sigma_n)) in degrees; `worst_frames` (largest chi2 / dof,
+    descending) and `worst_slots` (largest mean Mahalanobis distance^2 along the recording), `worst` of each; with `taps` the
+    `coef_filtered` and `trend` [N, 8] of `rigid_analysis`, from filtered matrices through `rigid.nearest_rotation`."""
+    from . import rigid as RG
+    from .engine import fir_series_f64, rigid_ml_series, rigid_series, solve3d_cov
+    table = eng._table32(table)
+    n = int(table.shape[0])
+    frame, kk, worst = _rigid_uncertainty_args(n, source, reject_k, iters, k, worst)
+    if frame is None:
+        if layout is None:
+            raise ValueError("source='layout' needs `layout` [M, 3]")
+        src = RG.source_from_layout(layout)
+    else:
+        src = RG.source_from_table(table, frame)
+    dev = eng.device.index
+    start = rigid_series(table, src, slots, False, reject_k, want=("rigid", "residual"), device=dev)
+    cov = solve3d_cov(table, cam, obs_cov, None, None, None, min_marker_size_px, piv_rel, device=dev)["cov"]
+    source_cov = None if frame is None else cov[frame].contiguous()
+    out = rigid_ml_series(table, src, cov, start["rigid"], start["residual"], source_cov, iters, piv_rel, device=dev)
+    out.update(rigid=start["rigid"], residual=start["residual"], cov=cov, source=src, k=kk)
+    out.update(rigid_uncertainty_columns(out["ml"].cpu().numpy(), out["pcov"].cpu().numpy(), out["mahal"].cpu().numpy(), kk, worst))
+    if taps is not None:
+        cf = fir_series_f64(out["coef"], taps, 3, min_coverage, device=dev)
+        ch = cf.cpu().numpy()
+        ok = (ch[:, :, 0] == 3.0).all(axis=1)
+        Rf = RG.nearest_rotation(np.where(ok[:, None, None], ch[:, :3, 1:4], np.eye(3)[None]))
+        out["coef_filtered"] = cf
+        out["trend"] = np.concatenate([ok[:, None].astype(np.float64), np.where(ok[:, None], RG.angles(Rf), 0.0),
+                                       np.where(ok[:, None], ch[:, 3, 1:4], 0.0)], axis=1)
+    return out
+
+
+RIGID_UNCERTAINTY_COLUMNS = ("frameno", "flag", "n_start", "n_used", "steps", "tilt_deg", "azimuth_deg", "twist_deg", "cx", "cy", "cz",
+                             "sigma_rot_x_deg", "sigma_rot_y_deg", "sigma_rot_z_deg", "sigma_cx", "sigma_cy", "sigma_cz", "t2_tilt",
+                             "significant", "tilt_limit_deg", "twist_z", "chi2", "dof", "chi2_dof", "chi2_start", "consistent",
+                             "step_rot", "step_c")
+
+
+def to_rigid_uncertainty_frame(result, frame_offset=0, path=None):
+    """The sheet of `rigid_uncertainty`: one row `RIGID_UNCERTAINTY_COLUMNS` per frame - the counts as integers, everything that
+    needs the weighted fit empty (NaN) where the frame has none - and with a trend also `RIGID_TREND_COLUMNS`.  `path`: also
+    written, as .csv or as .xlsx."""
+    import pandas as pd
+    from . import rigid as RG
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+    ml = host(result["ml"]).astype(np.float64)
+    if ml.ndim != 2 or ml.shape[1] != L.RIGID_ML_COLS:
+        raise ValueError(f"ml must be [N, {L.RIGID_ML_COLS}]")
+    N = ml.shape[0]
+    f64 = lambda name: np.asarray(result[name], dtype=np.float64)                                   # noqa: E731
+    cols = {"frameno": np.arange(N, dtype=np.int64) + int(frame_offset), "flag": ml[:, RG.ML_FLAG].astype(np.int64),
+            "n_start": ml[:, RG.ML_N_START].astype(np.int64), "n_used": ml[:, RG.ML_N_USED].astype(np.int64),
+            "steps": ml[:, RG.ML_STEPS].astype(np.int64), "tilt_deg": f64("tilt_deg"), "azimuth_deg": f64("azimuth_deg"),
+            "twist_deg": f64("twist_deg")}
+    for i, name in enumerate(("cx", "cy", "cz")):
+        cols[name] = f64("centre")[:, i]
+    for i, name in enumerate(("sigma_rot_x_deg", "sigma_rot_y_deg", "sigma_rot_z_deg")):
+        cols[name] = f64("sigma_rot_deg")[:, i]
+    for i, name in enumerate(("sigma_cx", "sigma_cy", "sigma_cz")):
+        cols[name] = f64("sigma_centre")[:, i]
+    have = ml[:, RG.ML_FLAG] != 0.0
+    cols.update({"t2_tilt": f64("t2_tilt"), "significant": np.asarray(result["significant"]).astype(bool),
+                 "tilt_limit_deg": f64("tilt_limit_deg"), "twist_z": f64("twist_z"), "chi2": np.where(have, ml[:, RG.ML_CHI2], np.nan),
+                 "dof": ml[:, RG.ML_DOF].astype(np.int64), "chi2_dof": f64("chi2_dof"),
+                 "chi2_start": np.where(have, ml[:, RG.ML_CHI2_START], np.nan), "consistent": np.asarray(result["consistent"]).astype(bool),
+                 "step_rot": ml[:, RG.ML_STEP_ROT], "step_c": ml[:, RG.ML_STEP_C]})
+    names = list(RIGID_UNCERTAINTY_COLUMNS)
+    if "trend" in result:
+        tr = host(result["trend"])
+        if tr.shape != (N, 8):
+            raise ValueError("trend must be [N, 8]")
+        for i, name in enumerate(RIGID_TREND_COLUMNS):
+            cols[name] = np.where(tr[:, 0] == 1.0, tr[:, 1 + i], np.nan)
+        names += list(RIGID_TREND_COLUMNS)
+    df = pd.DataFrame(cols, columns=names)
+    if path is not None:
+        if str(path).lower().endswith(".csv"):
+            df.to_csv(path, index=False)
+        else:
+            from .xlsx_io import dataframe_to_xlsx
+            dataframe_to_xlsx(df, path)
+    return df
+
+
 # ---- bonnet contact geometry along a recording (k_sphere.hip): the held sphere, the contact plane, offset, spot and normal ----------
 def bonnet_analysis(eng: Engine, table: torch.Tensor, still=(0, 8), sphere=None, contact_depth=0.1, source="start", fit_slots=None,
                     taps=None, grid=None, slots=None, piv_rel=1e-9, gap_rel=1e-3, reject_k=3.0, min_coverage=0.5):

@@ -1,6 +1,7 @@
 """Host-side companions of `analysis.rigid_series`: the point set a recording is registered to, the rotation nearest
 to a filtered matrix, the angles of a rotation, the share of the motion that is rigid and the kind of motion a row of `rigid`
-describes.  NumPy only; nothing here touches a device."""
+describes; and of `analysis.rigid_ml_series`: the standard deviations of the weighted pose, its covariance referred to
+another point and the chi-squared check.  NumPy only; nothing here touches a device."""
 import math
 
 import numpy as np
@@ -11,6 +12,10 @@ RIGID_COLS, RIGID_SWEEPS = 33, 8
 RIGID_COLUMNS = ("flag", "count", "n_used", "qmx", "qmy", "qmz", "pmx", "pmy", "pmz", "qw", "qx", "qy", "qz", "r00", "r01", "r02", "r10",
                  "r11", "r12", "r20", "r21", "r22", "tx", "ty", "tz", "scale", "rms", "rms0", "angle_deg", "tilt_deg", "azimuth_deg",
                  "twist_deg", "gap")
+RIGID_ML_COLS, RIGID_ML_PCOV_COLS = 40, 22
+(ML_FLAG, ML_N_START, ML_N_USED, ML_STEPS, ML_QW, ML_QX, ML_QY, ML_QZ) = range(8)
+(ML_R00, ML_TX, ML_CX, ML_QMX, ML_CHI2, ML_DOF, ML_CHI2_START, ML_STEP_ROT, ML_STEP_C, ML_ANGLE_DEG, ML_TILT_DEG, ML_AZIMUTH_DEG,
+ ML_TWIST_DEG, ML_NXX, ML_NXY, ML_NYY, ML_T2_TILT, ML_VAR_TWIST) = (8, 17, 20, 23, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39)
 KIND_NONE, KIND_STILL, KIND_SHIFT, KIND_TILT, KIND_TWIST, KIND_MIXED = range(6)
 KIND_NAMES = ("none", "still", "shift", "tilt", "twist", "mixed")
 _DEG = 57.29577951308232
@@ -163,3 +168,80 @@ def kind(row, shift_mm=0.05, tilt_deg=0.1, twist_deg=0.1):
     one = np.where(shift, KIND_SHIFT, np.where(tilt, KIND_TILT, KIND_TWIST))
     out = np.where(k == 0, KIND_STILL, np.where(k == 1, one, KIND_MIXED))
     return np.where(r[:, FLAG] == 0.0, KIND_NONE, out).astype(np.int64)
+
+
+# ---- the weighted pose (`rigid_ml_series`) --------------------------------------------------------------------------------------------
+def _ml_rows(ml, pcov=None):
+    a = np.asarray(ml, dtype=np.float64)
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2 or a.shape[1] != RIGID_ML_COLS:
+        raise ValueError(f"ml must be [N, {RIGID_ML_COLS}] (`rigid_ml_series`)")
+    if pcov is None:
+        return a
+    c = np.asarray(pcov, dtype=np.float64)
+    if c.ndim == 1:
+        c = c[None]
+    if c.shape != (a.shape[0], RIGID_ML_PCOV_COLS):
+        raise ValueError(f"pcov must be [N, {RIGID_ML_PCOV_COLS}], one row per row of ml")
+    return a, c
+
+
+def pose_covariance(pcov):
+    """The symmetric [N, 6, 6] over (omega in rad, c in mm) from the rows of `pcov` (NaN where its flag is 0)."""
+    c = np.asarray(pcov, dtype=np.float64)
+    if c.ndim == 1:
+        c = c[None]
+    if c.ndim != 2 or c.shape[1] != RIGID_ML_PCOV_COLS:
+        raise ValueError(f"pcov must be [N, {RIGID_ML_PCOV_COLS}] (`rigid_ml_series`)")
+    out = np.full((c.shape[0], 6, 6), np.nan)
+    at = 1
+    for i in range(6):
+        for j in range(i, 6):
+            out[:, i, j] = out[:, j, i] = c[:, at]
+            at += 1
+    out[c[:, 0] == 0.0] = np.nan
+    return out
+
+
+def pose_sigma(ml, pcov):
+    """-> (sigma_rot_deg [N, 3], sigma_c [N, 3]): the standard deviations of the three components of the rotation error omega, in
+    degrees, and of the centre c = the image of qm, in mm (NaN where the frame has no weighted fit).  Components 0 and 1 of omega
+    carry the tilt, component 2 the twist, for a body whose normal is near z."""
+    a, _ = _ml_rows(ml, pcov)
+    Cm = pose_covariance(pcov)
+    d = np.stack([Cm[:, k, k] for k in range(6)], axis=1)
+    with np.errstate(all="ignore"):
+        sg = np.sqrt(d)
+    return sg[:, :3] * _DEG, sg[:, 3:]
+
+
+def move_centre(pcov, ml, point):
+    """The covariance [N, 6, 6] of (omega, the image of `point`) from that of (omega, c = the image of qm): with lever = R (point -
+    qm) the image is c + R (point - qm), and to first order  d image = dc + omega x lever = dc - [lever]x omega.  R and qm are the
+    frame's own, read from its row of `ml` (`pcov` does not carry them).  `point` = qm is the identity; `point` = the origin gives
+    the covariance of (omega, t).  `point` is [3], or [N, 3] with one point per frame."""
+    a, _ = _ml_rows(ml, pcov)
+    Cm = pose_covariance(pcov)
+    Rm, qm = a[:, ML_R00:ML_R00 + 9].reshape(-1, 3, 3), a[:, ML_QMX:ML_QMX + 3]
+    pt = np.asarray(point, dtype=np.float64)
+    if pt.shape not in ((3,), (a.shape[0], 3)):
+        raise ValueError("point must be [3] or [N, 3]")
+    lever = np.einsum("nij,nj->ni", Rm, pt.reshape(-1, 3) - qm)
+    T = np.zeros((Cm.shape[0], 6, 6))
+    T[:, np.arange(6), np.arange(6)] = 1.0
+    # -[lever]x
+    T[:, 3, 1], T[:, 3, 2] = lever[:, 2], -lever[:, 1]
+    T[:, 4, 0], T[:, 4, 2] = -lever[:, 2], lever[:, 0]
+    T[:, 5, 0], T[:, 5, 1] = lever[:, 1], -lever[:, 0]
+    return np.einsum("nij,njk,nlk->nil", T, Cm, T)
+
+
+def consistent(ml, k=3.0):
+    """[N] bool: chi2 lies within dof +- k sqrt(2 dof), the k-sigma band of a chi-squared variable - the frame's residuals are what
+    the noise model predicts for a rigid body.  False where the frame has no weighted fit or dof < 1."""
+    a = _ml_rows(ml)
+    dof = a[:, ML_DOF]
+    ok = (a[:, ML_FLAG] == 2.0) & (dof >= 1.0)
+    with np.errstate(all="ignore"):
+        return ok & (np.abs(a[:, ML_CHI2] - dof) <= float(k) * np.sqrt(2.0 * np.where(ok, dof, 1.0)))
