@@ -42,6 +42,17 @@ static inline GrayCoef gray_coef(int bits) {
     return bits == 14 ? GrayCoef{1868u, 9617u, 4899u, 1u << 13, 14u} : GrayCoef{3735u, 19235u, 9798u, 1u << 14, 15u};
 }
 
+// The symmetric taps of k_fir, k_window_moments and k_poly_moments as a kernel argument: the centre weight, then the weights at
+// distance 1 .. n_half - 1; 0.0 beyond.  half [n_half] HOST, checked by the caller
+#define VBS_HALF_TAPS ((VBS_FIR_MAX_TAPS + 1) / 2)
+static_assert(VBS_HALF_TAPS == VBS_ENV_MAX_HALF + 1 && VBS_HALF_TAPS == VBS_KIN_MAX_HALF + 1, "one length serves the three entries");
+struct HalfTaps { double half[VBS_HALF_TAPS]; };
+static inline HalfTaps half_taps_arg(const double* half, int n_half) {
+    HalfTaps t{};
+    for (int i = 0; i < n_half; ++i) t.half[i] = half[i];
+    return t;
+}
+
 #ifdef VBS_DEBUG_KNOBS                                  // tools/ builds only: phase timing by early exit
 #include <cstdlib>
 #define VBS_KNOB(name) (getenv(name) ? atoi(getenv(name)) : 0)

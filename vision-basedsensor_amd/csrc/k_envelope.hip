@@ -1,7 +1,7 @@
 // Time-resolved amplitude and phase along a recording: the weighted sums of a sliding window at one known frequency
 // for every frame and series, and the floating-mean fit of those sums.  Float64, no atomics; a result depends on its inputs only.
-//   k_window_moments  a banded (Toeplitz) product [16 output frames x K input frames] . [K x 16 columns] on v_mfma_f64_16x16x4_f64,
-//            the third user of the lane map of k_field_map and k_project.  The columns are the FLATTENED axis
+//   k_window_moments  a banded (Toeplitz) product [16 output frames x K input frames] . [K x 16 columns] on the float64 matrix
+//            instruction (mfma_f64.h states its lane map).  The columns are the FLATTENED axis
 //            i * M + m of the output (slot i, sum m of M = 5 + 4 n_values), so a tile row is 16 contiguous doubles of `mom` and a
 //            tile may straddle slots.  A workgroup owns VBS_ENV_TILE output frames (one 16-frame tile a wave), aligned to multiples
 //            of VBS_ENV_TILE of the GLOBAL frame index whatever the range asked for, x ENV_CT column tiles: a frame meets the same
@@ -14,11 +14,10 @@
 //            zero; nothing past n or s or beyond n_values is read.  The staged rows walk the workgroup's input frames in chunks of
 //            ENV_CHUNK, double-buffered as k_project's: the next chunk's entries are fetched before this chunk's products and
 //            stored after them, one barrier a chunk.  A product outside the band is 0.0 * (a finite staged term) = 0.0 exactly.
-//            Lane map of the instruction: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], one double a lane;
-//            D[row = (lane >> 4) + 4 reg][col = lane & 15], reg 0..3.
 //   k_window_fit  one thread per (frame, slot), no barrier, nothing shared; every expression is the one include/vbs.h states,
 //            without contraction.
 #include "common.h"
+#include "mfma_f64.h"
 #pragma clang fp contract(off)
 
 #define ENV_WAVES   (VBS_ENV_TILE / 16)              // one 16-frame tile a wave
@@ -28,23 +27,18 @@
 #define ENV_CHUNK   32                               // input frames staged at a time
 #define ENV_BUF     (ENV_CHUNK * ENV_COLS)           // doubles of one staged chunk
 #define ENV_ENTRIES (ENV_BUF / ENV_THREADS)          // entries a thread stages per chunk
-#define ENV_WP      (2 * VBS_ENV_MAX_HALF + 40)      // the padded taps: 15 zeros, w[-h .. h], zeros up to the last step's reach
 static_assert(VBS_ENV_TILE % 16 == 0 && ENV_WAVES >= 1 && ENV_THREADS <= 1024, "a workgroup is a whole number of 16-frame tiles");
 static_assert(ENV_COLS == 64, "a thread stages one column: its lane");
 static_assert(ENV_CHUNK % 16 == 0 && ENV_BUF % ENV_THREADS == 0, "a wave's steps never straddle a chunk; equal staging shares");
-static_assert(2 * VBS_ENV_MAX_HALF + 1 <= VBS_FIR_MAX_TAPS && ENV_WAVES * 32 == VBS_ENV_MAX_HALF + 1, "the taps travel as the FIR's, 32 a wave");
-static_assert((2 * ENV_BUF + ENV_WP) * 8 <= 64 * 1024, "two staged chunks and the taps fit the LDS a workgroup gets without asking");
-
-struct EnvTaps { double half[VBS_ENV_MAX_HALF + 1]; };           // centre weight, then the weights at distance 1 .. h; 0.0 beyond
-
-typedef double env_acc __attribute__((ext_vector_type(4)));
+static_assert(ENV_WAVES * 32 == VBS_HALF_TAPS, "the taps travel 32 a wave");
+static_assert((2 * ENV_BUF + BAND_ROW) * 8 <= 64 * 1024, "two staged chunks and the taps fit the LDS a workgroup gets without asking");
 
 __global__ __launch_bounds__(ENV_THREADS) void k_window_moments(const double* __restrict__ rec, int n, int s, int cols, int nv,
-                                                                const double* __restrict__ carrier, EnvTaps taps, int h,
+                                                                const double* __restrict__ carrier, HalfTaps taps, int h,
                                                                 int frame_begin, int frame_end, int tile_first,
                                                                 double* __restrict__ mom) {
     __shared__ __attribute__((aligned(16))) double stage[2 * ENV_BUF];   // [buffer][column tile][input row][16]
-    __shared__ double wp[ENV_WP];
+    __shared__ double wp[BAND_ROW];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -57,10 +51,10 @@ __global__ __launch_bounds__(ENV_THREADS) void k_window_moments(const double* __
     const int rows = 16 * (ENV_WAVES - 1) + 4 * steps;                   // input rows of the workgroup: row p is frame F0 - h + p
     const int chunks = (rows + ENV_CHUNK - 1) / ENV_CHUNK;
 
-    // the padded taps: wp[15 + h + d] = w[d], |d| <= h; 0.0 elsewhere.  Wave w holds half[32 w + lane] (uniform loads, one select a
-    // lane) and writes both of its places
-    for (int i = tid; i < ENV_WP; i += ENV_THREADS) {
-        const int d = i - 15 - h;
+    // the padded taps: wp[BAND_PAD + h + d] = w[d], |d| <= h; 0.0 elsewhere.  Wave w holds half[32 w + lane] (uniform loads, one
+    // select a lane) and writes both of its places
+    for (int i = tid; i < BAND_ROW; i += ENV_THREADS) {
+        const int d = i - BAND_PAD - h;
         if (d < -h || d > h) wp[i] = 0.0;
     }
     {
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(ENV_THREADS) void k_window_moments(const double* __
             mine = lane == k ? t : mine;
         }
         const int d = wave * 32 + lane;
-        if (lane < 32 && d <= h) { wp[15 + h + d] = mine; wp[15 + h - d] = mine; }
+        if (lane < 32 && d <= h) { wp[BAND_PAD + h + d] = mine; wp[BAND_PAD + h - d] = mine; }
     }
 
     // this thread's column of the workgroup: slot, sum, and what its term is made of.  kind 0: 1; 1: the carrier row `crow`;
@@ -117,9 +111,9 @@ __global__ __launch_bounds__(ENV_THREADS) void k_window_moments(const double* __
     const bool live = f0 < frame_end && f0 + 16 > frame_begin;           // it emits something (it stages and waits either way)
     const int w_lo = 16 * wave, w_hi = 16 * wave + 4 * steps;            // its input rows, of the workgroup's
 
-    env_acc acc[ENV_CT];
+    f64x4 acc[ENV_CT];
 #pragma unroll
-    for (int ct = 0; ct < ENV_CT; ++ct) acc[ct] = env_acc{0.0, 0.0, 0.0, 0.0};
+    for (int ct = 0; ct < ENV_CT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
     double v[ENV_ENTRIES][3];
     gather(0, v);
     store(0, stage, v);
@@ -132,12 +126,12 @@ __global__ __launch_bounds__(ENV_THREADS) void k_window_moments(const double* __
             const int lo = w_lo > ch * ENV_CHUNK ? w_lo : ch * ENV_CHUNK;
             const int hi = w_hi < (ch + 1) * ENV_CHUNK ? w_hi : (ch + 1) * ENV_CHUNK;
             for (int p = lo; p < hi; p += 4) {
-                const double av = wp[p - w_lo + q - r + 15];             // A[r][k], k = p - w_lo + q
+                const double av = wp[p - w_lo + q - r + BAND_PAD];       // A[r][k], k = p - w_lo + q
                 const int lrow = p - ch * ENV_CHUNK + q;
 #pragma unroll
                 for (int ct = 0; ct < ENV_CT; ++ct) {
                     const double b = buf[(ct * ENV_CHUNK + lrow) * 16 + r];
-                    acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b, acc[ct], 0, 0, 0);
+                    acc[ct] = mfma_f64(av, b, acc[ct]);
                 }
             }
         }
@@ -158,16 +152,13 @@ __global__ __launch_bounds__(ENV_THREADS) void k_window_moments(const double* __
     }
 }
 
-// half [n_half] HOST, checked by the caller
 void launch_window_moments(const double* rec, int n, int s, int cols, int n_values, const double* carrier, const double* half,
                            int n_half, int frame_begin, int frame_end, double* mom, hipStream_t st) {
-    EnvTaps t{};
-    for (int i = 0; i < n_half; ++i) t.half[i] = half[i];
-    const int first = frame_begin / VBS_ENV_TILE, last = (frame_end - 1) / VBS_ENV_TILE;
+    int first;
     const int64_t C = (int64_t)s * (5 + 4 * n_values);
-    const dim3 grid((unsigned)(last - first + 1), (unsigned)((C + ENV_COLS - 1) / ENV_COLS));
-    hipLaunchKernelGGL(k_window_moments, grid, dim3(ENV_THREADS), 0, st, rec, n, s, cols, n_values, carrier, t, n_half - 1,
-                       frame_begin, frame_end, first, mom);
+    const dim3 grid((unsigned)band_tiles(frame_begin, frame_end, VBS_ENV_TILE, &first), (unsigned)((C + ENV_COLS - 1) / ENV_COLS));
+    hipLaunchKernelGGL(k_window_moments, grid, dim3(ENV_THREADS), 0, st, rec, n, s, cols, n_values, carrier,
+                       half_taps_arg(half, n_half), n_half - 1, frame_begin, frame_end, first, mom);
 }
 
 __global__ __launch_bounds__(256) void k_window_fit(const double* __restrict__ mom, int64_t count, int nv, double need,

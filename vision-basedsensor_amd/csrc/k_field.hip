@@ -1,6 +1,6 @@
 // Contact maps along a recording: a gap-aware normalised kernel smoother in space, the spatial counterpart of
 // k_fir, and the contact patch of every map.  Float64, no atomics; a result depends on its inputs only, never on the launch shape.
-//   k_field_map<NT>  [P grid points x s slots] . [s x 16 columns] on v_mfma_f64_16x16x4_f64.  The 16 columns of a tile are
+//   k_field_map<NT>  [P grid points x s slots] . [s x 16 columns] by mfma_f64 of mfma_f64.h.  The 16 columns of a tile are
 //            VBS_FIELD_FRAMES = 4 frames x (x1, x2, x3, flag as 1.0 / 0.0), so the flag column's product IS den.  A workgroup takes
 //            NT frame tiles (4, 2 or 1 by s, so that the staged values fit FIELD_LDS_MAX), stages their SELECTED values once in LDS
 //            - an invalid entry, a column beyond n_values, a slot >= s or a frame past the range is the constant 0.0 and is never
@@ -10,11 +10,10 @@
 //            contiguous 32-byte run, and uses element e in step e, so step e multiplies slots k0 + 4q + e, q = 0..3.  The staged
 //            rows are stored in that order (slot k0 + 4q + e at row k0 + 4e + q): a step reads 64 consecutive doubles of LDS.
 //            The order of summation is not part of the interface (include/vbs.h); every frame tile meets the same order.
-//            Lane map of the instruction: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], one double a lane;
-//            D[row = (lane >> 4) + 4 reg][col = lane & 15], reg 0..3.
 //   k_patch_stats   one wave per frame, VBS_PATCH_GROUP frames (waves) a workgroup, nothing shared; every sum follows the rule of
 //            k_axis_displacement (lane l adds points l, l + 64, .. ascending, then the fold 32, 16, 8, 4, 2, 1), without contraction.
 #include "common.h"
+#include "mfma_f64.h"
 #include "wave_fold.h"
 #pragma clang fp contract(off)
 
@@ -24,8 +23,6 @@
 #define FIELD_COLS    (VBS_FIELD_FRAMES * 4)     // columns of a tile
 static_assert(FIELD_COLS == 16, "a tile is 16 columns: 4 frames x (3 values, flag)");
 static_assert(((VBS_FIELD_MAX_SLOTS + 15) & ~15) * FIELD_COLS * 8 <= FIELD_LDS_MAX, "one frame tile of the longest record fits");
-
-typedef double field_acc __attribute__((ext_vector_type(4)));
 
 template <int NT>
 __global__ __launch_bounds__(FIELD_THREADS) void k_field_map(const double* __restrict__ rec, int s, int cols, int nv,
@@ -65,16 +62,16 @@ __global__ __launch_bounds__(FIELD_THREADS) void k_field_map(const double* __res
         const int p = t * 16 + r;
         const bool prow = p < P;
         const double* wr = W + (int64_t)(prow ? p : P - 1) * s + 4 * q;  // (a row of W in every lane; a row >= P is selected to 0.0)
-        field_acc acc[NT];
+        f64x4 acc[NT];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = field_acc{0.0, 0.0, 0.0, 0.0};
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = f64x4{0.0, 0.0, 0.0, 0.0};
         auto products = [&](int k0, const double* a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const double b = stage[(int64_t)(nt * s16 + k0 + 4 * e + q) * FIELD_COLS + r];
-                    acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(prow ? a[e] : 0.0, b, acc[nt], 0, 0, 0);
+                    acc[nt] = mfma_f64(prow ? a[e] : 0.0, b, acc[nt]);
                 }
             }
         };

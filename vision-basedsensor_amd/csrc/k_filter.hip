@@ -16,10 +16,8 @@
 #define FIR_ROWS  16                     // input rows staged in LDS at a time: 16 x 64 x (NV + 1) doubles, 32 KB at NV = 3
 static_assert(VBS_FIR_TILE % FIR_P == 0 && FIR_WAVES >= 1 && FIR_WAVES <= 16, "a tile is a whole number of waves");
 
-struct FirTaps { double half[(VBS_FIR_MAX_TAPS + 1) / 2]; };     // centre tap, then the taps at distance 1 .. n_half - 1
-
 template <int NV>
-__global__ __launch_bounds__(FIR_WAVES * 64) void k_fir(const double* __restrict__ rec, int n, int s, int cols, FirTaps taps,
+__global__ __launch_bounds__(FIR_WAVES * 64) void k_fir(const double* __restrict__ rec, int n, int s, int cols, HalfTaps taps,
                                                         int h, double need, int frame_begin, int frame_end,
                                                         double* __restrict__ out) {
     __shared__ double stage[FIR_ROWS][NV + 1][64];
@@ -99,8 +97,7 @@ __global__ __launch_bounds__(FIR_WAVES * 64) void k_fir(const double* __restrict
 // half [n_half] HOST.  need = min_coverage * sw, sw = the ascending sum of all 2 n_half - 1 taps (one IEEE product of the two).
 void launch_fir_series(const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half, double need,
                        int frame_begin, int frame_end, double* out, hipStream_t st) {
-    FirTaps t{};
-    for (int i = 0; i < n_half; ++i) t.half[i] = half[i];
+    const HalfTaps t = half_taps_arg(half, n_half);
     const dim3 grid((unsigned)(((int64_t)frame_end - frame_begin + VBS_FIR_TILE - 1) / VBS_FIR_TILE), (unsigned)((s + 63) / 64));
     const dim3 block(FIR_WAVES * 64);
 #define FIR_CASE(NV)                                                                                                          \

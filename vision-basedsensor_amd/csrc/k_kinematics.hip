@@ -1,8 +1,8 @@
 // Marker velocity, acceleration and gap filling along a recording: the moments of a gap-aware weighted local
 // polynomial fit (Savitzky-Golay with the gaps selected out) for every frame and series, and the fit of every window with its
 // fallback in degree.  Float64, no atomics; a result depends on its inputs only.
-//   k_poly_moments<D>  a banded (Toeplitz) product on v_mfma_f64_16x16x4_f64, the fourth user of the lane map of k_field_map,
-//            k_project and k_window_moments, and a new shape of it: SEVERAL bands over ONE staged operand.  The 2D + 1 tap rows
+//   k_poly_moments<D>  a banded (Toeplitz) product on the float64 matrix instruction (mfma_f64.h states its lane map) in a shape
+//            of its own: SEVERAL bands over ONE staged operand.  The 2D + 1 tap rows
 //            t_k[delta] = w[delta] u^k (u = delta / H, H a power of two, u^k exact, so one rounding a tap) each make their own A
 //            fragment, A_k[r][j] = t_k[j - r - h] inside the band and 0.0 outside, read from a zero-padded copy of the row in LDS
 //            (`wp`) as k_window_moments reads its one row.  B, staged ONCE per (input frame, slot) and chunk, is the SELECTED
@@ -21,14 +21,14 @@
 //            staged rows walk the workgroup's input frames in chunks of KIN_CHUNK, double-buffered: the next chunk's entries are
 //            fetched before this chunk's products and stored after them, one barrier a chunk.  A product outside the band is
 //            0.0 * (a finite staged term) = 0.0 exactly.
-//            Lane map of the instruction: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], one double a lane;
-//            D[row = (lane >> 4) + 4 reg][col = lane & 15], reg 0..3.
 //            LDS: a B fragment is 64 consecutive doubles (4 rows x 16 columns), an A fragment 19 consecutive doubles read with
 //            repeats, both free of bank conflicts; the staging writes of a wave fall on 4 of the 16 double-wide write banks, which
 //            costs about 150 cycles a chunk beside the chunk's 4 x 23 products.
 //   k_poly_fit<D>  one thread per (frame, slot), no barrier, nothing shared; every expression is the one include/vbs.h states,
 //            without contraction.
 #include "common.h"
+#include "mfma_f64.h"
+#include <type_traits>
 #pragma clang fp contract(off)
 
 #define KIN_WAVES   (VBS_KIN_TILE / 16)              // one 16-frame tile a wave
@@ -37,28 +37,24 @@
 #define KIN_TILES   9                                // staged tiles: 4 of values, 4 of squares, 1 of flags
 #define KIN_CHUNK   16                               // input frames staged at a time
 #define KIN_BUF     (KIN_TILES * KIN_CHUNK * 16)     // doubles of one staged chunk
-#define KIN_WP      (2 * VBS_KIN_MAX_HALF + 40)      // a padded tap row: 15 zeros, t[-h .. h], zeros up to the last step's reach
 #define KIN_ROWS    (2 * VBS_KIN_MAX_DEGREE + 1)     // tap rows at most
 static_assert(VBS_KIN_TILE % 16 == 0 && KIN_WAVES >= 1 && KIN_THREADS <= 1024, "a workgroup is a whole number of 16-frame tiles");
 static_assert(KIN_THREADS == KIN_CHUNK * KIN_SLOTS, "a thread stages one (input frame, slot) a chunk");
 static_assert(KIN_CHUNK % 16 == 0, "a wave's steps never straddle a chunk");
-static_assert(KIN_WAVES * 32 == VBS_KIN_MAX_HALF + 1, "the weights travel 32 a wave");
-static_assert((2 * KIN_BUF + KIN_ROWS * KIN_WP + VBS_KIN_MAX_HALF + 1) * 8 <= 64 * 1024,
+static_assert(KIN_WAVES * 32 == VBS_HALF_TAPS, "the weights travel 32 a wave");
+static_assert((2 * KIN_BUF + KIN_ROWS * BAND_ROW + VBS_HALF_TAPS) * 8 <= 64 * 1024,
               "two staged chunks, the tap rows and the weights fit the LDS a workgroup gets without asking");
 
-struct KinTaps { double half[VBS_KIN_MAX_HALF + 1]; };           // centre weight, then the weights at distance 1 .. h; 0.0 beyond
 struct KinThr { double t[VBS_KIN_MAX_DEGREE + 1]; };
-
-typedef double kin_acc __attribute__((ext_vector_type(4)));
 
 template <int D>
 __global__ __launch_bounds__(KIN_THREADS) void k_poly_moments(const double* __restrict__ rec, int n, int s, int cols, int nv,
-                                                              KinTaps taps, int h, double inv_H, int frame_begin, int frame_end,
+                                                              HalfTaps taps, int h, double inv_H, int frame_begin, int frame_end,
                                                               int tile_first, double* __restrict__ mom) {
     constexpr int R = 2 * D + 1;                                         // tap rows
     __shared__ __attribute__((aligned(32))) double stage[2 * KIN_BUF];   // [buffer][tile][input row][16]
-    __shared__ double wp[R * KIN_WP];
-    __shared__ double wh[VBS_KIN_MAX_HALF + 1];
+    __shared__ double wp[R * BAND_ROW];
+    __shared__ double wh[VBS_HALF_TAPS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -81,11 +77,11 @@ __global__ __launch_bounds__(KIN_THREADS) void k_poly_moments(const double* __re
         if (lane < 32) wh[wave * 32 + lane] = mine;
     }
     __syncthreads();
-    // the padded tap rows: wp[k][15 + h + d] = w[|d|] * u^k, u = d / H, |d| <= h; 0.0 elsewhere.  u^k by repeated multiplication,
-    // every product exact (|d|^k < 2^42), so the tap is rounded once
-    for (int i = tid; i < R * KIN_WP; i += KIN_THREADS) {
-        const int k = i / KIN_WP;
-        const int d = i - k * KIN_WP - 15 - h;
+    // the padded tap rows: wp[k][BAND_PAD + h + d] = w[|d|] * u^k, u = d / H, |d| <= h; 0.0 elsewhere.  u^k by repeated
+    // multiplication, every product exact (|d|^k < 2^42), so the tap is rounded once
+    for (int i = tid; i < R * BAND_ROW; i += KIN_THREADS) {
+        const int k = i / BAND_ROW;
+        const int d = i - k * BAND_ROW - BAND_PAD - h;
         double t = 0.0;
         if (d >= -h && d <= h) {
             const double u = (double)d * inv_H;
@@ -129,15 +125,15 @@ __global__ __launch_bounds__(KIN_THREADS) void k_poly_moments(const double* __re
     const bool live = f0 < frame_end && f0 + 16 > frame_begin;           // it emits something (it stages and waits either way)
     const int w_lo = 16 * wave, w_hi = 16 * wave + 4 * steps;            // its input rows, of the workgroup's
 
-    kin_acc accv[4][D + 1], accs[4], accf[D > 0 ? D : 1];
+    f64x4 accv[4][D + 1], accs[4], accf[D > 0 ? D : 1];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        accs[t] = kin_acc{0.0, 0.0, 0.0, 0.0};
+        accs[t] = f64x4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int k = 0; k <= D; ++k) accv[t][k] = kin_acc{0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k <= D; ++k) accv[t][k] = f64x4{0.0, 0.0, 0.0, 0.0};
     }
 #pragma unroll
-    for (int k = 0; k < (D > 0 ? D : 1); ++k) accf[k] = kin_acc{0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < (D > 0 ? D : 1); ++k) accf[k] = f64x4{0.0, 0.0, 0.0, 0.0};
 
     double v[4];
     gather(0, v);
@@ -151,26 +147,26 @@ __global__ __launch_bounds__(KIN_THREADS) void k_poly_moments(const double* __re
             const int lo = w_lo > ch * KIN_CHUNK ? w_lo : ch * KIN_CHUNK;
             const int hi = w_hi < (ch + 1) * KIN_CHUNK ? w_hi : (ch + 1) * KIN_CHUNK;
             for (int p = lo; p < hi; p += 4) {
-                const int ai = p - w_lo + q - r + 15;                    // A_k[r][j], j = p - w_lo + q
+                const int ai = p - w_lo + q - r + BAND_PAD;              // A_k[r][j], j = p - w_lo + q
                 double av[R];
 #pragma unroll
-                for (int k = 0; k < R; ++k) av[k] = wp[k * KIN_WP + ai];
+                for (int k = 0; k < R; ++k) av[k] = wp[k * BAND_ROW + ai];
                 const int lrow = p - ch * KIN_CHUNK + q;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const double b = buf[(t * KIN_CHUNK + lrow) * 16 + r];
 #pragma unroll
-                    for (int k = 0; k <= D; ++k) accv[t][k] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[k], b, accv[t][k], 0, 0, 0);
+                    for (int k = 0; k <= D; ++k) accv[t][k] = mfma_f64(av[k], b, accv[t][k]);
                 }
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const double b = buf[((4 + t) * KIN_CHUNK + lrow) * 16 + r];
-                    accs[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], b, accs[t], 0, 0, 0);
+                    accs[t] = mfma_f64(av[0], b, accs[t]);
                 }
                 if constexpr (D > 0) {
                     const double b = buf[(8 * KIN_CHUNK + lrow) * 16 + r];
 #pragma unroll
-                    for (int k = 0; k < D; ++k) accf[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[D + 1 + k], b, accf[k], 0, 0, 0);
+                    for (int k = 0; k < D; ++k) accf[k] = mfma_f64(av[D + 1 + k], b, accf[k]);
                 }
             }
         }
@@ -215,25 +211,26 @@ static int kin_scale(int h) {
     return H;
 }
 
-// half [n_half] HOST, checked by the caller
+// launch(D) with the degree as a constant: the kernels are compiled per degree
+template <class Launch> static void kin_by_degree(int degree, Launch launch) {
+    switch (degree) {
+        case 0: launch(std::integral_constant<int, 0>{}); break;
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        default: launch(std::integral_constant<int, 3>{}); break;
+    }
+}
+
 void launch_poly_moments(const double* rec, int n, int s, int cols, int n_values, const double* half, int n_half, int degree,
                          int frame_begin, int frame_end, double* mom, hipStream_t st) {
-    KinTaps t{};
-    for (int i = 0; i < n_half; ++i) t.half[i] = half[i];
     const int h = n_half - 1;
     const double inv_H = 1.0 / (double)kin_scale(h);
-    const int first = frame_begin / VBS_KIN_TILE, last = (frame_end - 1) / VBS_KIN_TILE;
-    const dim3 grid((unsigned)(last - first + 1), (unsigned)((s + KIN_SLOTS - 1) / KIN_SLOTS));
-#define KIN_LAUNCH(D_)                                                                                                            \
-    hipLaunchKernelGGL(k_poly_moments<D_>, grid, dim3(KIN_THREADS), 0, st, rec, n, s, cols, n_values, t, h, inv_H, frame_begin,  \
-                       frame_end, first, mom)
-    switch (degree) {
-        case 0: KIN_LAUNCH(0); break;
-        case 1: KIN_LAUNCH(1); break;
-        case 2: KIN_LAUNCH(2); break;
-        default: KIN_LAUNCH(3); break;
-    }
-#undef KIN_LAUNCH
+    int first;
+    const dim3 grid((unsigned)band_tiles(frame_begin, frame_end, VBS_KIN_TILE, &first), (unsigned)((s + KIN_SLOTS - 1) / KIN_SLOTS));
+    kin_by_degree(degree, [&](auto D) {
+        hipLaunchKernelGGL(k_poly_moments<decltype(D)::value>, grid, dim3(KIN_THREADS), 0, st, rec, n, s, cols, n_values,
+                           half_taps_arg(half, n_half), h, inv_H, frame_begin, frame_end, first, mom);
+    });
 }
 
 template <int D>
@@ -339,14 +336,8 @@ void launch_poly_fit(const double* mom, const double* rec, int s, int cols, int 
     const double inv_H = 1.0 / (double)kin_scale(half_window);
     const int64_t count = (int64_t)(frame_end - frame_begin) * s;
     const dim3 grid((unsigned)((count + 255) / 256));
-#define KIN_LAUNCH(D_)                                                                                                            \
-    hipLaunchKernelGGL(k_poly_fit<D_>, grid, dim3(256), 0, st, mom, rec, s, cols, n_values, frame_begin, count, t, inv_H,         \
-                       fill_degree, fit, filled)
-    switch (degree) {
-        case 0: KIN_LAUNCH(0); break;
-        case 1: KIN_LAUNCH(1); break;
-        case 2: KIN_LAUNCH(2); break;
-        default: KIN_LAUNCH(3); break;
-    }
-#undef KIN_LAUNCH
+    kin_by_degree(degree, [&](auto D) {
+        hipLaunchKernelGGL(k_poly_fit<decltype(D)::value>, grid, dim3(256), 0, st, mom, rec, s, cols, n_values, frame_begin, count,
+                           t, inv_H, fill_degree, fit, filled);
+    });
 }

@@ -1,7 +1,7 @@
 // Principal modes of the displacement field along a recording: the cross moments of all pairs of series, the
 // covariance they give, its leading eigenpairs by orthogonal iteration, and the score of every mode in every frame.  Float64, no
 // atomics, no wait across workgroups; a result depends on its inputs only.
-//   k_cross_moments  the symmetric product [4 s x n] . [n x 4 s] on v_mfma_f64_16x16x4_f64, the next user of the lane map and of the
+//   k_cross_moments  the symmetric product [4 s x n] . [n x 4 s] by mfma_f64 of mfma_f64.h, the next user of the lane map and of the
 //            fragment scheme of k_project (k_spectrum.hip), with the frame axis as K.  Per slot the staged columns are
 //            (z1, z2, z3, flag as 1.0 / 0.0), z = x - shift rounded once when a valid entry is staged: k_project's tile column set, so
 //            a 16-column tile is 4 slots.  A workgroup owns one PAIR of slot tiles (ti <= tj) of VBS_MOM_WG_SLOTS slots each: both
@@ -16,8 +16,6 @@
 //            doubles of LDS per operand.  On the diagonal (ti == tj) one staged tile is both operands.
 //            The workgroup writes its block and the mirror block: mom[j, i, w, v] is a copy of mom[i, j, v, w], and on the diagonal
 //            only the entries with 4 i + v <= 4 j + w are taken from the accumulators, so every cell has one writer and one value.
-//            Lane map of the instruction: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], one double a lane;
-//            D[row = (lane >> 4) + 4 reg][col = lane & 15], reg 0..3.
 //   k_covariance  one thread per slot pair i <= j; every expression is the one include/vbs.h states, without contraction.
 //   k_modes_apply  Y = A Q, one wave per row of A, lane l adds columns l, l + 64, .. ascending for all r vectors, the fold is 32,
 //            16, 8, 4, 2, 1: the kernel is bound by reading A and has no matrix instruction.
@@ -25,6 +23,7 @@
 //            is read and written by one thread and only the sums need a barrier (one each, the LDS slot alternates).
 //   k_mode_scores  one wave per frame, VBS_SCORE_GROUP frames a workgroup, no barrier, nothing shared.
 #include "common.h"
+#include "mfma_f64.h"
 #include "wave_fold.h"
 #pragma clang fp contract(off)
 
@@ -37,9 +36,7 @@
 static_assert(VBS_MOM_WG_SLOTS == 16, "the staging index splits an entry into (frame, slot of 16)");
 static_assert(VBS_MOM_CHUNK % 16 == 0 && (VBS_MOM_CHUNK * VBS_MOM_WG_SLOTS) % MOM_THREADS == 0, "tile multiples; equal staging shares");
 static_assert(4 * MOM_TILE * 8 <= 64 * 1024, "two staged chunks of two slot tiles fit the LDS a workgroup gets without asking");
-static_assert(MOM_THREADS <= 1024 && MOM_THREADS % 16 == 0, "a workgroup; a thread stages one slot of its tile");
-
-typedef double mom_acc __attribute__((ext_vector_type(4)));
+static_assert(MOM_THREADS <= 1024, "a workgroup");
 
 __global__ __launch_bounds__(MOM_THREADS) void k_cross_moments(const double* __restrict__ rec, int n, int s, int cols, int nv,
                                                                const double* __restrict__ shift, int tiles,
@@ -67,17 +64,8 @@ __global__ __launch_bounds__(MOM_THREADS) void k_cross_moments(const double* __r
             sh[o][0] = e[0]; sh[o][1] = e[nv > 1 ? 1 : 0]; sh[o][2] = e[nv > 2 ? 2 : 0];
         }
     }
-    // the entries of chunk `f0` this thread stages, as they lie in the record (x1, x2, x3, flag).  No branch and no load that waits
-    // for another: a slot >= s or a frame >= n fetches the record's last slot or frame instead, a column beyond n_values the flag
-    // again; nothing past n or s or beyond n_values is read
-    auto gather = [&](int f0, int m0, double (&v)[MOM_ENTRIES][4]) {
-#pragma unroll
-        for (int j = 0; j < MOM_ENTRIES; ++j) {
-            const int m = m0 + sl, f = f0 + ((tid + j * MOM_THREADS) >> 4);
-            const double* e = rec + ((int64_t)(f < n ? f : n - 1) * s + (m < s ? m : s - 1)) * cols;
-            v[j][3] = e[0]; v[j][0] = e[1]; v[j][1] = e[nv > 1 ? 2 : 0]; v[j][2] = e[nv > 2 ? 3 : 0];
-        }
-    };
+    // the entries of chunk `f0` this thread stages, fetched as quad_gather says
+    auto gather = [&](int f0, int m0, double (&v)[MOM_ENTRIES][4]) { quad_gather<MOM_THREADS>(rec, n, s, cols, nv, f0, m0, tid, v); };
     // ... SELECTED by the flag when they are staged (after the products that ran while they were in flight), the shift subtracted
     // once: the value of an invalid entry never reaches an operation
     auto store = [&](int f0, int m0, const double (&sft)[3], double* buf, const double (&v)[MOM_ENTRIES][4]) {
@@ -95,9 +83,9 @@ __global__ __launch_bounds__(MOM_THREADS) void k_cross_moments(const double* __r
     };
 
     const bool live = i0 + wave * 4 < s;                                 // this wave has a row tile (it stages and waits either way)
-    mom_acc acc[MOM_CT];
+    f64x4 acc[MOM_CT];
 #pragma unroll
-    for (int ct = 0; ct < MOM_CT; ++ct) acc[ct] = mom_acc{0.0, 0.0, 0.0, 0.0};
+    for (int ct = 0; ct < MOM_CT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
     double vi[MOM_ENTRIES][4], vj[MOM_ENTRIES][4];
     gather(0, i0, vi);
     if (!diag) gather(0, j0, vj);
@@ -123,7 +111,7 @@ __global__ __launch_bounds__(MOM_THREADS) void k_cross_moments(const double* __r
 #pragma unroll
                     for (int ct = 0; ct < MOM_CT; ++ct) {
                         const double b = bb[(ct * VBS_MOM_CHUNK + row) * 16 + r];
-                        acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b, acc[ct], 0, 0, 0);
+                        acc[ct] = mfma_f64(av, b, acc[ct]);
                     }
                 }
             }

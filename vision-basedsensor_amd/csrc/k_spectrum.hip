@@ -1,6 +1,6 @@
 // Displacement spectra along a recording: the gap-aware projection of every series onto a basis the caller gives, and
 // the floating-mean harmonic fit of those projections.  Float64, no atomics; a result depends on its inputs only.
-//   k_project  [R basis rows x n frames] . [n x 16 columns] on v_mfma_f64_16x16x4_f64, the second user of the lane map and of the
+//   k_project  [R basis rows x n frames] . [n x 16 columns] by mfma_f64 of mfma_f64.h, the second user of the lane map and of the
 //            fragment scheme of k_field_map (k_field.hip), with the LONG axis as K.  The 16 columns of a tile are
 //            VBS_PROJ_SLOTS = 4 slots x (x1, x2, x3, flag as 1.0 / 0.0), so the flag column's product IS den.  A workgroup owns
 //            VBS_PROJ_ROWS rows x VBS_PROJ_WG_SLOTS slots: wave w takes row tile w against all PROJ_CT column tiles, and keeps its
@@ -15,12 +15,11 @@
 //            multiplies frames k0 + 4q + e, q = 0..3.  The staged rows are stored in that order (frame k0 + 4q + e at row
 //            k0 + 4e + q) and column tile by column tile ([tile][row][16]): a step reads 64 consecutive doubles of LDS.
 //            The order of summation is not part of the interface (include/vbs.h); every output meets the same order.
-//            Lane map of the instruction: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15], one double a lane;
-//            D[row = (lane >> 4) + 4 reg][col = lane & 15], reg 0..3.
 //   k_harmonic_fit  one wave per slot, VBS_FIT_GROUP slots (waves) a workgroup, no barrier, nothing shared.  Lane l takes bins l,
 //            l + 64, .. ascending; every expression is the one include/vbs.h states, without contraction; the peak folds 32, 16,
 //            8, 4, 2, 1 with the tie rule of k_patch_stats.
 #include "common.h"
+#include "mfma_f64.h"
 #include <type_traits>
 #pragma clang fp contract(off)
 
@@ -38,8 +37,6 @@ static_assert((VBS_PROJ_CHUNK * VBS_PROJ_WG_SLOTS) % PROJ_THREADS == 0, "every t
 static_assert(2 * PROJ_BUF * 8 <= 64 * 1024, "two staged chunks fit the LDS a workgroup gets without asking");
 static_assert(PROJ_THREADS <= 1024, "a workgroup");
 
-typedef double proj_acc __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(PROJ_THREADS) void k_project(const double* __restrict__ rec, int n, int s, int cols, int nv,
                                                           const double* __restrict__ basis, int R, double* __restrict__ proj) {
     __shared__ __attribute__((aligned(16))) double stage[2 * PROJ_BUF];  // [buffer][column tile][frame row, permuted][16]
@@ -50,18 +47,8 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project(const double* __restri
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
 
-    // the entries of chunk `f0` this thread stages, as they lie in the record (x1, x2, x3, flag).  No branch and no load that waits
-    // for another: a slot >= s or a frame >= n fetches the record's last slot or frame instead, a column beyond n_values the flag
-    // again; nothing past n or s or beyond n_values is read
-    auto gather = [&](int f0, double (&v)[PROJ_ENTRIES][4]) {
-#pragma unroll
-        for (int j = 0; j < PROJ_ENTRIES; ++j) {
-            const int i = tid + j * PROJ_THREADS;
-            const int m = s0 + (i & 15), f = f0 + (i >> 4);
-            const double* e = rec + ((int64_t)(f < n ? f : n - 1) * s + (m < s ? m : s - 1)) * cols;
-            v[j][3] = e[0]; v[j][0] = e[1]; v[j][1] = e[nv > 1 ? 2 : 0]; v[j][2] = e[nv > 2 ? 3 : 0];
-        }
-    };
+    // the entries of chunk `f0` this thread stages, fetched as quad_gather says
+    auto gather = [&](int f0, double (&v)[PROJ_ENTRIES][4]) { quad_gather<PROJ_THREADS>(rec, n, s, cols, nv, f0, s0, tid, v); };
     // ... SELECTED by the flag when they are staged (after the products that ran while they were in flight): the value of an
     // invalid entry never reaches an operation
     auto store = [&](int f0, double* buf, const double (&v)[PROJ_ENTRIES][4]) {
@@ -100,9 +87,9 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project(const double* __restri
         }
     };
 
-    proj_acc acc[PROJ_CT];
+    f64x4 acc[PROJ_CT];
 #pragma unroll
-    for (int ct = 0; ct < PROJ_CT; ++ct) acc[ct] = proj_acc{0.0, 0.0, 0.0, 0.0};
+    for (int ct = 0; ct < PROJ_CT; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
     double v[PROJ_ENTRIES][4], a0[4 * PROJ_KB], a1[4 * PROJ_KB];
     // one chunk: the next chunk's entries and A values are asked for, this chunk's products run on `a` and stage buffer `cur`, the
     // next chunk is staged into the other buffer.  STEADY: a complete next chunk is known to exist, so the body has no branch and
@@ -128,7 +115,7 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project(const double* __restri
 #pragma unroll
                     for (int ct = 0; ct < PROJ_CT; ++ct) {
                         const double b = buf[(ct * VBS_PROJ_CHUNK + kb * 16 + 4 * e + q) * PROJ_COLS + r];
-                        acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b, acc[ct], 0, 0, 0);
+                        acc[ct] = mfma_f64(av, b, acc[ct]);
                     }
                 }
             }
